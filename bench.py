@@ -2,7 +2,7 @@
 """bench.py — BEV frames/s of the MI355X-native CoBEVT hot path on synthetic OPV2V-shaped inputs.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--dtype bf16|fp32] [--agents 5] [--workload camera|lidar]
-                    [--mode throughput|latency] [--frames-in-flight 3|4|1] [--no-graph]
+                    [--mode throughput|latency] [--frames-in-flight 3|4|1] [--no-graph] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 `--workload camera` (default; the configuration BASELINE.json's metric is quoted on): one "step" = one full CorpBEVT forward
@@ -10,16 +10,19 @@ per GPU: `agents` x 4 cameras x 512x512 fp32 images (resident in HBM) -> ResNet-
 features] -> STTF -> swap fusion -> decoder -> 256x256 logits, through cobevt_amd.host.pipeline (HIP graphs, three frames
 in flight).  N > 1: the headline is the same quantity ("throughput" mode, "weak" scaling): N frames per step, the N*agents
 agent tasks dealt round-robin over the ranks and exchanged ONCE before fusion; value = N frames / step time, so
-value_N / (N x value_1) is the agent-shard scaling efficiency.  The same line carries `latency_mode` ("strong" scaling, the
+value_N / (N x value_1) is the agent-shard scaling efficiency.  With --full the line carries `latency_mode` ("strong" scaling, the
 north-star's partition): ONE frame per step, rank r encodes agents r, r+N, .., one all-gather, fusion replicated, with its
 `frame_latency_ms`; `--mode latency` makes that the headline.
 `--workload lidar` (BASELINE configs[4]): one step = SwapFusionEncoder(64 ch, 8 agents, window 8, depth 3, mask) on
 x (1, 8, 64, 256, 256); N > 1 throughput = one frame per rank (replicas), latency = the map row-sharded over the ranks with
 an all-to-all between the window and grid halves of every block (cobevt_amd/dist.py).
 Rank 0 prints ONE JSON line.  Timing: W warm-up steps, then K steps between barrier + synchronize, MAX over ranks; the per-step
-median / p95 come from HIP events recorded after every step.
+median / p95 come from HIP events recorded after every step.  `--dump-outputs DIR`: what the timed path returned from its last
+step, one DIR/<name>.npy per output tensor (float32; the inputs and weights are seeded, so two builds compare output for output).
 
-Extra legs at N = 1 (rank 0): `one_frame_at_a_time`, `eager_model_call` (the plain `model(batch)` a drop-in user calls),
+A plain run sets up, warms up, times the K steps and prints the line.  `--full` adds everything else: the correctness checks of
+the timed runner against the un-pipelined / single-process forward, `box_calibration`, the latency-mode / exchange /
+single-GPU-reference legs at N > 1, the LiDAR roofline, and these extra legs at N = 1 (rank 0): `one_frame_at_a_time`, `eager_model_call` (the plain `model(batch)` a drop-in user calls),
 `fp32_parity_mode` (same frame in the exact-fp32 mode), `other_configs` (the captured bf16 training step of the same model and frame, 2-agent OPV2V, nuScenes SinBEVT, LiDAR FuseBEVT), `roofline` (+ the
 level-0 FAX attention launch on its own) from HIP-event timings of one eager frame and the committed rocprofv3 PMC summary
 (profiles/pmc_*.json), `cpu_baseline` (the oracle on the host cores, kind "port") and `parity` against it.
@@ -70,20 +73,31 @@ def parse():
     ap.add_argument("--frames-in-flight", type=int, default=3, choices=[1, 3, 4],
                     help="single-GPU software pipeline: 3 = encoder / FAX query / fusion+decoder of three consecutive frames "
                          "overlap on three HIP streams (throughput mode, default); 1 = one frame at a time")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the eager / fp32 / other-config legs")
-    ap.add_argument("--no-ingest", action="store_true", help="skip the host-to-device ingest leg (`ingest`, `value_with_h2d`)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline: correctness checks of the timed runner, box calibration, the "
+                         "one-frame / eager / ingest / other-precision / other-config legs, roofline, CPU baseline and parity at N = 1; "
+                         "the latency-mode, exchange and single-GPU reference legs at N > 1.  Off: set up, warm up, time, print")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned from its last step as DIR/<name>.npy "
+                         "(float32, float64 kept; at most 64 MB in all, a fixed seeded sample of larger outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and parity legs")
+    ap.add_argument("--no-roofline", action="store_true", help="--full: skip the roofline legs")
+    ap.add_argument("--no-extra", action="store_true", help="--full: skip the eager / fp32 / other-config legs")
+    ap.add_argument("--no-ingest", action="store_true", help="--full: skip the host-to-device ingest leg (`ingest`, `value_with_h2d`)")
     ap.add_argument("--direct-probe", action="store_true", help=argparse.SUPPRESS)   # the isolated child job of direct_probe_child()
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 # ----------------------------------------------------------------------------------------------
 # timing
 # ----------------------------------------------------------------------------------------------
-def timed_loop(step, warmup, steps, world, dev):
+def timed_loop(step, warmup, steps, world, dev, keep=None):
     """W warm-up steps, then exactly K steps between barrier + synchronize; MAX over ranks.  Returns (elapsed seconds,
-    per-step milliseconds from HIP events recorded after each step)."""
+    per-step milliseconds from HIP events recorded after each step).  keep: a list that receives host copies of what the last
+    timed step returned (host_arrays), made after the clock has stopped."""
     for _ in range(warmup):
         step()
     if world > 1:
@@ -93,18 +107,57 @@ def timed_loop(step, warmup, steps, world, dev):
     t0 = time.perf_counter()
     events[0].record()
     for i in range(steps):
-        step()
+        out = step()
         events[i + 1].record()
     torch.cuda.synchronize()
     if world > 1:
         torch.distributed.barrier()
     elapsed = time.perf_counter() - t0
+    if keep is not None:
+        keep.append(host_arrays(out))
     if world > 1:
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = t.item()
     per = sorted(events[i].elapsed_time(events[i + 1]) for i in range(steps))
     return elapsed, per
+
+
+def host_arrays(out, name="output"):
+    """what a step returned -> {name: numpy array}: the tensors of a dict by key, of a tuple / list by position, a lone tensor as
+    `output`; float64 stays float64, every other dtype becomes float32"""
+    if out is None:
+        raise RuntimeError("the timed step returned no output (a pipelined runner that has not filled yet)")
+    if torch.is_tensor(out):
+        t = out.detach()
+        return {name: (t.double() if t.dtype == torch.float64 else t.float()).cpu().numpy()}
+    if isinstance(out, dict):
+        items = [(str(k), v) for k, v in out.items()]
+    elif isinstance(out, (tuple, list)):
+        items = [("%s_%d" % (name, i), v) for i, v in enumerate(out)]
+    else:
+        return {}
+    res = {}
+    for k, v in items:
+        if torch.is_tensor(v) or isinstance(v, (dict, tuple, list)):
+            res.update(host_arrays(v, k))
+    return res
+
+
+def dump_outputs(arrays, dirname, limit=64 << 20):
+    """DIR/<name>.npy for every array.  If they hold more than `limit` bytes in all, each is replaced by the same share of its
+    flattened elements, picked by numpy.random.default_rng(0) and kept in index order: the same sample on every run"""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    for k, a in sorted(arrays.items()):
+        if total > limit:
+            n = a.size
+            m = max(1, int(n * (limit / float(total))))
+            idx = np.sort(np.random.default_rng(0).choice(n, size=m, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(dirname, k.replace(os.sep, "_") + ".npy"), a)
+    return sorted(arrays)
 
 
 def pct(sorted_ms, q):
@@ -356,7 +409,7 @@ def rt_nchw(y):
     return y.permute(0, 3, 1, 2)
 
 
-def run_lidar(args, rank, world, dev):
+def run_lidar(args, rank, world, dev, keep=None):
     enc = synth.fill_module_(host.SwapFusionEncoder(dict(LIDAR_ARGS)), 0).eval().to(dev)
     x, mask = lidar_inputs(dev, seed=rank)
     note = "SwapFusionEncoder.forward(x fp32 (1,8,64,256,256), mask) incl. the layout / dtype conversion at the module boundary"
@@ -369,13 +422,14 @@ def run_lidar(args, rank, world, dev):
         mine = sfm._to_blhwc(xf[:, rank * per:(rank + 1) * per].contiguous())
         step = lambda: pipe.step(mine, mask)                   # noqa: E731
         frames_per_step, scaling = 1, "strong"
-        with torch.no_grad():       # the sharded result must equal the single-process encoder on the whole map (bf16 rounding apart)
-            ref = enc(xf, mask)
-            got = rt_nchw(pipe.step(mine, mask))
-            torch.cuda.synchronize()
-            err = float(((got.float() - ref.float()).abs().max() / ref.float().abs().max()).item())
-        if err > 3e-2:
-            raise RuntimeError("rank %d: row-sharded FuseBEVT differs from the single-process encoder (rel %.3e)" % (rank, err))
+        if args.full:
+            with torch.no_grad():   # the sharded result must equal the single-process encoder on the whole map (bf16 rounding apart)
+                ref = enc(xf, mask)
+                got = rt_nchw(pipe.step(mine, mask))
+                torch.cuda.synchronize()
+                err = float(((got.float() - ref.float()).abs().max() / ref.float().abs().max()).item())
+            if err > 3e-2:
+                raise RuntimeError("rank %d: row-sharded FuseBEVT differs from the single-process encoder (rel %.3e)" % (rank, err))
         par = "row-sharded x%d: agent->band all-to-all, band<->grid all-to-all per half block, all-gather of fused bands" % world
         note = "channels-last compute-dtype agent maps resident on their owner GPU (agent-per-GPU), eager launches"
     else:
@@ -383,7 +437,7 @@ def run_lidar(args, rank, world, dev):
         step = run.step
         frames_per_step, scaling = world, "weak"
         par = "single GPU" if world == 1 else "replicas x%d (one LiDAR frame per GPU, no collective)" % world
-    elapsed, per_ms = timed_loop(step, args.warmup, args.steps, world, dev)
+    elapsed, per_ms = timed_loop(step, args.warmup, args.steps, world, dev, keep=keep)
     ms = elapsed / args.steps * 1e3
     fps = frames_per_step / (ms * 1e-3)
     res = {"metric": "bev_frames_per_sec", "value": round(fps, 3), "unit": "frames/s", "n_gpus": world, "steps": args.steps,
@@ -395,7 +449,7 @@ def run_lidar(args, rank, world, dev):
                       "hip_graph": not args.no_graph and not (world > 1 and args.mode == "latency"), "timed": note,
                       "weights": "procedural (cobevt_amd.synth)"},
            "achieved_tflops_end_to_end": round(LIDAR_GF * frames_per_step / (ms * 1e-3) / 1e3, 2)}
-    if rank == 0 and world == 1 and not args.no_roofline:
+    if rank == 0 and world == 1 and args.full and not args.no_roofline:
         ent = lidar_roofline(enc, x, mask, args.dtype)
         res["roofline"], res["roofline_other_kernels"] = ent[0], ent[1:]
     return res
@@ -522,7 +576,7 @@ def direct_probe_child(args, world):
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.abspath(__file__), "--gpus", str(world), "--steps", str(args.steps), "--warmup",
-           str(args.warmup), "--dtype", args.dtype, "--agents", str(args.agents), "--direct-probe"] + (["--no-graph"] if args.no_graph else [])
+           str(args.warmup), "--dtype", args.dtype, "--agents", str(args.agents), "--direct-probe", "--full"] + (["--no-graph"] if args.no_graph else [])
     # its own session / process group, so that a hung rank (a peer that never arrives leaves the others in bounded GPU polls, then in
     # a host-side barrier) can be killed as a whole; the limit is generous for a healthy job (~60-120 s) and short enough not to
     # eat the driver's window around the bench
@@ -549,8 +603,9 @@ def direct_probe_child(args, world):
     return {"error": "direct-exchange probe job failed (exit code %d): %s" % (p.returncode, p.stderr.strip()[-400:])}
 
 
-def camera_leg(args, mode, model, cfg, rank, world, dev, gather="rccl", depth=None):
-    """build the runner of one mode, check it against the plain forward, time it -> (result fields, runner, timed, batch, full)"""
+def camera_leg(args, mode, model, cfg, rank, world, dev, gather="rccl", depth=None, keep=None):
+    """build the runner of one mode, check it against the plain forward (--full), time it -> (result fields, runner, timed, batch,
+    full, frames in flight); keep: see timed_loop"""
     A = args.agents
     strong = world > 1 and mode == "latency"
     # throughput mode: this rank's A agent tasks (images differ per rank) + the pose / record_len of frame `rank`;
@@ -573,20 +628,21 @@ def camera_leg(args, mode, model, cfg, rank, world, dev, gather="rccl", depth=No
             world, "one RCCL all_gather_into_tensor between graph replays" if gather == "rccl" else
             "one direct peer-window exchange (csrc/peer_gather.hip) inside the captured graph",
             "; the tail of frame i-1 runs on a second stream under the encoder of frame i" if depth == 2 else ""))
-        # every rank must reproduce the un-sharded forward of the whole frame (agents are a pure batch dimension up to the gather;
-        # not bit for bit in bf16: the conv tile shapes - hence the summation order - are chosen per batch size)
-        ref = model(dict(batch))["dynamic_seg"]
+        # --full: every rank must reproduce the un-sharded forward of the whole frame (agents are a pure batch dimension up to the
+        # gather; not bit for bit in bf16: the conv tile shapes - hence the summation order - are chosen per batch size)
+        ref = model(dict(batch))["dynamic_seg"] if args.full else None
         for _ in range(depth):
             got = timed.step()
         got = got["dynamic_seg"]
         torch.cuda.synchronize()
         timed.status()
-        shard_check = float(((got - ref).abs().max() / ref.abs().max()).item())
-        if shard_check > (5e-2 if args.dtype == "bf16" else 1e-4):
-            raise RuntimeError("rank %d: frame-sharded output differs from the single-process forward (rel %.3e)" % (rank, shard_check))
+        if args.full:
+            shard_check = float(((got - ref).abs().max() / ref.abs().max()).item())
+            if shard_check > (5e-2 if args.dtype == "bf16" else 1e-4):
+                raise RuntimeError("rank %d: frame-sharded output differs from the single-process forward (rel %.3e)" % (rank, shard_check))
     else:
         runner = pipeline.CapturedCorpBEVT(model, batch, rank, world, A, use_graph=False)
-        ref_out = {k: v.clone() for k, v in runner.eager_step().items()}
+        ref_out = {k: v.clone() for k, v in runner.eager_step().items()} if args.full else None
         torch.cuda.synchronize()
         if not args.no_graph:
             try:
@@ -605,15 +661,16 @@ def camera_leg(args, mode, model, cfg, rank, world, dev, gather="rccl", depth=No
                 for _ in range(2 * args.frames_in_flight + 2):
                     out = timed.step()
                 torch.cuda.synchronize()
-                for k in ref_out:                  # steady state == un-pipelined forward, bit for bit
+                for k in (ref_out or {}):          # --full: steady state == un-pipelined forward, bit for bit
                     if not torch.equal(out[k], ref_out[k]):
                         raise RuntimeError("pipelined frame differs from the un-pipelined forward in %r" % k)
                 in_flight = args.frames_in_flight
                 pipeline_note = ("%s of %d consecutive frames on %d HIP streams in one captured graph; one frame in, one frame "
-                                 "out per step; steady-state output checked bit-identical to the un-pipelined forward" %
+                                 "out per step%s" %
                                  ("S1 encoder + K/V | S2 FAX query | S3 fusion + decoder" if in_flight == 3 else
                                   "S1 encoder + K/V | S2a FAX level 0 | S2b FAX levels 1-2 + global attention | S3 fusion + decoder",
-                                  in_flight, in_flight))
+                                  in_flight, in_flight,
+                                  "; steady-state output checked bit-identical to the un-pipelined forward" if ref_out else ""))
             except Exception as e:  # noqa: BLE001 — never lose the measurement: fall back to one frame at a time, say so
                 if world == 1:
                     raise
@@ -628,7 +685,7 @@ def camera_leg(args, mode, model, cfg, rank, world, dev, gather="rccl", depth=No
                 pipeline_note = "pipelined mode failed on another rank; one frame at a time"
         frames_per_step = world
 
-    elapsed, per_ms = timed_loop(timed.step, args.warmup, args.steps, world, dev)
+    elapsed, per_ms = timed_loop(timed.step, args.warmup, args.steps, world, dev, keep=keep)
     if strong:
         timed.status()
     ms_per_step = elapsed / args.steps * 1e3
@@ -674,9 +731,12 @@ def main():
     if args.workload == "lidar":
         if args.mode in (None, "both"):
             args.mode = "throughput"
-        result = run_lidar(args, rank, world, dev)
+        keep = [] if args.dump_outputs else None
+        result = run_lidar(args, rank, world, dev, keep=keep)
         result["rccl_ranks"] = rank_table(rank, world, dev)
         if rank == 0:
+            if keep:
+                result["dumped_outputs"] = dump_outputs(keep[0], args.dump_outputs)
             print(json.dumps(result), flush=True)
         if world > 1:
             torch.distributed.destroy_process_group()
@@ -710,6 +770,7 @@ def main():
         torch.distributed.destroy_process_group()
         return
     isolate_direct = False
+    keep = [] if args.dump_outputs else None
     if world > 1 and ranks.get("backend") == "nccl" and ranks.get("distinct_gpus") != world:
         raise SystemExit("bench.py: RCCL process group of %d ranks sits on %s distinct GPU(s) - one GPU per rank is required "
                          "(rank table: %s)" % (world, ranks.get("distinct_gpus"), ranks["ranks"]))
@@ -731,12 +792,12 @@ def main():
                 torch.cuda.synchronize()
                 return {"error": "%s: %s" % (type(e).__name__, str(e)[:300])}
         head_mode = "latency" if mode == "latency" else "throughput"
-        result, runner, timed, batch, full, in_flight = camera_leg(args, head_mode, model, cfg, rank, world, dev,
+        result, runner, timed, batch, full, in_flight = camera_leg(args, head_mode, model, cfg, rank, world, dev, keep=keep,
                                                                    **({"gather": args.gather} if head_mode == "latency" else {}))
         if head_mode == "latency":
             result["frame_latency_ms"] = round(result["ms_per_step"] * result["config"]["frame_latency_steps"], 4)
         other_gather = "direct" if args.gather == "rccl" else "rccl"
-        if mode == "both":
+        if mode == "both" and args.full:
             result["latency_mode"] = side(gather=args.gather)                      # depth 2: the tail of frame i-1 under frame i
             result["latency_mode_unpipelined"] = side(gather=args.gather, depth=1)
             # the direct peer-window legs run in a job of their own after this one (direct_probe_child) unless the direct exchange
@@ -747,10 +808,10 @@ def main():
             else:
                 result["latency_mode_%s_gather" % other_gather] = side(gather=other_gather)
                 safe(result, "all_gather_us", lambda: gather_latency_leg(model, batch, rank, world, A, dev))
-        # the N = 1 figures of the same box, measured by rank 0 alone while the other ranks wait at the barrier below: what the
-        # per-GPU numbers above are to be compared with
+        # --full: the N = 1 figures of the same box, measured by rank 0 alone while the other ranks wait at the barrier below: what
+        # the per-GPU numbers above are to be compared with
         torch.distributed.barrier()
-        if rank == 0:
+        if rank == 0 and args.full:
             def single():
                 r1, run1, _, _, _, _ = camera_leg(args, "throughput", model, cfg, 0, 1, dev)
                 lat = quick(run1.step, 3, 20)
@@ -772,13 +833,15 @@ def main():
                 result["scaling_summary"] = sc
         torch.distributed.barrier()
     else:
-        result, runner, timed, batch, full, in_flight = camera_leg(args, "throughput", model, cfg, rank, world, dev)
+        result, runner, timed, batch, full, in_flight = camera_leg(args, "throughput", model, cfg, rank, world, dev, keep=keep)
     result["rccl_ranks"] = ranks
     graph_ok_main = bool(result["config"].get("hip_graph"))
+    if rank == 0 and keep:
+        result["dumped_outputs"] = dump_outputs(keep[0], args.dump_outputs)
 
-    if rank == 0:
+    if rank == 0 and args.full:
         safe(result, "box_calibration", lambda: box_calibration(dev))
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         if in_flight > 1:
             safe(result, "one_frame_at_a_time", lambda: dict(
                 quick(runner.step, 5, 50), note="cobevt_amd.host.pipeline.CapturedCorpBEVT: the same forward from captured graphs "

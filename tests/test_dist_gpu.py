@@ -76,14 +76,31 @@ def test_collective_exchange_rccl(cuda):
     _launch("collective", 2, "nccl")
 
 
-def _bench(extra, env=None, timeout=900):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "2", "--no-cpu-baseline", "--no-roofline",
-           "--no-extra"] + extra
+def _bench(extra, env=None, timeout=900, full=True):
+    # --full: the latency-mode legs, the single-GPU reference, box calibration and the ranks' checks against the single-process
+    # forward live behind it
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py")] + (["--full"] if full else []) + [
+        "--steps", "3", "--warmup", "2", "--no-cpu-baseline", "--no-roofline", "--no-extra"] + extra
     out = subprocess.run(cmd, env=dict(os.environ, **(env or {})), stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=timeout)
     assert out.returncode == 0, out.stderr.decode(errors="replace")[-3000:]
     lines = [l for l in out.stdout.decode().splitlines() if l.startswith("{")]
     assert len(lines) == 1, "bench.py must print exactly ONE JSON line, got %d" % len(lines)
     return json.loads(lines[0])
+
+
+def test_bench_plain_run_dumps_outputs(cuda, tmp_path):
+    """`python bench.py --steps 3 --warmup 2 --dump-outputs DIR` without --full: the headline fields over exactly the requested
+    steps, none of the --full legs, and the last timed step's outputs (both heads' logits) as float32 .npy files"""
+    import numpy as np
+    res = _bench(["--dump-outputs", str(tmp_path)], full=False)
+    assert res["metric"] == "bev_frames_per_sec" and res["unit"] == "frames/s" and res["higher_is_better"] is True
+    assert res["steps"] == 3 and res["warmup"] == 2 and res["ms_per_step"] > 0 and res["value"] > 0 and res["dtype"] == "bf16"
+    assert not {"box_calibration", "one_frame_at_a_time", "roofline", "cpu_baseline", "parity", "other_configs"} & set(res)
+    assert res["dumped_outputs"] == ["dynamic_seg", "static_seg"]
+    for name in res["dumped_outputs"]:
+        a = np.load(str(tmp_path / (name + ".npy")))
+        assert a.dtype == np.float32 and a.shape[-2:] == (256, 256) and np.isfinite(a).all(), (name, a.dtype, a.shape)
+    assert np.load(str(tmp_path / "dynamic_seg.npy")).std() > 0
 
 
 def test_bench_spawns_its_own_ranks(cuda):

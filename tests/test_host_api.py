@@ -304,6 +304,31 @@ def test_bench_line_finishing_touches():
     bench.finish_line({"value": 1.0, "config": {"workload": "OPV2V-LiDAR FuseBEVT"}}, 1)     # a line without any of the legs
 
 
+def test_bench_output_dump(tmp_path):
+    """bench.py --dump-outputs (pure host logic): what a step returned -> one float32 / float64 .npy per tensor, named by dict key or
+    position; above the size cap a sample of the same seeded indices on every call, within the cap"""
+    import bench
+    seg = torch.linspace(-1, 1, 2 * 4 * 5, dtype=torch.bfloat16).reshape(1, 2, 4, 5)
+    arrs = bench.host_arrays({"dynamic_seg": seg, "meta": "x", "pair": (torch.arange(3, dtype=torch.float64), torch.ones(2, dtype=torch.int32))})
+    assert sorted(arrs) == ["dynamic_seg", "pair_0", "pair_1"]
+    assert arrs["dynamic_seg"].dtype == np.float32 and arrs["dynamic_seg"].shape == (1, 2, 4, 5)
+    assert np.array_equal(arrs["dynamic_seg"], seg.float().numpy())
+    assert arrs["pair_0"].dtype == np.float64 and arrs["pair_1"].dtype == np.float32
+    assert list(bench.host_arrays(torch.zeros(3))) == ["output"]
+    with pytest.raises(RuntimeError):
+        bench.host_arrays(None)
+    names = bench.dump_outputs(arrs, str(tmp_path / "full"))
+    assert names == ["dynamic_seg", "pair_0", "pair_1"]
+    assert np.array_equal(np.load(str(tmp_path / "full" / "dynamic_seg.npy")), arrs["dynamic_seg"])
+    big = {"a": np.arange(1000, dtype=np.float32), "b": np.arange(3000, dtype=np.float64)}
+    for d in ("s1", "s2"):
+        bench.dump_outputs(big, str(tmp_path / d), limit=8000)
+    a1, b1 = np.load(str(tmp_path / "s1" / "a.npy")), np.load(str(tmp_path / "s1" / "b.npy"))
+    assert a1.nbytes + b1.nbytes <= 8000 and a1.size > 0 and b1.size > 0 and b1.dtype == np.float64
+    assert np.all(np.diff(a1) > 0) and set(a1.tolist()) <= set(big["a"].tolist())
+    assert np.array_equal(a1, np.load(str(tmp_path / "s2" / "a.npy"))) and np.array_equal(b1, np.load(str(tmp_path / "s2" / "b.npy")))
+
+
 def test_host_frame_feeder_protocol(monkeypatch):
     """HostFrameFeeder's hand-over protocol on a stand-in runner (no GPU: the fetch kernel and the events are recorded, not run): which
     pinned slot is fetched into which image slot and when, which event a put() waits for before it rewrites a ring slot, and that a frame

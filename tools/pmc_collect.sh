@@ -10,7 +10,7 @@ WORKLOAD=${3:-camera}
 ROOT=$(pwd)
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-CMD="python $ROOT/bench.py --steps 3 --warmup 1 --no-graph --no-cpu-baseline --no-roofline --no-extra --no-ingest --frames-in-flight 1"
+CMD="python $ROOT/bench.py --full --steps 3 --warmup 1 --no-graph --no-cpu-baseline --no-roofline --no-extra --no-ingest --frames-in-flight 1"
 NAME="pmc_${TAG}.json"
 if [ "$WORKLOAD" = "lidar" ]; then
     CMD="python $ROOT/bench.py --workload lidar --steps 3 --warmup 1 --no-graph --no-roofline"
