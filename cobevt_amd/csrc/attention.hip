@@ -484,7 +484,7 @@ __global__ __launch_bounds__(256) void attn_ksplit_merge_kernel(AttnParams p) {
     if (item >= total) return;
     const int c8 = (int)(item & 3), head = (int)((item >> 2) % p.heads);
     const long row = (item >> 2) / p.heads;
-    float lse[8], mx = -INFINITY;
+    float lse[16], mx = -INFINITY;                    // ksplit <= 16 (window_attention_impl)
     for (int s = 0; s < p.ksplit; ++s) {
         lse[s] = p.part_lse[((size_t)s * p.part_rows + row) * p.heads + head];
         if (lse[s] > mx) mx = lse[s];
@@ -582,9 +582,12 @@ static int window_attention_impl(const void* q, const void* k, const void* v, vo
     // keys of a single window that covers the whole map are rows b * Nk + tk: no table (CVT attends to 4 x 64 x 64 keys)
     p.klinear = (p.kmap.mode != 2 && p.kmap.X == 1 && p.kmap.Y == 1 && !p.bias_mode && !mask) ? 1 : 0;
     if (lse && p.mean_q) return COBEVT_ERR_UNSUPPORTED;     // (the training path averages cameras outside the kernel)
-    if (ksplit > 1) {       // key split: streaming kernel only, plain inference attention, every query of a window on its own
-        if (ksplit > 8 || !part_out || !part_lse || part_rows < 1 || lse || p.mean_q || drop_p > 0.f) return COBEVT_ERR_ARG;
-        if (p.omap.ncam != p.qmap.ncam) return COBEVT_ERR_UNSUPPORTED;
+    // key split: streaming kernel only, plain inference attention - every query of a window on its own, or camera-paired (mean_q = 2:
+    // partial rows and the merge follow the output map, one row per BEV position; a split may start or end inside a camera, the key
+    // loop reloads the query copy whenever a tile's camera differs from the one it holds)
+    if (ksplit > 1) {
+        if (ksplit > 16 || !part_out || !part_lse || part_rows < 1 || lse || p.mean_q == 1 || drop_p > 0.f) return COBEVT_ERR_ARG;
+        if (p.mean_q != 2 && p.omap.ncam != p.qmap.ncam) return COBEVT_ERR_UNSUPPORTED;
         p.ksplit = ksplit; p.part_out = part_out; p.part_lse = part_lse; p.part_rows = part_rows;
     }
     if (dtype == 0 && variant == 0 && p.mean_q != 2 && !lse && ksplit == 1) {
@@ -601,7 +604,9 @@ static int window_attention_impl(const void* q, const void* k, const void* v, vo
     // registers cost occupancy: 512-token LiDAR windows, bias + mask, 8192 workgroups: 357 us against 266 us with 64-key tiles)
     const bool wide = dtype == 0 && p.mean_q != 2 && p.Nk >= 256 && variant != 2 &&      // variant 2: 64-key tiles (A/B)
                       (long)grid.x * grid.y * grid.z <= 1024;
-    if (p.ksplit > 1 && (p.Nk + (wide ? 127 : 63)) / (wide ? 128 : 64) < p.ksplit) return COBEVT_ERR_SHAPE;   // >= 1 tile per split
+    // >= 1 key tile per split (camera-paired: 64-key tiles that never mix cameras, as the kernel counts them)
+    const int key_tiles = p.mean_q == 2 ? p.kmap.ncam * ((p.kmap.w1 * p.kmap.w2 + 63) / 64) : (p.Nk + (wide ? 127 : 63)) / (wide ? 128 : 64);
+    if (p.ksplit > 1 && key_tiles < p.ksplit) return COBEVT_ERR_SHAPE;
     size_t lds = dtype == 0 ? (wide ? AttnLds<bf16_t, 128>::kFixed : AttnLds<bf16_t, 64>::kFixed) : AttnLds<float, 64>::kFixed;
     if (p.bias_mode) lds += ((size_t)p.bias_rows * 4 + 15) & ~(size_t)15;
     if (!p.klinear) lds += (size_t)p.Nk * 8;        // per-key row / coordinate table

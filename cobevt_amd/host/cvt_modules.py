@@ -49,8 +49,9 @@ class CrossAttention(HipModule):
         self.mlp = nn.Sequential(nn.Linear(dim, 2 * dim), nn.GELU(), nn.Linear(2 * dim, dim))
         self.postnorm = norm(dim)
 
-    def attend_tokens(self, q, k, v, skip, H, W, h, w):
-        """q (b, n, H*W, d), k / v (b*n, h, w, d) channels-last compute dtype, skip (b, H, W, d) | None -> (b, H, W, d)"""
+    def attend_tokens(self, q, k, v, skip, H, W, h, w, key_split=False):
+        """q (b, n, H*W, d), k / v (b*n, h, w, d) channels-last compute dtype, skip (b, H, W, d) | None -> (b, H, W, d).
+        key_split: share each query tile's keys out over ops.paired_ksplit workgroups + a merge (the nuScenes encoder's 6 x 6720-key level)"""
         b, n = q.shape[:2]
         inner = self.heads * self.dim_head
         qt = ops.linear(q, rt.linear_plan(self, "q", self.to_q[1], ln=self.to_q[0]))
@@ -58,7 +59,8 @@ class CrossAttention(HipModule):
         vt = ops.linear(v, rt.linear_plan(self, "v", self.to_v[1], ln=self.to_v[0]))
         a = torch.empty((b, H, W, inner), device=qt.device, dtype=qt.dtype)
         qmap, kmap, omap = ops.tokmap(0, n, H, W, H, W), ops.tokmap(0, n, h, w, h, w), ops.tokmap(0, 1, H, W, H, W)
-        ops.window_attention(qt, kt, vt, a, qmap, kmap, omap, b, self.heads, self.scale, inner, inner, inner, inner, mean_q=2)
+        ks = ops.paired_ksplit(b, self.heads, qmap, kmap) if key_split else None
+        ops.window_attention(qt, kt, vt, a, qmap, kmap, omap, b, self.heads, self.scale, inner, inner, inner, inner, mean_q=2, ksplit=ks)
         z = ops.linear(a, rt.linear_plan(self, "proj", self.proj), residual=skip)
         z = rt.layernorm(self, "prenorm", self.prenorm, z)                  # z = prenorm(z); z = z + mlp(z); z = postnorm(z)
         t = ops.linear(z, rt.linear_plan(self, "mlp0", self.mlp[0], act=2))
@@ -78,6 +80,7 @@ class CrossAttention(HipModule):
 
 class CrossViewAttention(HipModule):
     """cvt_modules.py:173-283."""
+    key_split = False           # the OPV2V baselines: one single-pass attention launch (nuscenes.encoder.CrossViewAttention splits)
 
     def __init__(self, feat_height, feat_width, feat_dim, dim, config):
         super().__init__()
@@ -117,7 +120,7 @@ class CrossViewAttention(HipModule):
         b_bev = rt.f32_param(self, "b_bev", self.bev_embed.bias)
         query = ops.bev_embed(E_inv, world, w_bev, b_bev, w_cam, x.reshape(b, H * W, d), n)          # (b, n, HW, d)
         skip = (x if x.is_contiguous() else x.contiguous()) if self.skip else None
-        return self.cross_attend.attend_tokens(query, key, val, skip, H, W, h, w)
+        return self.cross_attend.attend_tokens(query, key, val, skip, H, W, h, w, key_split=self.key_split)
 
     def forward(self, x, bev, feature, I_inv, E_inv):
         """x (b, d, H, W); feature (b, n, C, h, w); I_inv (b, n, 3, 3); E_inv (b, n, 4, 4) -> (b, d, H, W)"""

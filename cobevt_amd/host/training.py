@@ -399,28 +399,44 @@ def corpbevt(model, batch_dict):
 # the CVT baselines: cvt_modules.py CrossAttention / CrossViewAttention / CrossViewModule, the per-pixel agent
 # attention of base_transformer.py, and the models cross_view_transformer{,_swap_fuse,_fcooper,_att_fuse}.py in train() mode
 # ----------------------------------------------------------------------------------------------
-def cvt_cross_attention(m, q, k, v, skip):
+def cvt_cross_attention(m, q, k, v, skip, per_camera=False):
     """cvt_modules.CrossAttention.forward (:116-170) on token-major sources: q (b, n, Q, d), k / v (b, n, K, d), skip (b, Q, d) | None
     -> (b, Q, d).  Camera c's query copy scores camera c's keys and ONE softmax runs over the keys of all cameras (:142-153).
     With s_c the scores of camera c,   softmax over (c, K)  =  softmax_K(s_c) * softmax_c(lse_c),   lse_c = log sum_K exp(s_c):
     the attention kernels run once with the cameras as the windows of a stored-partitioned map (the per-camera outputs and their
-    log-sum-exp), a softmax over the n log-sum-exps merges them - both differentiable (WindowAttentionFn takes the lse gradient)."""
+    log-sum-exp), a softmax over the n log-sum-exps merges them - both differentiable (WindowAttentionFn takes the lse gradient).
+    per_camera: one launch per camera instead, each a single whole-map window whose keys are addressed row-linearly - the stored-
+    partitioned map keeps an 8-byte row entry per key in LDS, which does not fit for the nuScenes encoder's 56 x 120 = 6720 keys."""
     _check(q, k, v, skip)
     b, n, Q, d = q.shape
     K = k.shape[2]
     heads = m.heads
     qt, kt, vt = _project(m.to_q, q), _project(m.to_k, k), _project(m.to_v, v)
-    # mode-2 maps with ncam = 1, X * Y = n windows, w1 * w2 tokens: row = (b * n + camera) * tokens + token
-    qmap, kmap = (2, 1, n * Q, 1, Q, 1, n, 1), (2, 1, n * K, 1, K, 1, n, 1)
-    if Q >= 256 or K >= 256:                 # a window side is < 256 in the token-coordinate packing: factor the token count
-        def sides(t):
-            for a in (128, 64, 32, 16, 8, 4, 2):
-                if t % a == 0 and t // a < 256:
-                    return t // a, a
-            raise CobevtHipError("CVT cross attention: cannot factor %d tokens into a window below 256 x 256" % t)
+
+    def sides(t):                            # a window side is < 256 in the token-coordinate packing: factor the token count
+        for a in (128, 64, 32, 16, 8, 4, 2) + tuple(range(255, 2, -1)):     # (the nuScenes encoder's 25 x 25 = 625 queries: 5 x 125)
+            if t % a == 0 and t // a < 256:
+                return t // a, a
+        raise CobevtHipError("CVT cross attention: cannot factor %d tokens into a window below 256 x 256" % t)
+    if per_camera:
         (q1, q2), (k1, k2) = sides(Q), sides(K)
-        qmap, kmap = (2, 1, n * q1, q2, q1, q2, n, 1), (2, 1, n * k1, k2, k1, k2, n, 1)
-    a, lse = ag.window_attention(qt, kt, vt, qmap, kmap, qmap, b, heads, m.scale, qt.shape[0], return_lse=True)   # (b n Q, inner), (b, n, heads, Q)
+        qm, km = (0, 1, q1, q2, q1, q2, 1, 1), (0, 1, k1, k2, k1, k2, 1, 1)
+        inner = heads * 32
+        q4, k4, v4 = qt.reshape(b, n, Q, inner), kt.reshape(b, n, K, inner), vt.reshape(b, n, K, inner)
+        outs, lses = [], []
+        for c in range(n):
+            a_c, l_c = ag.window_attention(q4[:, c].reshape(b * Q, inner), k4[:, c].reshape(b * K, inner), v4[:, c].reshape(b * K, inner),
+                                           qm, km, qm, b, heads, m.scale, b * Q, return_lse=True)
+            outs.append(a_c.reshape(b, Q, inner))
+            lses.append(l_c.reshape(b, 1, heads, Q))
+        a, lse = torch.stack(outs, 1), torch.cat(lses, 1)                                     # (b, n, Q, inner), (b, n, heads, Q)
+    else:
+        # mode-2 maps with ncam = 1, X * Y = n windows, w1 * w2 tokens: row = (b * n + camera) * tokens + token
+        qmap, kmap = (2, 1, n * Q, 1, Q, 1, n, 1), (2, 1, n * K, 1, K, 1, n, 1)
+        if Q >= 256 or K >= 256:
+            (q1, q2), (k1, k2) = sides(Q), sides(K)
+            qmap, kmap = (2, 1, n * q1, q2, q1, q2, n, 1), (2, 1, n * k1, k2, k1, k2, n, 1)
+        a, lse = ag.window_attention(qt, kt, vt, qmap, kmap, qmap, b, heads, m.scale, qt.shape[0], return_lse=True)   # (b n Q, inner), (b, n, heads, Q)
     wts = torch.softmax(lse, dim=1).permute(0, 1, 3, 2)                                     # (b, n, Q, heads)
     a = (a.reshape(b, n, Q, heads, 32) * wts[..., None]).sum(dim=1).reshape(b * Q, heads * 32)
     z = ag.linear(a, m.proj).reshape(b, Q, d)
@@ -431,8 +447,9 @@ def cvt_cross_attention(m, q, k, v, skip):
     return ag.layernorm(z.contiguous(), m.postnorm)
 
 
-def cvt_cross_view_attention(m, x, bev, feature, I_inv, E_inv):
-    """cvt_modules.CrossViewAttention.forward (:217-283): x (b d H W), feature (b n C h w), I_inv (b n 3 3), E_inv (b n 4 4) -> (b d H W)"""
+def cvt_cross_view_attention(m, x, bev, feature, I_inv, E_inv, per_camera=False):
+    """cvt_modules.CrossViewAttention.forward (:217-283): x (b d H W), feature (b n C h w), I_inv (b n 3 3), E_inv (b n 4 4) -> (b d H W)
+    (per_camera: see cvt_cross_attention)"""
     _check(x, feature, I_inv, E_inv)
     b, n, _, h, w = feature.shape
     _, d, H, W = x.shape
@@ -451,7 +468,7 @@ def cvt_cross_view_attention(m, x, bev, feature, I_inv, E_inv):
     val = _pre_act_conv1x1(m.feature_linear, feat)
     tok = lambda t, hh, ww: t.reshape(b, n, d, hh * ww).permute(0, 1, 3, 2).contiguous()       # (b, n, tokens, d)
     skip = x.reshape(b, d, H * W).permute(0, 2, 1) if m.skip else None
-    z = cvt_cross_attention(m.cross_attend, tok(query, H, W), tok(key, h, w), tok(val, h, w), skip)
+    z = cvt_cross_attention(m.cross_attend, tok(query, H, W), tok(key, h, w), tok(val, h, w), skip, per_camera)
     return z.reshape(b, H, W, d).permute(0, 3, 1, 2)
 
 
@@ -626,9 +643,29 @@ def nusc_decoder(dec, x):
     return y
 
 
+def nusc_cvt_encoder(m, batch):
+    """nuScenes Encoder.forward (encoder.py:319-337, the cvt.yaml encoder): image (b, n, 3, h, w), intrinsics, extrinsics -> (b, d, H, W).
+    The OPV2V CVT operators (cvt_cross_view_attention), with the extrinsics inverted in the model (:324)."""
+    image = batch["image"]
+    _check(image, batch["intrinsics"], batch["extrinsics"])
+    b, n = image.shape[:2]
+    I_inv = ops.invert_small(batch["intrinsics"].reshape(b * n, 3, 3).to(torch.float32)).reshape(b, n, 3, 3)
+    E_inv = ops.invert_small(batch["extrinsics"].reshape(b * n, 4, 4).to(torch.float32)).reshape(b, n, 4, 4)
+    feats = efficientnet_extractor(m.backbone, (image.flatten(0, 1) - m.norm.mean) / m.norm.std)
+    prior = m.bev_embedding.get_prior()
+    x = prior[None].expand(b, *prior.shape)
+    for cross_view, feature, layer in zip(m.cross_views, feats, m.layers):
+        feature = feature.reshape(b, n, *feature.shape[1:])
+        x = cvt_cross_view_attention(cross_view, x.contiguous(), m.bev_embedding, feature.contiguous(), I_inv, E_inv, per_camera=True)
+        for blk in layer:
+            x = bottleneck(blk, x)
+    return x
+
+
 def nusc_cross_view_transformer(model, batch):
-    """nuScenes CrossViewTransformer.forward (cvt.py:35-40) as a differentiable graph"""
-    bev = pyramid_axial_encoder(model.encoder, batch)
+    """nuScenes CrossViewTransformer.forward (cvt.py:35-40) as a differentiable graph, on either encoder (SinBEVT or the original CVT)"""
+    from .nuscenes.encoder import Encoder
+    bev = (nusc_cvt_encoder if isinstance(model.encoder, Encoder) else pyramid_axial_encoder)(model.encoder, batch)
     y = nusc_decoder(model.decoder, bev)
     hidden = _conv_bn(y, model.to_logits[0], model.to_logits[1], relu=True)
     logits = ag.conv2d(hidden, model.to_logits[3])

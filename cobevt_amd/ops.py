@@ -804,6 +804,11 @@ def window_attention(q, k, v, out, qmap, kmap, omap, batch, heads, scale, ldq, l
                     and 512 < nk_ <= 1024 and (ATTN_VARIANT if variant is None else int(variant)) == 0 and omap[1] == qmap[1])
     use_ks = (ks > 1 and not big_resident and not mean_q and nk_ >= 1024 and batch * L * heads * ((nq_ + 127) // 128) * ks <= 1024
               and out.is_contiguous() and ldo == out.shape[-1] and ooff == 0 and omap[1] == qmap[1])
+    if int(mean_q) == 2:
+        # camera-paired (CVT): split only when the caller asks for it - with ksplit=None the OPV2V CVT baselines keep their single-pass launch
+        use_ks = ksplit is not None and ks > 1
+        if use_ks and not (out.is_contiguous() and ldo == out.shape[-1] and ooff == 0):
+            raise CobevtHipError("window_attention: the camera-paired key split writes a contiguous `out` (ldo = width, ooff = 0)")
     # "fp32_fast": the attention launches go to the third library as well (lib.encoder_scope() is a no-op in every other mode) - fp16
     # queries / probabilities against fp16 (hi, lo) keys / values, csrc/attention.hip kStage16
     with _L.encoder_scope(), _timed("attention|B%d L%d h%d Nq%d Nk%d%s" % (batch, L, heads, nq_, nk_, " ks%d" % ks if use_ks else ""), cost):
@@ -818,6 +823,21 @@ def window_attention(q, k, v, out, qmap, kmap, omap, batch, heads, scale, ldq, l
                                                    ctypes.c_float(scale), _stream())
     _L.check(rc, "cobevt_window_attention")
     return out
+
+
+PAIRED_KSPLIT_MAX = 16      # cobevt_window_attention_ksplit's cap
+PAIRED_KSPLIT_WG = 512      # ... and the grid the split count aims at: up to two workgroups per CU
+
+
+def paired_ksplit(batch, heads, qmap, kmap):
+    """Key split for a camera-paired (mean_q = 2) window_attention over whole-map windows: as many splits as keep the grid at or below
+    PAIRED_KSPLIT_WG workgroups (batch x heads x 128-query tiles each), at most PAIRED_KSPLIT_MAX and at most one per 64-key tile
+    (tiles never mix cameras).  None when the unsplit grid is already that large (no split)."""
+    L = qmap[6] * qmap[7]
+    wg = batch * L * heads * ((qmap[4] * qmap[5] + 127) // 128)
+    tiles = kmap[1] * ((kmap[4] * kmap[5] + 63) // 64)
+    ks = min(PAIRED_KSPLIT_MAX, tiles, PAIRED_KSPLIT_WG // wg)
+    return ks if ks >= 2 else None
 
 
 def attention_index_map(tmap, batch, device):

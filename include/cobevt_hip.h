@@ -507,11 +507,14 @@ int cobevt_channel_gate_nhwc(const void* in, const float* gate, void* out, int d
 int cobevt_mean_linear_rows_small_k(const void* in, const void* wfrag, const float* bias, void* out, const long* dims,
                                     float ln_eps, hipStream_t stream);
 
-/* cobevt_window_attention with the KEYS of every window shared out over `ksplit` (2..8) workgroups per query tile and a merge
+/* cobevt_window_attention with the KEYS of every window shared out over `ksplit` (2..16) workgroups per query tile and a merge
  * pass (same reference code: fax_modules.py:211-237, 137-171): for launches whose grid leaves the chip idle while every query
- * walks a long key list (FAX level 2 / global attention: 1024 keys, 160 workgroups).  Plain inference attention only (no camera
- * mean / pairing, no lse, no dropout); bias table and mask as there.  part_out: [ksplit][out_rows][heads * 32] in the storage
- * dtype, part_lse: fp32 [ksplit][out_rows][heads] - scratch; out_rows = rows of `out` (ld = dims' ldo). */
+ * walks a long key list (FAX level 2 / global attention: 1024 keys, 160 workgroups; the nuScenes CVT encoder's camera-paired
+ * level-1 attention: 625 queries x 6 x 6720 keys, 20 workgroups unsplit).  Inference attention without camera mean, lse or
+ * dropout; camera-paired (mean_q = 2, cvt_modules.py:142-153 / nuscenes encoder.py:142-153) allowed - its partial rows follow
+ * the output map.  Bias table and mask as there.  COBEVT_ERR_SHAPE when a split would get no key tile (64 keys; camera-paired:
+ * tiles never mix cameras).  part_out: [ksplit][out_rows][heads * 32] in the storage dtype, part_lse: fp32 [ksplit][out_rows]
+ * [heads] - scratch; out_rows = rows of `out` (ld = dims' ldo). */
 int cobevt_window_attention_ksplit(const void* q, const void* k, const void* v, void* out, const float* bias_table,
                                    const float* mask, void* part_out, float* part_lse, const int* dims, float scale,
                                    int ksplit, long out_rows, hipStream_t stream);
