@@ -1,0 +1,60 @@
+"""PointPillarFuseBEVT — the LiDAR leg of CoBEVT from real voxels: PillarVFE -> PointPillarScatter -> regroup -> FuseBEVT
+(SwapFusionEncoder), i.e. opencood's pillar_vfe.py / point_pillar_scatter.py / fuse_utils.regroup in front of
+fusion_modules/swap_fusion_modules.py.  OpenCOOD projects every agent's points into the ego frame before voxelisation, so there is
+no STTF warp here.
+
+args: voxel_size [x, y, z]; lidar_range [x0, y0, z0, x1, y1, z1]; max_cav; pillar_vfe {use_norm, with_distance, use_absolute_xyz,
+num_filters: [64]}; point_pillar_scatter {num_features: 64, grid_size: [nx, ny, 1]}; fax_fusion: SwapFusionEncoder's arguments.
+
+forward(batch_dict): batch_dict['processed_lidar'] = {voxel_features (P, T <= 32, 4) fp32, voxel_coords (P, 4) [n, z, y, x],
+voxel_num_points (P,)} and batch_dict['record_len'] (B,) -> {'fused_feature': (B, 64, ny, nx)} fp32.  The front end is ONE operator
+call (two launches) from the voxels straight into the (B, max_cav, ny, nx, 64) canvas FuseBEVT reads; rows whose batch index is
+negative are skipped, which is how a caller pads P to a fixed size for graph replay."""
+import torch
+
+from .. import ops
+from ..lib import CobevtHipError
+from . import runtime as rt
+from .pillar_vfe import PillarVFE
+from .point_pillar_scatter import PointPillarScatter
+from .runtime import HipModule
+from .swap_fusion_modules import SwapFusionEncoder
+
+
+class PointPillarFuseBEVT(HipModule):
+    def __init__(self, args):
+        super().__init__()
+        self.max_cav = args["max_cav"]
+        vfe_cfg = dict(args["pillar_vfe"])
+        if "max_points_per_voxel" in args and "max_points_per_voxel" not in vfe_cfg:
+            vfe_cfg["max_points_per_voxel"] = args["max_points_per_voxel"]
+        self.pillar_vfe = PillarVFE(vfe_cfg, num_point_features=4, voxel_size=args["voxel_size"],
+                                    point_cloud_range=args["lidar_range"])
+        self.scatter = PointPillarScatter(args["point_pillar_scatter"])
+        self.fusion_net = SwapFusionEncoder(args["fax_fusion"])
+        c = self.pillar_vfe.get_output_feature_dim()
+        if self.scatter.num_bev_features != c or args["fax_fusion"]["input_dim"] != c:
+            raise CobevtHipError("PointPillarFuseBEVT: point_pillar_scatter.num_features and fax_fusion.input_dim must equal the "
+                                 "PFN layer's %d channels" % c)
+        if self.max_cav < 1:
+            raise CobevtHipError("PointPillarFuseBEVT: max_cav must be at least 1")
+
+    def front_end(self, batch_dict, out=None):
+        """voxels -> (canvas (B, max_cav, ny, nx, 64) in the compute dtype, cav_mask (B, max_cav) fp32): one operator call"""
+        lidar = batch_dict["processed_lidar"]
+        vf, coords, npts = lidar["voxel_features"], lidar["voxel_coords"], lidar["voxel_num_points"]
+        self._require_inference(vf, coords, npts)
+        rl = torch.as_tensor(batch_dict["record_len"]).to(device=vf.device, dtype=torch.int32)
+        w, shift = self.pillar_vfe.pfn_layers[0].folded()
+        return ops.pillar_vfe_scatter(vf, npts, coords, w, shift, self.pillar_vfe.geom(), (self.scatter.ny, self.scatter.nx),
+                                      rt.get_compute_dtype(), use_absolute_xyz=self.pillar_vfe.use_absolute_xyz,
+                                      with_distance=self.pillar_vfe.with_distance, record_len=rl, max_cav=self.max_cav, out=out)
+
+    def forward(self, batch_dict):
+        self._require_inference()
+        x, cav_mask = self.front_end(batch_dict)
+        b, l, h, w, _ = x.shape
+        # the agent mask as CorpBEVT.fuse_and_decode builds it without an ROI mask (corpbevt.py:125-128)
+        com_mask = cav_mask[:, None, None, None, :].expand(b, h, w, 1, l).contiguous()
+        fused = self.fusion_net.forward_blhwc(x, com_mask)                      # (B, ny, nx, 64)
+        return {"fused_feature": rt.nchw_view(fused).float()}

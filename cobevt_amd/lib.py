@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("COBEVT_HIP_LIB") or LIB_PATH
 
 _c_int_p = ctypes.POINTER(ctypes.c_int)
 _c_long_p = ctypes.POINTER(ctypes.c_long)
+_c_float_p = ctypes.POINTER(ctypes.c_float)
 _vp = ctypes.c_void_p
 
 # name -> (restype, argtypes); must list every symbol of include/cobevt_hip.h
@@ -136,6 +137,8 @@ SIGNATURES = {
                                             _c_int_p, _c_int_p, ctypes.c_long, ctypes.c_long, _vp]),
     "cobevt_host_fetch": (ctypes.c_int, [_vp, _vp, ctypes.c_long, ctypes.c_int, _vp]),
     "cobevt_channel_gate_nhwc": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]),
+    "cobevt_pillar_vfe": (ctypes.c_int, [_vp] * 8 + [_c_int_p, _c_float_p, _vp]),
+    "cobevt_scatter_rows": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_long] + [ctypes.c_int] * 4 + [_vp]),
 }
 
 _libs = {}

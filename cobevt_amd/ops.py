@@ -1076,6 +1076,127 @@ def regroup(x, record_len, max_cav):
     return out, mask
 
 
+PILLAR_CHANNELS = 64        # the one PFN layer csrc/pillar_vfe.hip implements
+PILLAR_MAX_POINTS = 32      # a pillar's points sit on the lanes of one half-wave
+
+
+def _index_i32(t, what, shape_tail=None):
+    """int32 contiguous device index tensor; an int64 one is converted on the device (no host round trip)"""
+    if t.dtype == torch.int64:
+        t = t.to(torch.int32)
+    if t.dtype != torch.int32:
+        raise CobevtHipError("%s must be an int32 (or int64) tensor, got %s" % (what, t.dtype))
+    if shape_tail is not None and tuple(t.shape[1:]) != shape_tail:
+        raise CobevtHipError("%s must have shape (P%s), got %s" % (what, "".join(", %d" % d for d in shape_tail), tuple(t.shape)))
+    return t if t.is_contiguous() else t.contiguous()
+
+
+def _pillar_call(voxel_features, voxel_num_points, voxel_coords, w, shift, geom, use_absolute_xyz, with_distance, out, dtype, rows,
+                 record_len, cav, n, b, max_cav, ny, nx):
+    _need_cuda(voxel_features, voxel_num_points, voxel_coords, w, shift, record_len, out)
+    if voxel_features.dtype != torch.float32 or voxel_features.dim() != 3 or not voxel_features.is_contiguous():
+        raise CobevtHipError("pillar_vfe: voxel_features must be contiguous fp32 (P, T, F)")
+    p, t, f = voxel_features.shape
+    k = (4 if use_absolute_xyz else 1) + 6 + (1 if with_distance else 0)
+    if f != 4 or t < 1 or t > PILLAR_MAX_POINTS:
+        raise CobevtHipError("pillar_vfe: F = 4 point features and 1 <= T <= %d points per pillar are supported, got F = %d, T = %d"
+                             % (PILLAR_MAX_POINTS, f, t))
+    if w.dtype != torch.float32 or shift.dtype != torch.float32 or not w.is_contiguous() or not shift.is_contiguous() \
+            or tuple(w.shape) != (k, PILLAR_CHANNELS) or tuple(shift.shape) != (PILLAR_CHANNELS,):
+        raise CobevtHipError("pillar_vfe: folded weight / shift must be contiguous fp32 (%d, %d) / (%d)" % (k, PILLAR_CHANNELS, PILLAR_CHANNELS))
+    npts = _index_i32(voxel_num_points, "pillar_vfe: voxel_num_points", ())
+    coords = _index_i32(voxel_coords, "pillar_vfe: voxel_coords", (4,))
+    if npts.shape[0] != p or coords.shape[0] != p:
+        raise CobevtHipError("pillar_vfe: voxel_num_points (P) and voxel_coords (P, 4) must match voxel_features' P = %d" % p)
+    if len(geom) != 6:
+        raise CobevtHipError("pillar_vfe: geom = (voxel x, y, z, offset x, y, z)")
+    dims = _ints([p, t, f, k, int(bool(use_absolute_xyz)), int(bool(with_distance)), dcode(dtype), rows, n, b, max_cav, ny, nx])
+    g = (ctypes.c_float * 6)(*[float(v) for v in geom])
+    rc = _L.load().cobevt_pillar_vfe(_p(voxel_features), _p(npts), _p(coords), _p(w), _p(shift), _p(record_len), _p(out), _p(cav), dims, g,
+                                     _stream())
+    _L.check(rc, "cobevt_pillar_vfe")
+
+
+def _canvas(out, shape, dtype, device, what):
+    if out is None:
+        return torch.empty(shape, device=device, dtype=dtype)
+    if tuple(out.shape) != tuple(shape) or out.dtype != dtype or not out.is_contiguous() or out.device != device:
+        raise CobevtHipError("%s: out= must be a contiguous %s tensor of shape %s on %s" % (what, dtype, tuple(shape), device))
+    return out
+
+
+def pillar_vfe_scatter(voxel_features, voxel_num_points, voxel_coords, w, shift, geom, grid, dtype, use_absolute_xyz=True,
+                       with_distance=False, record_len=None, max_cav=None, num_agents=None, out=None):
+    """PillarVFE (one 64-channel PFN layer) + PointPillarScatter (+ regroup) in one operator (csrc/pillar_vfe.hip).
+    voxel_features (P, T <= 32, 4) fp32; voxel_num_points (P); voxel_coords (P, 4) as [n, z, y, x] (int32, or int64: converted on the
+    device); w (K, 64) / shift (64) fp32 folded layer; geom = (voxel x, y, z, offset x, y, z); grid = (ny, nx); dtype: the canvas's.
+    With record_len (int32 device (B,)) and max_cav: -> canvas (B, max_cav, ny, nx, 64), cav_mask (B, max_cav) fp32 as ops.regroup;
+    num_agents (host int, optional) is a further upper bound on the batch indices; by default only record_len bounds them.  Without: -> canvas (num_agents, ny, nx, 64), None.
+    Every element of the canvas is written (cells without a pillar and padded agent slots with 0, whatever `out=` held).  Rows with a
+    batch index < 0 (the padding convention for a fixed P under graph replay) or >= num_agents, in a slot >= max_cav, with y / x
+    outside the grid or voxel_num_points <= 0 are skipped.  No host synchronisation."""
+    ny, nx = int(grid[0]), int(grid[1])
+    dev = voxel_features.device
+    if record_len is not None:
+        _need_cuda(record_len)
+        if record_len.dtype != torch.int32 or record_len.dim() != 1 or not record_len.is_contiguous() or max_cav is None:
+            raise CobevtHipError("pillar_vfe_scatter: record_len must be int32 (B,) on the device, with max_cav given")
+        b, l = record_len.shape[0], int(max_cav)
+        # with record_len the slot search already rejects n >= sum(record_len): no second bound unless the caller gives one (a sample
+        # with more than max_cav agents pushes later samples' agent indices past B * max_cav)
+        n = 0x7fffffff if num_agents is None else int(num_agents)
+        shape = (b, l, ny, nx, PILLAR_CHANNELS)
+        cav = torch.empty((b, l), device=dev, dtype=torch.float32)
+    else:
+        if num_agents is None:
+            raise CobevtHipError("pillar_vfe_scatter: num_agents (a host integer) is required without record_len")
+        b, l, n, cav = 0, 0, int(num_agents), None
+        shape = (n, ny, nx, PILLAR_CHANNELS)
+    if n < 1 or ny < 1 or nx < 1 or (record_len is not None and (b < 1 or l < 1)):
+        raise CobevtHipError("pillar_vfe_scatter: empty canvas %s" % (shape,))
+    _need_cuda(voxel_features)
+    out = _canvas(out, shape, dtype, dev, "pillar_vfe_scatter")
+    k = (4 if use_absolute_xyz else 1) + 6 + (1 if with_distance else 0)
+    pts = voxel_features.shape[0] * voxel_features.shape[1]
+    cost = lambda: (2.0 * pts * k * PILLAR_CHANNELS, 16.0 * pts + out.numel() * out.element_size())         # noqa: E731
+    with _timed("pillar_vfe|P%d T%d %dx%d" % (voxel_features.shape[0], voxel_features.shape[1], ny, nx), cost):
+        _pillar_call(voxel_features, voxel_num_points, voxel_coords, w, shift, geom, use_absolute_xyz, with_distance, out, dtype, 0,
+                     record_len, cav, n, b, l, ny, nx)
+    return out, cav
+
+
+def pillar_vfe_rows(voxel_features, voxel_num_points, voxel_coords, w, shift, geom, dtype, use_absolute_xyz=True, with_distance=False):
+    """The same layer as dense rows: -> (P, 64) in `dtype`, row p = pillar p (always two-dimensional: the reference's squeeze()
+    collapses P = 1).  A pillar with voxel_num_points <= 0 gives a zero row."""
+    _need_cuda(voxel_features)
+    out = torch.empty((voxel_features.shape[0], PILLAR_CHANNELS), device=voxel_features.device, dtype=dtype)
+    if out.numel() == 0:
+        dcode(dtype)
+        return out
+    _pillar_call(voxel_features, voxel_num_points, voxel_coords, w, shift, geom, use_absolute_xyz, with_distance, out, dtype, 1,
+                 None, None, 0, 0, 0, 0, 0)
+    return out
+
+
+def scatter_rows(rows, voxel_coords, num_agents, grid, out=None):
+    """PointPillarScatter: rows (P, C) bf16 / fp32 contiguous, voxel_coords (P, 4) [n, z, y, x] -> (num_agents, ny, nx, C) channels-last,
+    cell z + y * nx + x of agent n; every other element 0.  Rows with n outside [0, num_agents) or y / x outside the grid are skipped."""
+    _need_cuda(rows, voxel_coords, out)
+    if rows.dim() != 2 or not rows.is_contiguous() or (rows.shape[1] * rows.element_size()) % 16:
+        raise CobevtHipError("scatter_rows: rows must be contiguous (P, C) with C * element size a multiple of 16 bytes")
+    p, c = rows.shape
+    coords = _index_i32(voxel_coords, "scatter_rows: voxel_coords", (4,))
+    if coords.shape[0] != p:
+        raise CobevtHipError("scatter_rows: voxel_coords must be (P, 4) with P = %d" % p)
+    n, ny, nx = int(num_agents), int(grid[0]), int(grid[1])
+    if n < 1 or ny < 1 or nx < 1:
+        raise CobevtHipError("scatter_rows: empty canvas (%d, %d, %d, %d)" % (n, ny, nx, c))
+    out = _canvas(out, (n, ny, nx, c), rows.dtype, rows.device, "scatter_rows")
+    rc = _L.load().cobevt_scatter_rows(_p(rows), _p(coords), _p(out), dcode(rows.dtype), p, c, n, ny, nx, _stream())
+    _L.check(rc, "cobevt_scatter_rows")
+    return out
+
+
 def sttf_warp(x, tmat, cav_mask, discrete_ratio, downsample_rate, want_mask=True, record_len=None, max_cav=None):
     """x: (B, L, H, W, C) contiguous ; tmat (B, L, 4, 4) fp32 -> warped (B,L,H,W,C), com_mask (B,H,W,1,L)|None.
     With record_len (int32 device (B,)) x is the un-grouped agent batch (N, H, W, C): regroup + warp in one launch,

@@ -743,6 +743,29 @@ int cobevt_calibrate_copy(const void* src, void* dst, long bytes, hipStream_t st
 /* rate of the wall clock behind clk[1] and the device's maximum shader clock (kHz), of the current device */
 int cobevt_calibrate_clock_khz(int* wall_khz, int* sclk_max_khz);
 
+/*
+ * LiDAR pillar front end (csrc/pillar_vfe.hip): PillarVFE with ONE PFN layer of 64 channels (pillar_vfe.py:10-53, 105-146), fused with
+ * PointPillarScatter (point_pillar_scatter.py:14-47) and regroup (fuse_utils.py:8-61).  fp32 VALU arithmetic in every library; only
+ * the store converts to `dtype`.
+ *   voxel_features (P, T, 4) fp32, T <= 32; voxel_num_points (P) int32; voxel_coords (P, 4) int32 as [n, z, y, x];
+ *   w (K, 64) / shift (64) fp32: the eval BatchNorm1d folded into the bias-free Linear (or the Linear's weight^T and bias);
+ *   dims  = [P, T, F = 4, K, use_absolute_xyz, with_distance, dtype, rows, N, B, max_cav, ny, nx] (host), K = (4 | 1) + 6 + (1 | 0);
+ *   geom  = [voxel x, y, z, offset x, y, z] (host), offset = voxel / 2 + range minimum.
+ * rows = 0: `out` is the channels-last canvas - (B, max_cav, ny, nx, 64) with record_len (device int32 (B)), which also writes
+ * cav_mask (B, max_cav) fp32 as cobevt_regroup does, or (N, ny, nx, 64) when record_len is NULL.  Two launches: every 16-byte chunk of
+ * the canvas <- 0, then one 64-channel row per pillar at cell z + y * nx + x of its agent's slot.  A pillar is skipped (never
+ * written) when its batch index is negative, >= N or regroups to a slot >= max_cav, when y or x lies outside the grid, or when
+ * voxel_num_points <= 0.  Coordinates are unique per agent (the voxel generator's contract).  No atomics, no host synchronisation.
+ * rows = 1: `out` is (P, 64), destination row = p (a pillar with voxel_num_points <= 0 gives a zero row); N .. nx are ignored.
+ */
+int cobevt_pillar_vfe(const float* voxel_features, const int* voxel_num_points, const int* voxel_coords, const float* w,
+                      const float* shift, const int* record_len, void* out, float* cav_mask, const int* dims, const float* geom,
+                      hipStream_t stream);
+/* PointPillarScatter on given rows: rows (P, C) in `dtype` (C * element size a multiple of 16) -> out (N, ny, nx, C), every chunk
+ * zeroed first; the skip rules of the fused operator without the point count. */
+int cobevt_scatter_rows(const void* rows, const int* voxel_coords, void* out, int dtype, long P, int C, int N, int ny, int nx,
+                        hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
