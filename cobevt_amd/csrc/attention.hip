@@ -637,7 +637,7 @@ static int window_attention_impl(const void* q, const void* k, const void* v, vo
         if (dtype == 0) hipLaunchKernelGGL(attn_ksplit_merge_kernel<bf16_t>, mg, dim3(256), 0, stream, p);
         else hipLaunchKernelGGL(attn_ksplit_merge_kernel<float>, mg, dim3(256), 0, stream, p);
     }
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }
 
 // Key-split form of cobevt_window_attention, see include/cobevt_hip.h
@@ -682,7 +682,7 @@ extern "C" int cobevt_attention_dropout_mask(int B, int L, int heads, int Nq, in
     AttnParams p = {};
     p.B = B; p.L = L; p.heads = heads; p.Nq = Nq; p.Nk = Nk; p.drop_p = drop_p; p.drop_seed = drop_seed;
     hipLaunchKernelGGL(attn_dropout_mask_kernel, dim3(2048), dim3(256), 0, stream, p, keep);
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }
 
 // Test hooks (tests/test_kernels_gpu.py: bit-exact against tests/golden/gv1_index_maps.npz), see include/cobevt_hip.h
@@ -694,7 +694,7 @@ extern "C" int cobevt_attention_index_map(const int* map8, int B, int* rows, hip
     const long total = (long)B * L * ntok;
     hipLaunchKernelGGL(attn_index_dump_kernel, dim3((unsigned)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256)), dim3(256), 0,
                        stream, m, B, L, ntok, rows);
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }
 
 extern "C" int cobevt_attention_bias_index(const int* qmap8, const int* kmap8, int bias_L, int* idx, hipStream_t stream) {
@@ -705,5 +705,5 @@ extern "C" int cobevt_attention_bias_index(const int* qmap8, const int* kmap8, i
     const long total = (long)nq * nk;
     hipLaunchKernelGGL(attn_bias_index_dump_kernel, dim3((unsigned)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256)), dim3(256),
                        0, stream, qm, km, bias_L, nq, nk, idx);
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }

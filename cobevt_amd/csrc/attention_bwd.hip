@@ -22,6 +22,7 @@
 // The softmax is recomputed in both (3 extra products over the minimal 5): 7 x 10^4 fp32 MFMAs are cheaper than the atomics.
 // The partitions / reverses are the forward's index arithmetic (attn_common.hpp).
 #include "attn_common.hpp"
+#include "wave_ops.hpp"
 
 namespace cobevt {
 
@@ -54,23 +55,6 @@ constexpr int kMaskedKey = (int)0x80000000;   // per-key info of a masked / out-
 // the k-slots (half h, element e) of instruction m then stand for row 16 m + 8 (e / 4) + 4 h + e % 4 = acc_row(8 m + e, lane), i.e. the B
 // operand is the lane's accumulator registers 8 m .. 8 m + 7 packed to bf16, unchanged.
 constexpr int kRowB = 80;     // bytes per row of a bf16 tile
-// four consecutive elements at element offset `off` of an fp32 (sb = 0) or bf16 (sb = 1) tensor
-__device__ __forceinline__ float4 ld4q(const void* base, size_t off, int sb) {
-    if (sb) {
-        const uint2 u = *(const uint2*)((const uint16_t*)base + off);
-        return make_float4(__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u), __uint_as_float(u.y << 16), __uint_as_float(u.y & 0xffff0000u));
-    }
-    return *(const float4*)((const float*)base + off);
-}
-__device__ __forceinline__ void st4q(void* base, size_t off, int sb, const float4& v) {
-    if (sb) *(uint2*)((uint16_t*)base + off) = make_uint2(pack_bf2(v.x, v.y), pack_bf2(v.z, v.w));
-    else *(float4*)((float*)base + off) = v;
-}
-typedef short v4s_b __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ uint2 tr_read_b(const unsigned char* lds) {
-    const v4s_b r = __builtin_amdgcn_ds_read_tr16_b64_v4i16((v4s_b __attribute__((address_space(3)))*)lds);
-    return __builtin_bit_cast(uint2, r);
-}
 // accumulator registers 8 M .. 8 M + 7 as one bf16 operand (constant indices: an indexed copy of the vector went through scratch)
 template <int M> __device__ __forceinline__ bf16x8 pack_acc8(const f32x16& v) {
     return __builtin_bit_cast(bf16x8, make_uint4(pack_bf2(v[8 * M], v[8 * M + 1]), pack_bf2(v[8 * M + 2], v[8 * M + 3]),
@@ -83,7 +67,7 @@ __device__ __forceinline__ uint4 pack8f4(const float4& a, const float4& b) {
 __device__ __forceinline__ bf16x8 tr_operand(const unsigned char* tile, int lane, int m) {
     const int g = lane >> 4, i = lane & 15;
     const unsigned char* a = tile + (16 * m + 4 * (g >> 1) + (i >> 2)) * kRowB + (16 * (g & 1) + 4 * (i & 3)) * 2;
-    const uint2 lo = tr_read_b(a), hi = tr_read_b(a + 8 * kRowB);
+    const uint2 lo = tr_read(a), hi = tr_read(a + 8 * kRowB);
     return __builtin_bit_cast(bf16x8, make_uint4(lo.x, lo.y, hi.x, hi.y));
 }
 
@@ -740,11 +724,6 @@ __global__ __launch_bounds__(256) void attn_bwd_q4_kernel(AttnBwdParams bp) {
     }
 }
 
-template <typename K>
-static void set_max_lds(K kernel) {
-    (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-}
-
 }  // namespace
 }  // namespace cobevt
 
@@ -813,8 +792,10 @@ extern "C" int cobevt_window_attention_bwd(const void* q, const void* k, const v
     const bool hb = p.bias_mode != 0, hm = mask != nullptr;
 #define COBEVT_BWD_LAUNCH2(B_, M_, F_)                                                                \
     do {                                                                                              \
-        static cobevt::PerDeviceOnce attr;                                                                   \
-        if (attr.first()) { set_max_lds(attn_bwd_kv_kernel<B_, M_, F_>); set_max_lds(attn_bwd_q_kernel<B_, M_, F_>); set_max_lds(attn_bwd_kv2_kernel<B_, M_>); set_max_lds(attn_bwd_q4_kernel<B_, M_>); } \
+        allow_dynamic_lds<attn_bwd_kv_kernel<B_, M_, F_>>(160 * 1024);                                \
+        allow_dynamic_lds<attn_bwd_q_kernel<B_, M_, F_>>(160 * 1024);                                 \
+        allow_dynamic_lds<attn_bwd_kv2_kernel<B_, M_>>(160 * 1024);                                   \
+        allow_dynamic_lds<attn_bwd_q4_kernel<B_, M_>>(160 * 1024);                                    \
         if (F_ && kv2) {                                                                              \
             hipLaunchKernelGGL((attn_bwd_q4_kernel<B_, M_>), grid_q4, block, lds_q4, stream, bp2);    \
             hipLaunchKernelGGL((attn_bwd_kv2_kernel<B_, M_>), grid_kv2, block, lds_kv, stream, bp2);  \
@@ -830,5 +811,5 @@ extern "C" int cobevt_window_attention_bwd(const void* q, const void* k, const v
     else COBEVT_BWD_LAUNCH(false, false);
 #undef COBEVT_BWD_LAUNCH
 #undef COBEVT_BWD_LAUNCH2
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }

@@ -17,6 +17,7 @@
 // MFMA mapping as in attention.hip: S^T = K.Q^T (lane = query), O^T += V^T.P^T.
 #include <stdlib.h>
 #include "attn_common.hpp"
+#include "wave_ops.hpp"
 
 namespace cobevt {
 
@@ -25,10 +26,6 @@ namespace {
 constexpr float kLog2e = 1.4426950408889634f;
 constexpr float kHeadroom = 1.099511627776e12f;   // 2^40: a tile is redone against its exact maximum when a row sum exceeds this
 constexpr float kTiny = 8.271806125530277e-25f;   // 2^-80: a task is redone exactly when a row's total sum ends up below this
-
-__device__ __forceinline__ int perm16(int k) {   // swap bits 2 and 3: key order inside a 16-key MFMA k-block
-    return (k & ~12) | ((k & 4) << 1) | ((k & 8) >> 1);
-}
 
 __device__ __forceinline__ float max3(float a, float b, float c) { return fmaxf(fmaxf(a, b), c); }
 
@@ -42,17 +39,6 @@ __device__ __forceinline__ uint4 scale_bf16x8(const uint4& v, float sc) {
         o[i] = pack_bf2(f.x, f.y);
     }
     return make_uint4(o[0], o[1], o[2], o[3]);
-}
-
-// max / sum across the two half-waves (lane ^ 32) without LDS: v_permlane32_swap exchanges the upper half of the first
-// operand with the lower half of the second, so {r0, r1} = {own, partner} in one order or the other on every lane
-__device__ __forceinline__ float xor32_max(float v) {
-    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-}
-__device__ __forceinline__ float xor32_sum(float v) {
-    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
 }
 
 #ifdef COBEVT_RES_TRACE
@@ -564,7 +550,7 @@ __global__ __launch_bounds__(NW * 64, NT > 8 ? 1 : (BIAS || MASK || PERSIST) ? 2
                 }
                 if (SUMV) {
                     const f32x2 t2 = (ls2[0] + ls2[1]) + (ls2[2] + ls2[3]);
-                    l_run = xor32_sum(t2.x + t2.y);
+                    l_run = xhalf_sum(t2.x + t2.y);
                 } else {
                     l_run = lt[0];
                 }
@@ -642,7 +628,7 @@ __global__ __launch_bounds__(NW * 64, NT > 8 ? 1 : (BIAS || MASK || PERSIST) ? 2
                                 for (int r = 3; r < 15; r += 2) m0 = max3(m0, st[r], st[r + 1]);
                                 mloc = max3(mloc, m0, st[15]);
                             }
-                            float m_new = fmaxf(m_run, xor32_max(mloc));
+                            float m_new = fmaxf(m_run, xhalf_max(mloc));
                             if (INFO) m_new = __uint_as_float(__float_as_uint(m_new) & 0xffff0000u);     // a bf16 value (see qaugm)
                             const float m_safe = (m_new == -INFINITY) ? 0.f : m_new;
                             const float alpha = __builtin_amdgcn_exp2f(m_run - m_safe);       // first tile: exp2(-inf) = 0
@@ -769,7 +755,7 @@ int launch_nt(const AttnParams& p, int qsplit, size_t lds, dim3 grid, hipStream_
     else COBEVT_RES_LAUNCH(false, false, false, false);
 #undef COBEVT_RES_LAUNCH
 #undef COBEVT_RES_LAUNCH_W8
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }
 
 // windows of 513 .. 1024 keys: the plain variant only (four waves, one workgroup per CU)
@@ -777,7 +763,7 @@ template <int NT>
 int launch_big(const AttnParams& p, int qsplit, size_t lds, dim3 grid, hipStream_t stream) {
     if (p.Nk != NT * 64) hipLaunchKernelGGL((attn_resident_kernel<NT, 4, false, false, false, true>), grid, dim3(256), lds, stream, p, qsplit);
     else hipLaunchKernelGGL((attn_resident_kernel<NT, 4, false, false, false, false>), grid, dim3(256), lds, stream, p, qsplit);
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }
 
 }  // namespace

@@ -423,12 +423,12 @@ static int launch_basicblock(BasicBlockParams p, hipStream_t stream) {
     long blocks = (long)p.N * p.tiles_y * p.tiles_x;
     if (blocks <= 0 || blocks > 0x7fffffffL) return COBEVT_ERR_SHAPE;
     p.ntiles = (int)blocks;
-    static cobevt::PerDeviceOnce attr_once;
+    cobevt::allow_dynamic_lds<basicblock_kernel<T, C, TH_>>(G::LDS);
+    static cobevt::PerDeviceOnce cu_once;
     static int cu_slots[16];
     int dev = 0;
     (void)hipGetDevice(&dev);
-    if (attr_once.first()) {
-        (void)hipFuncSetAttribute((const void*)basicblock_kernel<T, C, TH_>, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS);
+    if (cu_once.first()) {
         int cus = 0;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
         const int per_cu = (160 * 1024) / (G::LDS + 2048) < 1 ? 1 : (160 * 1024) / (G::LDS + 2048);     // workgroups of this kernel a CU holds
@@ -436,7 +436,7 @@ static int launch_basicblock(BasicBlockParams p, hipStream_t stream) {
     }
     if (G::PERSIST && cu_slots[dev & 15] > 0 && blocks > cu_slots[dev & 15]) blocks = cu_slots[dev & 15];
     hipLaunchKernelGGL((basicblock_kernel<T, C, TH_>), dim3((unsigned)blocks), dim3(G::NT), G::LDS, stream, p);
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -719,12 +719,9 @@ extern "C" int cobevt_dsblock_nhwc(const void* in, const void* wfrag1, const flo
     p.tiles_x = (p.Wo + DsCfg::TW - 1) / DsCfg::TW;
     const long blocks = (long)p.N * p.tiles_y * p.tiles_x;
     if (blocks <= 0 || blocks > 0x7fffffffL) return COBEVT_ERR_SHAPE;
-    static cobevt::PerDeviceOnce attr_once;
-    if (attr_once.first()) {
-        (void)hipFuncSetAttribute((const void*)dsblock_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, DsCfg::LDS);
-    }
+    cobevt::allow_dynamic_lds<dsblock_kernel>(DsCfg::LDS);
     hipLaunchKernelGGL(dsblock_kernel, dim3((unsigned)blocks), dim3(512), DsCfg::LDS, stream, p);
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }
 
 #ifdef COBEVT_BB_TRACE

@@ -11,6 +11,7 @@
 // with one v_permlane32_swap) and feeds the packed rows straight to the to_q MFMAs, whose weight fragments sit in LDS for the
 // life of the (persistent) workgroup.  No barrier after the prologue; HBM sees x once and q once.
 #include "bev_query.hpp"
+#include "wave_ops.hpp"
 
 namespace cobevt {
 
@@ -22,23 +23,10 @@ constexpr int kWBytes = 32 * 1024;                 // 32 fragments
 //      | czw[B n][128] bf16 pair {cz_hi, cz_lo} of (b_bev - w_cam . c) | bias[128]
 constexpr int kLdsBytes = kWBytes + 128 * 16 + kMaxCams * 128 * 4 + 128 * 4;
 
-__device__ __forceinline__ float xhalf_sum(float v) {
-    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-__device__ __forceinline__ void half_swap(uint2& a, uint2& b) {      // see row_chain64.hip
-    auto r = __builtin_amdgcn_permlane32_swap(a.x, b.x, false, false);
-    a.x = r[0]; b.x = r[1];
-    r = __builtin_amdgcn_permlane32_swap(a.y, b.y, false, false);
-    a.y = r[0]; b.y = r[1];
-}
-__device__ __forceinline__ uint4 pack8(const float* v) {
-    return make_uint4(pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3]), pack_bf2(v[4], v[5]), pack_bf2(v[6], v[7]));
-}
 // x = hi + lo with both halves bf16 values (|x - hi - lo| <= 2^-17 |x|)
 __device__ __forceinline__ void split_bf(float x, float& hi, float& lo) {
-    hi = bf2f(f2bf(x));
-    lo = bf2f(f2bf(x - hi));
+    hi = rbf(x);
+    lo = rbf(x - hi);
 }
 
 // The embedding  em[row][ch] = w_bev[ch] . world[row] + (b_bev[ch] - w_cam[ch] . c_cam)  is a K = 3 matrix product; on the VALU it
@@ -162,10 +150,10 @@ __global__ __launch_bounds__(NW * 64, 3) void bev_query_kernel(BevQueryParams p,
                 uint2 s0 = make_uint2(xr[2 * t + m].x, xr[2 * t + m].y), s1 = make_uint2(xr[2 * t + m].z, xr[2 * t + m].w);
                 half_swap(s0, s1);
                 float* d = &em[t][8 * m];
-                d[0] = bf2f(f2bf(d[0] * inv + bf2f(s0.x & 0xffff))); d[1] = bf2f(f2bf(d[1] * inv + bf2f(s0.x >> 16)));
-                d[2] = bf2f(f2bf(d[2] * inv + bf2f(s0.y & 0xffff))); d[3] = bf2f(f2bf(d[3] * inv + bf2f(s0.y >> 16)));
-                d[4] = bf2f(f2bf(d[4] * inv + bf2f(s1.x & 0xffff))); d[5] = bf2f(f2bf(d[5] * inv + bf2f(s1.x >> 16)));
-                d[6] = bf2f(f2bf(d[6] * inv + bf2f(s1.y & 0xffff))); d[7] = bf2f(f2bf(d[7] * inv + bf2f(s1.y >> 16)));
+                d[0] = rbf(d[0] * inv + bf2f(s0.x & 0xffff)); d[1] = rbf(d[1] * inv + bf2f(s0.x >> 16));
+                d[2] = rbf(d[2] * inv + bf2f(s0.y & 0xffff)); d[3] = rbf(d[3] * inv + bf2f(s0.y >> 16));
+                d[4] = rbf(d[4] * inv + bf2f(s1.x & 0xffff)); d[5] = rbf(d[5] * inv + bf2f(s1.x >> 16));
+                d[6] = rbf(d[6] * inv + bf2f(s1.y & 0xffff)); d[7] = rbf(d[7] * inv + bf2f(s1.y >> 16));
 #pragma unroll
                 for (int e = 0; e < 8; ++e) s += d[e];
             }
@@ -213,15 +201,12 @@ __global__ __launch_bounds__(NW * 64, 3) void bev_query_kernel(BevQueryParams p,
 int launch_bev_query(const BevQueryParams& p, hipStream_t stream) {
     if (p.hw % 32 != 0 || (long)p.B * p.n > kMaxCams || p.B < 1 || p.n < 1) return -1;
     constexpr int NW = 4;
-    static cobevt::PerDeviceOnce attr_once;
-    if (attr_once.first()) {
-        (void)hipFuncSetAttribute((const void*)bev_query_kernel<NW>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-    }
+    cobevt::allow_dynamic_lds<bev_query_kernel<NW>>(kLdsBytes);
     const int nblk = p.B * (p.hw >> 5) * p.n;
     int blocks = (nblk + NW - 1) / NW;
     if (blocks > 256 * 3) blocks = 256 * 3;                // persistent: three workgroups (12 waves) per CU
     hipLaunchKernelGGL((bev_query_kernel<NW>), dim3((unsigned)blocks), dim3(NW * 64), kLdsBytes, stream, p, nblk);
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }
 
 }  // namespace cobevt

@@ -220,8 +220,7 @@ extern "C" int cobevt_bottleneck_f32_nhwc(const void* in, const void* y1, const 
     p.tiles_x = (p.W + kTW - 1) / kTW;
     const long blocks = (long)p.N * p.tiles_y * p.tiles_x;
     if (blocks > 0x7fffffffL) return COBEVT_ERR_SHAPE;
-    static cobevt::PerDeviceOnce attr_once;
-    if (attr_once.first()) (void)hipFuncSetAttribute((const void*)bottleneck_f32_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
+    cobevt::allow_dynamic_lds<bottleneck_f32_kernel>(kLds);
     hipLaunchKernelGGL(bottleneck_f32_kernel, dim3((unsigned)blocks), dim3(kThreads), kLds, stream, p);
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }

@@ -49,7 +49,7 @@ __global__ __launch_bounds__(256) void calib_copy_kernel(const u32x4* __restrict
 extern "C" int cobevt_calibrate_mfma(float* out, long long* clk, int blocks, int iters, hipStream_t stream) {
     if (!out || !clk || blocks < 1 || iters < 1) return COBEVT_ERR_ARG;
     hipLaunchKernelGGL(calib_mfma_kernel, dim3(blocks), dim3(256), 0, stream, out, clk, iters);
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }
 
 extern "C" int cobevt_calibrate_clock_khz(int* wall_khz, int* sclk_max_khz) {
@@ -66,5 +66,5 @@ extern "C" int cobevt_calibrate_clock_khz(int* wall_khz, int* sclk_max_khz) {
 extern "C" int cobevt_calibrate_copy(const void* src, void* dst, long bytes, hipStream_t stream) {
     if (!src || !dst || bytes < 16 || (bytes & 15)) return COBEVT_ERR_ARG;
     hipLaunchKernelGGL(calib_copy_kernel, dim3(256 * 16), dim3(256), 0, stream, (const u32x4*)src, (u32x4*)dst, bytes / 16);
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }

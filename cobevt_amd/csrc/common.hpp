@@ -11,6 +11,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+// error codes shared with include/cobevt_hip.h
+#define COBEVT_OK 0
+#define COBEVT_ERR_ARG 1
+#define COBEVT_ERR_SHAPE 2
+#define COBEVT_ERR_LAUNCH 3
+#define COBEVT_ERR_UNSUPPORTED 4
+
 namespace cobevt {
 
 struct bf16_t { uint16_t bits; };
@@ -75,6 +82,20 @@ template <> __device__ __forceinline__ float load_elem<float>(const float* p, si
 template <typename T> __device__ __forceinline__ void store_elem(T* p, size_t i, float v);
 template <> __device__ __forceinline__ void store_elem<bf16_t>(bf16_t* p, size_t i, float v) { p[i].bits = f2bf(v); }
 template <> __device__ __forceinline__ void store_elem<float>(float* p, size_t i, float v) { p[i] = v; }
+
+// four consecutive elements at element offset `off` of an fp32 (sb = 0) or bf16 (sb = 1) tensor, as fp32 (the training kernels
+// take either storage behind one pointer)
+__device__ __forceinline__ float4 ld4q(const void* base, size_t off, int sb) {
+    if (sb) {
+        const uint2 u = *(const uint2*)((const uint16_t*)base + off);
+        return make_float4(__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u), __uint_as_float(u.y << 16), __uint_as_float(u.y & 0xffff0000u));
+    }
+    return *(const float4*)((const float*)base + off);
+}
+__device__ __forceinline__ void st4q(void* base, size_t off, int sb, const float4& v) {
+    if (sb) *(uint2*)((uint16_t*)base + off) = make_uint2(pack_bf2(v.x, v.y), pack_bf2(v.z, v.w));
+    else *(float4*)((float*)base + off) = v;
+}
 
 // COBEVT_F32_SPLIT = 1 builds the SECOND library of the package (cobevt_amd/build.py: libcobevt_hip_f32s.so, same sources, same
 // C ABI): every fp32-storage kernel of the inference path then takes its matrix products through the split-bf16 form below
@@ -370,13 +391,8 @@ template <typename T = float> __device__ __forceinline__ float apply_act(float x
     return x;
 }
 
-__device__ __forceinline__ float wave_sum_xor(float v, int width) {
-    for (int o = width >> 1; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// hipFuncSetAttribute(MaxDynamicSharedMemorySize) is a PER-DEVICE attribute: a launch site keeps one of these (static) and
-// raises the limit once per device the process launches on, not once per process.
+// hipFuncSetAttribute(MaxDynamicSharedMemorySize) is a PER-DEVICE attribute: the limit is raised once per device the process
+// launches on, not once per process.  Launch sites do not use this directly: they call allow_dynamic_lds below.
 struct PerDeviceOnce {
     unsigned long long done = 0;
     bool first() {
@@ -389,11 +405,14 @@ struct PerDeviceOnce {
     }
 };
 
-}  // namespace cobevt
+// Opt `Kernel` into `bytes` of dynamic LDS (more than the default 64 KB) on the current device; called in front of every launch
+// of such a kernel, it sets the attribute the first time the kernel is launched on a device.
+template <auto Kernel> inline void allow_dynamic_lds(int bytes) {
+    static PerDeviceOnce once;
+    if (once.first()) (void)hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+}
 
-// error codes shared with include/cobevt_hip.h
-#define COBEVT_OK 0
-#define COBEVT_ERR_ARG 1
-#define COBEVT_ERR_SHAPE 2
-#define COBEVT_ERR_LAUNCH 3
-#define COBEVT_ERR_UNSUPPORTED 4
+// what an entry point returns after its launches
+inline int launch_status() { return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH; }
+
+}  // namespace cobevt

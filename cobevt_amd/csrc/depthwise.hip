@@ -9,26 +9,10 @@
 // through L1 / L2 (k^2 / stride^2 reads per element, arithmetic intensity k^2 MACs per 2 bytes).
 // reference: efficientnet-pytorch 0.7.1 model.py MBConvBlock.forward (third-party, restated in oracle/efficientnet.py),
 // wrapped by nuscenes/cross_view_transformer/model/backbones/efficientnet.py:24-96.
-#include "common.hpp"
+#include "warp_common.hpp"
+#include "wave_ops.hpp"
 
 namespace cobevt {
-
-template <typename T> __device__ __forceinline__ void dw_load8(const T* p, float* v) {
-    if constexpr (Elem<T>::kIsBf16) {
-        chunk_to_f32<T>(*(const uint4*)p, v);
-    } else {
-        chunk_to_f32<T>(*(const uint4*)p, v);
-        chunk_to_f32<T>(*(const uint4*)(p + 4), v + 4);
-    }
-}
-template <typename T> __device__ __forceinline__ void dw_store8(T* p, const float* v) {
-    if constexpr (Elem<T>::kIsBf16) {
-        *(uint4*)p = f32_to_chunk<T>(v);
-    } else {
-        *(uint4*)p = f32_to_chunk<T>(v);
-        *(uint4*)(p + 4) = f32_to_chunk<T>(v + 4);
-    }
-}
 
 struct DwParams {
     const void* in; const float* wgt; const float* bias; void* out;
@@ -57,7 +41,7 @@ __global__ __launch_bounds__(256) void depthwise_conv_kernel(DwParams p) {
             const int ix = ix0 + kw;
             if (ix < 0 || ix >= p.W) continue;
             float x[8];
-            dw_load8<T>(in + ((size_t)iy * p.W + ix) * p.C, x);
+            load8<T>(in + ((size_t)iy * p.W + ix) * p.C, x);
             const float4 w0 = *(const float4*)(p.wgt + (size_t)(kh * p.k + kw) * p.C + g * 8);
             const float4 w1 = *(const float4*)(p.wgt + (size_t)(kh * p.k + kw) * p.C + g * 8 + 4);
             acc[0] = fmaf(x[0], w0.x, acc[0]); acc[1] = fmaf(x[1], w0.y, acc[1]);
@@ -68,7 +52,7 @@ __global__ __launch_bounds__(256) void depthwise_conv_kernel(DwParams p) {
     }
 #pragma unroll
     for (int e = 0; e < 8; ++e) acc[e] = apply_act(acc[e], p.act);
-    dw_store8<T>((T*)p.out + (size_t)pix * p.C + g * 8, acc);
+    store8<T>((T*)p.out + (size_t)pix * p.C + g * 8, acc);
 }
 
 // out[n][c] = mean over the hw pixels of in[n][.][c].  grid (ceil(C / 64), N), 256 threads = 32 pixel lanes x 8 chunks of
@@ -85,7 +69,7 @@ __global__ __launch_bounds__(256) void spatial_mean_kernel(const T* in, float* o
         const T* src = in + (size_t)n * hw * C + c0;
         for (int px = tp; px < hw; px += 32) {
             float x[8];
-            dw_load8<T>(src + (size_t)px * C, x);
+            load8<T>(src + (size_t)px * C, x);
 #pragma unroll
             for (int e = 0; e < 8; ++e) acc[e] += x[e];
         }
@@ -136,10 +120,10 @@ __global__ __launch_bounds__(256) void channel_gate_kernel(const T* in, const fl
     if (pix >= npix) return;
     const int n = (int)(pix / hw);
     float x[8];
-    dw_load8<T>(in + (size_t)pix * C + g * 8, x);
+    load8<T>(in + (size_t)pix * C + g * 8, x);
     const float4 a = *(const float4*)(gate + (size_t)n * C + g * 8), b = *(const float4*)(gate + (size_t)n * C + g * 8 + 4);
     x[0] *= a.x; x[1] *= a.y; x[2] *= a.z; x[3] *= a.w; x[4] *= b.x; x[5] *= b.y; x[6] *= b.z; x[7] *= b.w;
-    dw_store8<T>(out + (size_t)pix * C + g * 8, x);
+    store8<T>(out + (size_t)pix * C + g * 8, x);
 }
 
 }  // namespace cobevt
@@ -165,7 +149,7 @@ extern "C" int cobevt_depthwise_conv_nhwc(const void* in, const float* wgt, cons
     if (dims[0] == 0) hipLaunchKernelGGL(depthwise_conv_kernel<bf16_t>, dim3((unsigned)blocks), dim3(256), 0, stream, p);
     else if (dims[0] == 1) hipLaunchKernelGGL(depthwise_conv_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, stream, p);
     else return COBEVT_ERR_ARG;
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }
 
 extern "C" int cobevt_spatial_mean_nhwc(const void* in, float* out, int dtype, int N, int hw, int C, hipStream_t stream) {
@@ -175,7 +159,7 @@ extern "C" int cobevt_spatial_mean_nhwc(const void* in, float* out, int dtype, i
     if (dtype == 0) hipLaunchKernelGGL(spatial_mean_kernel<bf16_t>, grid, block, 0, stream, (const bf16_t*)in, out, hw, C);
     else if (dtype == 1) hipLaunchKernelGGL(spatial_mean_kernel<float>, grid, block, 0, stream, (const float*)in, out, hw, C);
     else return COBEVT_ERR_ARG;
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }
 
 extern "C" int cobevt_se_gate(const float* mean, const float* w_reduce, const float* b_reduce, const float* w_expand,
@@ -184,7 +168,7 @@ extern "C" int cobevt_se_gate(const float* mean, const float* w_reduce, const fl
     if (N < 1 || C < 1 || Cs < 1 || Cs > 4096) return COBEVT_ERR_SHAPE;
     hipLaunchKernelGGL(se_gate_kernel, dim3(N), dim3(256), (size_t)Cs * 4, stream, mean, w_reduce, b_reduce, w_expand, b_expand,
                        gate, C, Cs);
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }
 
 extern "C" int cobevt_channel_gate_nhwc(const void* in, const float* gate, void* out, int dtype, int N, int hw, int C,
@@ -196,5 +180,5 @@ extern "C" int cobevt_channel_gate_nhwc(const void* in, const float* gate, void*
     if (dtype == 0) hipLaunchKernelGGL(channel_gate_kernel<bf16_t>, dim3((unsigned)blocks), dim3(256), 0, stream, (const bf16_t*)in, gate, (bf16_t*)out, npix, hw, C);
     else if (dtype == 1) hipLaunchKernelGGL(channel_gate_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, stream, (const float*)in, gate, (float*)out, npix, hw, C);
     else return COBEVT_ERR_ARG;
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }

@@ -2,6 +2,7 @@
 // channels-last rows; a row of C channels is owned by a group of C/8 adjacent lanes so loads/stores stay
 // coalesced and the per-row reductions are xor-shuffles inside the group.
 #include "warp_common.hpp"
+#include "wave_ops.hpp"
 
 namespace cobevt {
 
@@ -428,7 +429,7 @@ static int launch1d(K kern, long work_items, hipStream_t stream, Args... args) {
     const long blocks = (work_items + 255) / 256;
     if (blocks <= 0 || blocks > 0x7fffffffL) return COBEVT_ERR_SHAPE;
     hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), 0, stream, args...);
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }
 
 static bool group_ok(int C) { const int G = C >> 3; return C % 8 == 0 && G >= 1 && G <= 64 && (G & (G - 1)) == 0; }
@@ -458,7 +459,7 @@ extern "C" int cobevt_fax_ray_embed(const float* I_inv, const float* E_inv, cons
     if (dtype == 0) hipLaunchKernelGGL(ray_embed_kernel<bf16_t>, grid, block, 0, stream, I_inv, E_inv, image_plane, w_img, w_cam, (bf16_t*)out, BN, hw, D);
     else if (dtype == 1) hipLaunchKernelGGL(ray_embed_kernel<float>, grid, block, 0, stream, I_inv, E_inv, image_plane, w_img, w_cam, (float*)out, BN, hw, D);
     else return COBEVT_ERR_ARG;
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }
 
 extern "C" int cobevt_fax_bev_embed(const float* E_inv, const float* world, const float* w_bev, const float* b_bev,
@@ -471,7 +472,7 @@ extern "C" int cobevt_fax_bev_embed(const float* E_inv, const float* world, cons
     if (dtype == 0) hipLaunchKernelGGL(bev_embed_kernel<bf16_t>, grid, block, 0, stream, E_inv, world, w_bev, b_bev, w_cam, (const bf16_t*)x, (bf16_t*)out, B, n, hw, D, x_bcast);
     else if (dtype == 1) hipLaunchKernelGGL(bev_embed_kernel<float>, grid, block, 0, stream, E_inv, world, w_bev, b_bev, w_cam, (const float*)x, (float*)out, B, n, hw, D, x_bcast);
     else return COBEVT_ERR_ARG;
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }
 
 extern "C" int cobevt_agent_max(const void* in, void* out, int dtype, int B, int L, long per, hipStream_t stream) {
@@ -544,7 +545,7 @@ extern "C" int cobevt_sttf_warp(const void* x, const float* tmat, const float* c
     if (dtype == 0) hipLaunchKernelGGL(sttf_warp_kernel<bf16_t>, grid, dim3(256), 0, stream, (const bf16_t*)x, tmat, cav_mask, (bf16_t*)out, com_mask, record_len, cav_out, B, L, H, W, C, discrete_ratio, downsample_rate);
     else if (dtype == 1) hipLaunchKernelGGL(sttf_warp_kernel<float>, grid, dim3(256), 0, stream, (const float*)x, tmat, cav_mask, (float*)out, com_mask, record_len, cav_out, B, L, H, W, C, discrete_ratio, downsample_rate);
     else return COBEVT_ERR_ARG;
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }
 
 extern "C" int cobevt_invert_small(const float* in, float* out, int n, int dim, hipStream_t stream) {
@@ -553,7 +554,7 @@ extern "C" int cobevt_invert_small(const float* in, float* out, int n, int dim, 
     const dim3 grid((n + 63) / 64), block(64);
     if (dim == 3) hipLaunchKernelGGL(invert_small_kernel<3>, grid, block, 0, stream, in, out, n);
     else hipLaunchKernelGGL(invert_small_kernel<4>, grid, block, 0, stream, in, out, n);
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }
 
 extern "C" int cobevt_resize_nhwc(const void* in, void* out, int dtype, int N, int H, int W, int C, int Ho, int Wo, int mode,
@@ -602,7 +603,7 @@ extern "C" int cobevt_host_fetch(const void* host_src, void* dst, long bytes, in
     if (blocks < 1) blocks = 128;
     if (blocks > 1024) blocks = 1024;
     hipLaunchKernelGGL(host_fetch_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, (const unsigned long long*)host_src, (unsigned long long*)dst, bytes / 8);
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }
 
 extern "C" const char* cobevt_strerror(int code) {

@@ -647,14 +647,11 @@ extern "C" int cobevt_linear_rows(const void* in, const void* wgt, const float* 
     if (blocks > 0x7fffffffL) return COBEVT_ERR_SHAPE;
     constexpr size_t lds = kGrLds;                 // A + W tiles (the fp32 staging (128 x 528) fits inside) + coefficients
     static_assert(128 * kGrStageRow <= 2 * kGrTile * kGrRow, "staging must fit");
-    static cobevt::PerDeviceOnce attr_once;
-    if (attr_once.first()) {
-        (void)hipFuncSetAttribute((const void*)gemm_rows_kernel<bf16_t, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute((const void*)gemm_rows_kernel<float, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    }
+    cobevt::allow_dynamic_lds<gemm_rows_kernel<bf16_t, false>>((int)lds);
+    cobevt::allow_dynamic_lds<gemm_rows_kernel<float, false>>((int)lds);
     if (dtype == 0) hipLaunchKernelGGL((gemm_rows_kernel<bf16_t, false>), dim3((unsigned)blocks), dim3(kGrThreads), lds, stream, p);
     else hipLaunchKernelGGL((gemm_rows_kernel<float, false>), dim3((unsigned)blocks), dim3(kGrThreads), lds, stream, p);
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }
 
 // C-ABI entry point, see include/cobevt_hip.h
@@ -682,14 +679,11 @@ extern "C" int cobevt_bev_embed_linear_rows(const float* E_inv, const float* wor
     p.emb_n = (int)n; p.emb_hw = (int)hw;
     const long blocks = (long)((p.M + 127) / 128) * ((p.N + 127) / 128);
     if (blocks > 0x7fffffffL) return COBEVT_ERR_SHAPE;
-    static cobevt::PerDeviceOnce attr_once;
-    if (attr_once.first()) {
-        (void)hipFuncSetAttribute((const void*)gemm_rows_kernel<bf16_t, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kGrLds);
-        (void)hipFuncSetAttribute((const void*)gemm_rows_kernel<float, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kGrLds);
-    }
+    cobevt::allow_dynamic_lds<gemm_rows_kernel<bf16_t, true>>(kGrLds);
+    cobevt::allow_dynamic_lds<gemm_rows_kernel<float, true>>(kGrLds);
     if (dtype == 0) hipLaunchKernelGGL((gemm_rows_kernel<bf16_t, true>), dim3((unsigned)blocks), dim3(kGrThreads), kGrLds, stream, p);
     else hipLaunchKernelGGL((gemm_rows_kernel<float, true>), dim3((unsigned)blocks), dim3(kGrThreads), kGrLds, stream, p);
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }
 
 // C-ABI entry point, see include/cobevt_hip.h
@@ -728,14 +722,11 @@ extern "C" int cobevt_linear_rows_wfrag(const void* in, const void* wfrag, const
     const long blocks = ntn * per_col;
     if (blocks > 0x7fffffffL) return COBEVT_ERR_SHAPE;
     const size_t lds = (size_t)kGrTile * kGrRow + (size_t)128 * (128 * (dtype == 0 ? 2 : 4) + 16);
-    static cobevt::PerDeviceOnce attr_once;
-    if (attr_once.first()) {
-        (void)hipFuncSetAttribute((const void*)gemm_rows2_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, 34816 + 34816);
-        (void)hipFuncSetAttribute((const void*)gemm_rows2_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, 34816 + 67584);
-    }
+    cobevt::allow_dynamic_lds<gemm_rows2_kernel<bf16_t>>(34816 + 34816);
+    cobevt::allow_dynamic_lds<gemm_rows2_kernel<float>>(34816 + 67584);
     if (dtype == 0) hipLaunchKernelGGL(gemm_rows2_kernel<bf16_t>, dim3((unsigned)blocks), dim3(kGrThreads), lds, stream, p);
     else hipLaunchKernelGGL(gemm_rows2_kernel<float>, dim3((unsigned)blocks), dim3(kGrThreads), lds, stream, p);
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }
 
 #ifdef COBEVT_GEMM_TRACE

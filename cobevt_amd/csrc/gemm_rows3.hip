@@ -12,8 +12,8 @@
 // LDS), wave w owns columns [32w, 32w+32) of every 128-column pass with the next pass's fragments in flight (two register
 // sets), D = W.X^T so a lane owns one row and runs of four consecutive columns (bias / residual / activation in registers),
 // results leave through a bf16 LDS tile as 16-byte coalesced stores.
-#include "common.hpp"
 #include "bev_query.hpp"
+#include "wave_ops.hpp"
 
 namespace cobevt {
 
@@ -151,7 +151,7 @@ __global__ __launch_bounds__(ROWS * 8, 4) void gemm_rows3_kernel(Gr3Params p) {
                     em[e] = (kb + e) < p.K ? (c.x * wx + c.y * wy + c.z) : 0.f;
                     ss += em[e] * em[e];
                 }
-                ss += __shfl_xor(ss, 1, 64); ss += __shfl_xor(ss, 2, 64); ss += __shfl_xor(ss, 4, 64);
+                ss = lane8_sum(ss);
                 const float inv = 1.0f / (sqrtf(ss) + 1e-7f);
 #pragma unroll
                 for (int e = 0; e < 16; ++e) v[e] = ok ? em[e] * inv + v[e] : 0.f;
@@ -160,6 +160,7 @@ __global__ __launch_bounds__(ROWS * 8, 4) void gemm_rows3_kernel(Gr3Params p) {
                 chunk_to_f32<bf16_t>(f32_to_chunk<bf16_t>(v + 8), v + 8);
             }
             if (p.ln) {                                   // Kp == 128 (checked by the entry point): the row is here
+                // (the 8-lane sums stay written out here: through lane8_sum the compiler schedules this kernel differently)
                 float s = 0.f;
 #pragma unroll
                 for (int e = 0; e < 16; ++e) s += v[e];
@@ -295,15 +296,12 @@ extern "C" int cobevt_linear_rows_small_k(const void* in, const void* wfrag, con
     p.emb_n = p.emb_hw = 1; p.emb_xbcast = 0;
     p.navg = 1; p.avg_rows_per_batch = 1; p.avg_stride = p.avg_batch_stride = 0;
     if (rows == 64) {
-        static cobevt::PerDeviceOnce attr_once;
-        if (attr_once.first()) {
-            (void)hipFuncSetAttribute((const void*)gemm_rows3_kernel<false, 64>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1040 + 64 * kG3Row + 4096 * 4);
-        }
+        cobevt::allow_dynamic_lds<gemm_rows3_kernel<false, 64>>(64 * 1040 + 64 * kG3Row + 4096 * 4);
         hipLaunchKernelGGL((gemm_rows3_kernel<false, 64>), dim3(blocks), dim3(512), lds, stream, p);
     } else {
         hipLaunchKernelGGL((gemm_rows3_kernel<false, 32>), dim3(blocks), dim3(256), lds, stream, p);
     }
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }
 
 // C-ABI entry point, see include/cobevt_hip.h
@@ -338,7 +336,7 @@ extern "C" int cobevt_bev_embed_linear_rows_small_k(const float* E_inv, const fl
     const size_t lds = (size_t)kG3Rows * (p.Kp * 2 + 16) + (size_t)kG3Rows * kG3Row + (size_t)((p.N + 127) / 128) * 128 * 4 + 128 * 16;
     const unsigned blocks = (unsigned)((p.M + kG3Rows - 1) / kG3Rows);
     hipLaunchKernelGGL((gemm_rows3_kernel<true, 32>), dim3(blocks), dim3(256), lds, stream, p);
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }
 
 // C-ABI entry point, see include/cobevt_hip.h: out (B * R, N) = act(LayerNorm?(mean_j in[b][j][r][:]) . W^T + bias), in (B, L, R, K)
@@ -363,5 +361,5 @@ extern "C" int cobevt_mean_linear_rows_small_k(const void* in, const void* wfrag
     const size_t lds = (size_t)kG3Rows * (p.Kp * 2 + 16) + (size_t)kG3Rows * kG3Row + (size_t)((p.N + 127) / 128) * 128 * 4;
     const unsigned blocks = (unsigned)((p.M + kG3Rows - 1) / kG3Rows);
     hipLaunchKernelGGL((gemm_rows3_kernel<false, 32>), dim3(blocks), dim3(256), lds, stream, p);
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }

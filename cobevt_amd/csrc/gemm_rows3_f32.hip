@@ -8,7 +8,7 @@
 // through stage_x_piece (already split in the split-bf16 / fp16 libraries), wave w owns columns [32 w, 32 w + 32) of every 128-column
 // pass, weights as MFMA fragments straight from L2 in two ping-pong sets of eight k-groups with the next set in flight, D = W . X^T so
 // bias / residual / activation happen in registers, results leave through an fp32 LDS tile as 16-byte coalesced stores.
-#include "common.hpp"
+#include "wave_ops.hpp"
 
 namespace cobevt {
 
@@ -83,6 +83,8 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_rows3_f32_kernel(Gr3fParams 
                 if (ok) t = *(const float4*)(src + sub * 16 + j * 4);
                 v[4 * j] = t.x; v[4 * j + 1] = t.y; v[4 * j + 2] = t.z; v[4 * j + 3] = t.w;
             }
+            // (normalise128 with the store folded in; the 8-lane sums stay written out: through lane8_sum the compiler schedules this
+            // kernel differently)
             float s = 0.f;
 #pragma unroll
             for (int e = 0; e < 16; ++e) s += v[e];
@@ -194,12 +196,10 @@ int launch_linear_rows_f32(const void* in, const void* wfrag, const float* bias,
     if ((pre_scale == nullptr) != (pre_shift == nullptr) || (p.ln && pre_scale)) return -1;
     if (p.act < 0 || p.act > 4) return -1;
     const size_t lds = (size_t)kRows * (p.Kp * 4 + 16) + (size_t)kRows * kYRow + (size_t)((p.N + 127) / 128) * 128 * 4;
-    static cobevt::PerDeviceOnce attr_once;
-    if (attr_once.first())
-        (void)hipFuncSetAttribute((const void*)gemm_rows3_f32_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kRows * (512 * 4 + 16) + kRows * kYRow + 4096 * 4);
+    cobevt::allow_dynamic_lds<gemm_rows3_f32_kernel>(kRows * (512 * 4 + 16) + kRows * kYRow + 4096 * 4);
     const unsigned blocks = (unsigned)((p.M + kRows - 1) / kRows);
     hipLaunchKernelGGL(gemm_rows3_f32_kernel, dim3(blocks), dim3(kThreads), lds, stream, p);
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }
 
 }  // namespace cobevt

@@ -280,7 +280,7 @@ static int launch_igemm(const IgemmParams& p, hipStream_t stream) {
     } else {
         hipLaunchKernelGGL((igemm_kernel<T, 128, 32, 32, 32, SMALLC>), dim3(blocks(128, 32)), dim3(256), 0, stream, p);
     }
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }
 
 }  // namespace cobevt

@@ -9,22 +9,11 @@
 // four-column runs that a v_permlane32_swap per register turns back into 16-byte stores - waves never synchronise, and the NEXT block's
 // rows are requested before the current block's arithmetic starts.
 #include <stdlib.h>
-#include "common.hpp"
+#include "wave_ops.hpp"
 
 namespace cobevt {
 
 namespace {
-
-__device__ __forceinline__ float xhalf_sum(float v) {          // v + the value of lane ^ 32
-    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-__device__ __forceinline__ void half_swap(uint2& a, uint2& b) {
-    auto r = __builtin_amdgcn_permlane32_swap(a.x, b.x, false, false);
-    a.x = r[0]; b.x = r[1];
-    r = __builtin_amdgcn_permlane32_swap(a.y, b.y, false, false);
-    a.y = r[0]; b.y = r[1];
-}
 
 struct LnLin64Params {
     const bf16_t* in;       // [M][64]
@@ -142,7 +131,7 @@ template <int NNT> int launch_nnt(const LnLin64Params& p, hipStream_t stream) {
     static const int cap = [] { const char* e = getenv("COBEVT_LN64_BLOCKS"); return e && atoi(e) > 0 ? atoi(e) : 1536; }();
     if (blocks > cap) blocks = cap;
     hipLaunchKernelGGL((ln_linear64_kernel<NNT, NW>), dim3((unsigned)blocks), dim3(NW * 64), lds, stream, p, nblk);
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }
 
 }  // namespace

@@ -221,7 +221,7 @@ int launch1d(K kern, long work_items, hipStream_t stream, Args... args) {
     const long blocks = (work_items + 255) / 256;
     if (blocks <= 0 || blocks > 0x7fffffffL) return COBEVT_ERR_SHAPE;
     hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), 0, stream, args...);
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }
 
 bool group_ok(int C) { const int G = C >> 3; return C % 8 == 0 && G >= 1 && G <= 64 && (G & (G - 1)) == 0; }
@@ -242,7 +242,7 @@ extern "C" int cobevt_pairwise_warp(const void* x, const float* pairwise, const 
     if (dtype == 0) hipLaunchKernelGGL(pairwise_warp_kernel<bf16_t>, grid, dim3(256), 0, stream, (const bf16_t*)x, pairwise, record_len, (bf16_t*)nb, roi, B, L, H, W, C, discrete_ratio, downsample_rate);
     else if (dtype == 1) hipLaunchKernelGGL(pairwise_warp_kernel<float>, grid, dim3(256), 0, stream, (const float*)x, pairwise, record_len, (float*)nb, roi, B, L, H, W, C, discrete_ratio, downsample_rate);
     else return COBEVT_ERR_ARG;
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }
 
 extern "C" int cobevt_pairwise_warp_bwd(const void* dnb, const float* pairwise, const int* record_len, float* dx, int dtype, int B, int L,
@@ -254,7 +254,7 @@ extern "C" int cobevt_pairwise_warp_bwd(const void* dnb, const float* pairwise, 
     if (dtype == 0) hipLaunchKernelGGL(pairwise_warp_bwd_kernel<bf16_t>, grid, dim3(256), 0, stream, (const bf16_t*)dnb, pairwise, record_len, dx, B, L, H, W, C, discrete_ratio, downsample_rate);
     else if (dtype == 1) hipLaunchKernelGGL(pairwise_warp_bwd_kernel<float>, grid, dim3(256), 0, stream, (const float*)dnb, pairwise, record_len, dx, B, L, H, W, C, discrete_ratio, downsample_rate);
     else return COBEVT_ERR_ARG;
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }
 
 extern "C" int cobevt_agent_message_reduce(const void* msg, const void* ego, const float* roi, const int* record_len, void* out,

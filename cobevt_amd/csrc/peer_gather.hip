@@ -196,5 +196,5 @@ extern "C" int cobevt_peer_exchange(const void* local, void* const* windows, int
     if (grid < 1) grid = 1;
     hipLaunchKernelGGL(peer_push_kernel, dim3(grid), dim3(256), 0, stream, (const uint4*)local, wins, plan, world, rank,
                        n_local, units, window_bytes, spin_limit);
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }

@@ -31,7 +31,7 @@ struct PillarArgs {
 template <int X> __device__ __forceinline__ float swz_xor(float v) {
     return __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(v), (X << 10) | 0x1f));
 }
-__device__ __forceinline__ float half_wave_sum(float v) {
+__device__ __forceinline__ float half_wave_sum_swz(float v) {
     v += swz_xor<16>(v);
     v += swz_xor<8>(v);
     v += swz_xor<4>(v);
@@ -88,8 +88,8 @@ __global__ __launch_bounds__(256) void pillar_vfe_kernel(const float4* __restric
     const bool inrow = t < a.T;
     // the mean sums all T rows (pillar_vfe.py:110-112), whatever the rows >= n_p hold
     const float fn = (float)n_p;
-    const float mx = half_wave_sum(inrow ? pt.x : 0.f) / fn, my = half_wave_sum(inrow ? pt.y : 0.f) / fn,
-                mz = half_wave_sum(inrow ? pt.z : 0.f) / fn;
+    const float mx = half_wave_sum_swz(inrow ? pt.x : 0.f) / fn, my = half_wave_sum_swz(inrow ? pt.y : 0.f) / fn,
+                mz = half_wave_sum_swz(inrow ? pt.z : 0.f) / fn;
     // voxel centre as the reference forms it: coord * voxel rounded, then + offset rounded (no contraction: at +-140 m an fma moves the
     // centre by an ulp of 1.5e-5 m, which is not small against the +-0.2 m offsets it is subtracted from)
     const float cx = __fadd_rn(__fmul_rn((float)c.w, a.vx), a.xoff);
@@ -195,7 +195,7 @@ static int clear_canvas(void* out, long bytes, const int* record_len, float* mas
     if (blocks < mask_blocks) blocks = mask_blocks;
     if (blocks < 1 || blocks > 0x7fffffffL) return COBEVT_ERR_SHAPE;
     hipLaunchKernelGGL(canvas_clear_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, (uint4*)out, chunks, record_len, mask, B, max_cav);
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }
 
 template <typename T, bool kAbs, bool kDist>
@@ -205,7 +205,7 @@ static int launch_pillar(const float* vf, const int* npts, const int* coords, co
     if (blocks > 0x7fffffffL) return COBEVT_ERR_SHAPE;
     hipLaunchKernelGGL((pillar_vfe_kernel<T, kAbs, kDist>), dim3((unsigned)blocks), dim3(256), 0, stream, (const float4*)vf, npts,
                        (const int4*)coords, w, shift, record_len, (T*)out, a);
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }
 
 }  // namespace cobevt
@@ -269,5 +269,5 @@ extern "C" int cobevt_scatter_rows(const void* rows, const int* voxel_coords, vo
     if (blocks > 0x7fffffffL) return COBEVT_ERR_SHAPE;
     hipLaunchKernelGGL(scatter_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, (const uint4*)rows, (const int4*)voxel_coords,
                        (uint4*)out, P, cpr, N, ny, nx);
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }

@@ -11,10 +11,6 @@ namespace cobevt {
 
 constexpr int kPostMaxClasses = 8;
 
-template <typename T> __device__ __forceinline__ float post_load(const T* p, size_t i);
-template <> __device__ __forceinline__ float post_load<float>(const float* p, size_t i) { return p[i]; }
-template <> __device__ __forceinline__ float post_load<bf16_t>(const bf16_t* p, size_t i) { return bf2f(p[i].bits); }
-
 template <typename T, int C>
 __global__ __launch_bounds__(256) void softmax_argmax_kernel(const T* logits, float* prob, long long* map, int hw) {
     const int n = blockIdx.y;
@@ -23,7 +19,7 @@ __global__ __launch_bounds__(256) void softmax_argmax_kernel(const T* logits, fl
     const size_t base = (size_t)n * C * hw + pix;
     float x[C];
 #pragma unroll
-    for (int c = 0; c < C; ++c) x[c] = post_load<T>(logits, base + (size_t)c * hw);
+    for (int c = 0; c < C; ++c) x[c] = load_elem<T>(logits, base + (size_t)c * hw);
     float m = x[0];
 #pragma unroll
     for (int c = 1; c < C; ++c) m = fmaxf(m, x[c]);
@@ -97,7 +93,7 @@ static int launch_softmax_argmax(const void* logits, float* prob, long long* map
 #undef COBEVT_SA_CASE
         default: return COBEVT_ERR_SHAPE;
     }
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }
 
 }  // namespace cobevt
@@ -122,7 +118,7 @@ extern "C" int cobevt_seg_class_counts(const long long* pred, const long long* g
     const int per_thread = 16;
     const dim3 grid((hw + 256 * per_thread - 1) / (256 * per_thread), N), block(256);
     hipLaunchKernelGGL(seg_counts_kernel, grid, block, 0, stream, pred, gt, counts, hw, K, per_thread);
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -146,7 +142,7 @@ __global__ __launch_bounds__(256) void wce_partial_kernel(const T* logits, const
         if (pix >= hw) break;
         float x[C];
 #pragma unroll
-        for (int c = 0; c < C; ++c) x[c] = post_load<T>(logits, base + (size_t)c * hw + pix);
+        for (int c = 0; c < C; ++c) x[c] = load_elem<T>(logits, base + (size_t)c * hw + pix);
         float m = x[0];
 #pragma unroll
         for (int c = 1; c < C; ++c) m = fmaxf(m, x[c]);
@@ -235,7 +231,7 @@ static int launch_wce(const void* logits, const long long* target, const float* 
 #undef COBEVT_WCE_CASE
         default: return COBEVT_ERR_SHAPE;
     }
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }
 
 }  // namespace cobevt
@@ -254,7 +250,7 @@ extern "C" int cobevt_weighted_cross_entropy(const void* logits, const long long
     else return COBEVT_ERR_ARG;
     if (rc != COBEVT_OK) return rc;
     hipLaunchKernelGGL(wce_final_kernel, dim3(1), dim3(256), 0, stream, scratch, out, nparts, 3);
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }
 
 // Backward of cobevt_weighted_cross_entropy (fp32 logits (N, C, hw)): see wce_backward_kernel.  stats = the forward's out[4].
@@ -269,7 +265,7 @@ extern "C" int cobevt_weighted_cross_entropy_bwd(const float* logits, const long
 #undef COBEVT_WCEB_CASE
         default: return COBEVT_ERR_SHAPE;
     }
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -339,7 +335,7 @@ extern "C" int cobevt_iou_counts(const float* pred, const float* label, const un
     const dim3 grid((hw + 256 * per_thread - 1) / (256 * per_thread), N), block(256);
     hipLaunchKernelGGL(iou_counts_kernel, grid, block, 0, stream, pred, label, visibility, label_mask, thresholds, counts, C, NL, hw,
                        T, min_visibility, per_thread);
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -410,7 +406,7 @@ extern "C" int cobevt_sigmoid_focal_loss(const float* pred, const float* label, 
     hipLaunchKernelGGL(focal_partial_kernel, dim3(gx, N), dim3(256), 0, stream, pred, label, visibility, label_mask, scratch, C, NL, hw,
                        min_visibility, alpha, gamma, soft_label, per_thread);
     hipLaunchKernelGGL(wce_final_kernel, dim3(1), dim3(256), 0, stream, scratch, out, gx * N, 2);
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -497,12 +493,12 @@ static int launch_head(const void* in, const float* wgt, const float* bias, floa
     switch (Cout) {
 #define COBEVT_HEAD_CASE(c) case c: \
         if (Cin * (int)sizeof(T) == 64) { hipLaunchKernelGGL((conv3x3_head_kernel<T, c, 4>), grid, block, lds, stream, (const T*)in, wgt, bias, out, N, H, W, Cin); break; } \
-        (void)hipFuncSetAttribute((const void*)conv3x3_head_kernel<T, c>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024); hipLaunchKernelGGL((conv3x3_head_kernel<T, c>), grid, block, lds, stream, (const T*)in, wgt, bias, out, N, H, W, Cin); break;
+        allow_dynamic_lds<conv3x3_head_kernel<T, c>>(96 * 1024); hipLaunchKernelGGL((conv3x3_head_kernel<T, c>), grid, block, lds, stream, (const T*)in, wgt, bias, out, N, H, W, Cin); break;
         COBEVT_HEAD_CASE(1) COBEVT_HEAD_CASE(2) COBEVT_HEAD_CASE(3) COBEVT_HEAD_CASE(4)
 #undef COBEVT_HEAD_CASE
         default: return COBEVT_ERR_SHAPE;
     }
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }
 
 }  // namespace cobevt

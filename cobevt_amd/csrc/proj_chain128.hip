@@ -10,6 +10,7 @@
 // once (Wn with its contraction index in accumulator-register order, see row_chain64.hip) and its waves walk 32-row blocks on
 // their own: a in natural B-operand order straight from global memory, y / LN(y) in registers, 16-byte stores after a half swap.
 #include "row_chain.hpp"
+#include "wave_ops.hpp"
 
 namespace cobevt {
 
@@ -20,21 +21,6 @@ constexpr int kTab = (kFn + kMaxNnt * 8) * 1024;             // fp32 tables behi
 constexpr int kSc = 0, kSh = 128, kBp = 256, kBn = 384;      // pre_scale[128] pre_shift[128] bp[128] bn[256]
 constexpr int kTabFloats = 640;
 constexpr int kLdsBytes = kTab + kTabFloats * 4;             // 100,864 B: one workgroup per CU
-
-__device__ __forceinline__ float xhalf_sum(float v) {
-    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-__device__ __forceinline__ void half_swap(uint2& a, uint2& b) {      // see row_chain64.hip
-    auto r = __builtin_amdgcn_permlane32_swap(a.x, b.x, false, false);
-    a.x = r[0]; b.x = r[1];
-    r = __builtin_amdgcn_permlane32_swap(a.y, b.y, false, false);
-    a.y = r[0]; b.y = r[1];
-}
-__device__ __forceinline__ uint4 pack8(const float* v) {
-    return make_uint4(pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3]), pack_bf2(v[4], v[5]), pack_bf2(v[6], v[7]));
-}
-__device__ __forceinline__ float rbf(float x) { return bf2f(f2bf(x)); }
 
 // NNT: 32-column tiles of the next projection (Nn = 32 NNT).  NW waves per workgroup.
 template <int NNT, int NW>
@@ -212,15 +198,12 @@ __global__ __launch_bounds__(NW * 64, 1) void proj_chain128_kernel(RowChainParam
 
 template <int NNT> int launch128(const RowChainParams& p, hipStream_t stream) {
     constexpr int NW = 8;
-    static cobevt::PerDeviceOnce attr_once;
-    if (attr_once.first()) {
-        (void)hipFuncSetAttribute((const void*)proj_chain128_kernel<NNT, NW>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-    }
+    cobevt::allow_dynamic_lds<proj_chain128_kernel<NNT, NW>>(kLdsBytes);
     const int nblk = (p.M + 31) / 32;
     int blocks = (nblk + NW - 1) / NW;
     if (blocks > 256) blocks = 256;                        // persistent: one workgroup per CU
     hipLaunchKernelGGL((proj_chain128_kernel<NNT, NW>), dim3((unsigned)blocks), dim3(NW * 64), kLdsBytes, stream, p, nblk);
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }
 
 }  // namespace

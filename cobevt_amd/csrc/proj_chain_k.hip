@@ -16,6 +16,7 @@
 // Weights arrive in MFMA fragment order [N/32 tiles][K/16 k-groups][64 lanes][16 B] straight from L2 (ops.ConvPlan.wfrag_rows);
 // D = W . X^T, so a lane owns one row and four runs of four consecutive columns.
 #include "row_chain.hpp"
+#include "wave_ops.hpp"
 
 namespace cobevt {
 
@@ -50,21 +51,6 @@ struct Lds {
     static constexpr int BIAS = Y + 32 * kRow;          // fp32: [0,128) bp, [128, 128 + 768) bn
     static constexpr int BYTES = BIAS + 4 * (128 + kNnMax);
 };
-
-__device__ __forceinline__ void normalise128(float (&v)[16], float eps) {      // one row held by 8 lanes, 16 channels each
-    float s = 0.f;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) s += v[e];
-    s += __shfl_xor(s, 1, 64); s += __shfl_xor(s, 2, 64); s += __shfl_xor(s, 4, 64);
-    const float mean = s * (1.0f / 128.0f);
-    float q = 0.f;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) { const float d = v[e] - mean; q += d * d; }
-    q += __shfl_xor(q, 1, 64); q += __shfl_xor(q, 2, 64); q += __shfl_xor(q, 4, 64);
-    const float rstd = rsqrtf(q * (1.0f / 128.0f) + eps);
-#pragma unroll
-    for (int e = 0; e < 16; ++e) v[e] = (v[e] - mean) * rstd;
-}
 
 // NCH = K / 128 chunks of the first GEMM (2, 3 or 4)
 template <int NCH>
@@ -257,9 +243,7 @@ __global__ __launch_bounds__(256, 4) void proj_chain_k_kernel(ProjChainKParams p
 
 template <int NCH>
 void launch(const ProjChainKParams& p, int nsides, hipStream_t stream) {
-    static cobevt::PerDeviceOnce attr_once;
-    if (attr_once.first())
-        (void)hipFuncSetAttribute((const void*)proj_chain_k_kernel<NCH>, hipFuncAttributeMaxDynamicSharedMemorySize, Lds::BYTES);
+    cobevt::allow_dynamic_lds<proj_chain_k_kernel<NCH>>(Lds::BYTES);
     hipLaunchKernelGGL((proj_chain_k_kernel<NCH>), dim3((unsigned)((p.M + 31) / 32), (unsigned)nsides), dim3(256), Lds::BYTES, stream, p);
 }
 
@@ -301,5 +285,5 @@ extern "C" int cobevt_proj_chain_kv(const void* a, const void* const* ptrs, cons
         case 3: launch<3>(p, nsides, stream); break;
         default: launch<4>(p, nsides, stream); break;
     }
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }

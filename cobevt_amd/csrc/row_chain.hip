@@ -25,6 +25,7 @@
 //
 // 512 threads = 8 waves arranged 2 (row halves) x 4 (32-column tiles of a 128-column panel).  C <= 128, hidden <= 256.
 #include "row_chain.hpp"
+#include "wave_ops.hpp"
 
 namespace cobevt {
 
@@ -50,12 +51,12 @@ __device__ __forceinline__ void rc_normalise(float (&v)[16], int sub, int C, flo
     float s = 0.f;
 #pragma unroll
     for (int e = 0; e < 16; ++e) s += v[e];
-    s += __shfl_xor(s, 1, 64); s += __shfl_xor(s, 2, 64); s += __shfl_xor(s, 4, 64);
+    s = lane8_sum(s);
     const float mean = s / (float)C;
     float q = 0.f;
 #pragma unroll
     for (int e = 0; e < 16; ++e) { const float d = (sub * 16 + e) < C ? v[e] - mean : 0.f; q += d * d; }
-    q += __shfl_xor(q, 1, 64); q += __shfl_xor(q, 2, 64); q += __shfl_xor(q, 4, 64);
+    q = lane8_sum(q);
     const float rstd = rsqrtf(q / (float)C + eps);
 #pragma unroll
     for (int e = 0; e < 16; ++e) v[e] = (sub * 16 + e) < C ? (v[e] - mean) * rstd : 0.f;
@@ -331,10 +332,7 @@ __global__ __launch_bounds__(ROWS * 8, 4) void row_chain_kernel(RowChainParams p
 
 template <int NPASS, int ROWS, bool FULL, bool MLP = true>
 static void launch_chain(const RowChainParams& p, hipStream_t stream) {
-    static cobevt::PerDeviceOnce attr_once;
-    if (attr_once.first()) {
-        (void)hipFuncSetAttribute((const void*)row_chain_kernel<NPASS, ROWS, FULL, MLP>, hipFuncAttributeMaxDynamicSharedMemorySize, RcLds<ROWS>::BYTES);
-    }
+    cobevt::allow_dynamic_lds<row_chain_kernel<NPASS, ROWS, FULL, MLP>>(RcLds<ROWS>::BYTES);
     const unsigned blocks = (unsigned)((p.M + ROWS - 1) / ROWS);
     hipLaunchKernelGGL((row_chain_kernel<NPASS, ROWS, FULL, MLP>), dim3(blocks), dim3(ROWS * 8), RcLds<ROWS>::BYTES, stream, p);
 }
@@ -389,7 +387,7 @@ extern "C" int cobevt_attn_mlp_chain(const void* a, const void* skip, void* out,
         if (two) { if (full) launch_chain<2, 32, true>(p, stream); else launch_chain<2, 32, false>(p, stream); }
         else { if (full) launch_chain<1, 32, true>(p, stream); else launch_chain<1, 32, false>(p, stream); }
     }
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }
 
 // Projection chain, see include/cobevt_hip.h: y = ReLU?(a * pre_scale + pre_shift) . Wp^T + bp + skip ; next = act(LN?(y) . Wn'^T + bn')
@@ -419,5 +417,5 @@ extern "C" int cobevt_proj_chain(const void* a, const float* pre_scale, const fl
         if (rc >= 0) return rc;
     }
     launch_chain<1, 32, true, false>(p, stream);
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }

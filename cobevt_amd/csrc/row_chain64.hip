@@ -21,6 +21,7 @@
 //     157 us per launch, a 64-row tile costing ~20k cycles of mostly exposed round trips).
 #include <stdlib.h>
 #include "row_chain.hpp"
+#include "wave_ops.hpp"
 
 namespace cobevt {
 
@@ -31,20 +32,6 @@ namespace {
 constexpr int kFp = 0, kF1 = kFp + 8, kF2 = kF1 + 16, kFn = kF2 + 16, kFrags = kFn + 24;      // in 1-KB fragments
 constexpr int kBp = 0, kB1 = 64, kB2 = 192, kPg = 256, kPb = 320, kBn = 384, kBiasFloats = 576;
 constexpr int kLdsBytes = kFrags * 1024 + kBiasFloats * 4;                                    // 67,840 B: two workgroups per CU
-
-__device__ __forceinline__ float xhalf_sum(float v) {          // v + the value of lane ^ 32
-    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-// {lo, hi} (16 bytes at natural channel order, channels 16 m + 8 h .. + 7) <-> the two 4-channel runs this lane holds in
-// accumulator order (run 2 m: channels 16 m + 4 h .. + 3; run 2 m + 1: channels 16 m + 8 + 4 h .. + 3).  The same exchange in
-// both directions: it swaps the upper half-wave's `a` with the lower half-wave's `b`.
-__device__ __forceinline__ void half_swap(uint2& a, uint2& b) {
-    auto r = __builtin_amdgcn_permlane32_swap(a.x, b.x, false, false);
-    a.x = r[0]; b.x = r[1];
-    r = __builtin_amdgcn_permlane32_swap(a.y, b.y, false, false);
-    a.y = r[0]; b.y = r[1];
-}
 
 // v[t][r]: the lane's 32 values of its row (2 column tiles x 16 accumulator registers) -> normalised over the row's 64 channels
 __device__ __forceinline__ void row_normalise(float (&v)[2][16], float eps) {
@@ -65,12 +52,6 @@ __device__ __forceinline__ void row_normalise(float (&v)[2][16], float eps) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) v[t][r] = (v[t][r] - mean) * rstd;
 }
-
-// 8 accumulator registers [8 u, 8 u + 8) of a tile -> one bf16 B operand (k-group 2 t + u of the accumulator k order)
-__device__ __forceinline__ uint4 pack8(const float* v) {
-    return make_uint4(pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3]), pack_bf2(v[4], v[5]), pack_bf2(v[6], v[7]));
-}
-__device__ __forceinline__ float rbf(float x) { return bf2f(f2bf(x)); }          // the value a bf16 store would keep
 
 // NNT2: 32-column tiles of the next projection (Nn = 32 NNT2 <= 192; 0 = none).  NW waves per workgroup.
 // PF (round 6): the NEXT block's a / skip rows are requested before the current block's chain starts (32 more registers: four waves per
@@ -311,15 +292,12 @@ __global__ __launch_bounds__(NW * 64, 2) void row_chain64_kernel(RowChainParams 
 }
 
 template <int NNT2, int NW, bool PF> int launch64v(const RowChainParams& p, hipStream_t stream) {
-    static cobevt::PerDeviceOnce attr_once;
-    if (attr_once.first()) {
-        (void)hipFuncSetAttribute((const void*)row_chain64_kernel<NNT2, NW, PF>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-    }
+    cobevt::allow_dynamic_lds<row_chain64_kernel<NNT2, NW, PF>>(kLdsBytes);
     const int nblk = (p.M + 31) / 32;
     int blocks = (nblk + NW - 1) / NW;
     if (blocks > 512) blocks = 512;                        // persistent: two workgroups per CU walk the 32-row blocks
     hipLaunchKernelGGL((row_chain64_kernel<NNT2, NW, PF>), dim3((unsigned)blocks), dim3(NW * 64), kLdsBytes, stream, p, nblk);
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }
 template <int NNT2> int launch64(const RowChainParams& p, hipStream_t stream) {
     // Round 6, same-job A/B on the LiDAR FuseBEVT workload (profiles/r06_rc64_prefetch_ab.txt): the next block's rows prefetched under the

@@ -19,6 +19,7 @@
 // split-bf16 / fp16 libraries (common.hpp): the main loops are ds_read_b128 + MFMA, the weight fragment's split is shared by nothing
 // (one 32-row tile per wave) but costs 12 VALU instructions per MFMA pair against 24.  73 KB per workgroup, two per CU.
 #include "row_chain.hpp"
+#include "wave_ops.hpp"
 
 namespace cobevt {
 
@@ -45,22 +46,6 @@ struct RowChainF32Params {
     int M, Nn, next_ln, next_act, skip_rows;
     float eps1, eps_post, eps_next;
 };
-
-// normalise one 128-channel row held by 8 lanes (16 channels each)
-__device__ __forceinline__ void normalise128(float (&v)[16], float eps) {
-    float s = 0.f;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) s += v[e];
-    s += __shfl_xor(s, 1, 64); s += __shfl_xor(s, 2, 64); s += __shfl_xor(s, 4, 64);
-    const float mean = s * (1.0f / 128.0f);
-    float q = 0.f;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) { const float d = v[e] - mean; q += d * d; }
-    q += __shfl_xor(q, 1, 64); q += __shfl_xor(q, 2, 64); q += __shfl_xor(q, 4, 64);
-    const float rstd = rsqrtf(q * (1.0f / 128.0f) + eps);
-#pragma unroll
-    for (int e = 0; e < 16; ++e) v[e] = (v[e] - mean) * rstd;
-}
 
 __global__ __launch_bounds__(kFThreads, 2) void row_chain_f32_kernel(RowChainF32Params p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -288,12 +273,10 @@ int launch_row_chain_f32(const void* a, const void* skip, void* out, const void*
     p.post_g = post_g; p.post_b = post_b; p.wn = (const uint4*)wnext; p.bn = bnext; p.out_next = (float*)out_next;
     p.M = M; p.Nn = Nn; p.next_ln = next_ln; p.next_act = next_act; p.skip_rows = skip_rows;
     p.eps1 = eps1; p.eps_post = eps_post; p.eps_next = eps_next;
-    static cobevt::PerDeviceOnce attr_once;
-    if (attr_once.first())
-        (void)hipFuncSetAttribute((const void*)row_chain_f32_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, F32Lds::BYTES);
+    cobevt::allow_dynamic_lds<row_chain_f32_kernel>(F32Lds::BYTES);
     const unsigned blocks = (unsigned)((M + kFRows - 1) / kFRows);
     hipLaunchKernelGGL(row_chain_f32_kernel, dim3(blocks), dim3(kFThreads), F32Lds::BYTES, stream, p);
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }
 
 }  // namespace cobevt

@@ -585,16 +585,13 @@ extern "C" int cobevt_stem_conv7x7s2(const float* in, const void* wgt, const flo
     if (nt > 0x7fffffffL) return COBEVT_ERR_SHAPE;
     p.ntiles = (int)nt;
     const size_t lds = dtype == 0 ? StemCfg<bf16_t>::LDS : StemCfg<float>::LDS;
-    static cobevt::PerDeviceOnce attr_once;
-    if (attr_once.first()) {
-        (void)hipFuncSetAttribute((const void*)stem7x7_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)StemCfg<bf16_t>::LDS);
-        (void)hipFuncSetAttribute((const void*)stem7x7_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)StemCfg<float>::LDS);
-    }
+    cobevt::allow_dynamic_lds<stem7x7_kernel<bf16_t>>((int)StemCfg<bf16_t>::LDS);
+    cobevt::allow_dynamic_lds<stem7x7_kernel<float>>((int)StemCfg<float>::LDS);
     const int per_cu = dtype == 0 ? 2 : 1;
     const unsigned blocks = (unsigned)(nt < 256L * per_cu ? nt : 256L * per_cu);
     if (dtype == 0) hipLaunchKernelGGL(stem7x7_kernel<bf16_t>, dim3(blocks), dim3(256), lds, stream, p);
     else hipLaunchKernelGGL(stem7x7_kernel<float>, dim3(blocks), dim3(256), lds, stream, p);
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }
 
 // C-ABI entry point, see include/cobevt_hip.h
@@ -615,11 +612,8 @@ extern "C" int cobevt_stem_conv7x7s2_pool(const float* in, const void* wgt, cons
     if (nt > 0x7fffffffL) return COBEVT_ERR_SHAPE;
     p.ntiles = (int)nt;
     const size_t lds = dtype == 0 ? StemPoolCfg<bf16_t>::LDS : StemPoolCfg<float>::LDS;
-    static cobevt::PerDeviceOnce attr_once;
-    if (attr_once.first()) {
-        (void)hipFuncSetAttribute((const void*)stem_pool_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)StemPoolCfg<bf16_t>::LDS);
-        (void)hipFuncSetAttribute((const void*)stem_pool_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)StemPoolCfg<float>::LDS);
-    }
+    cobevt::allow_dynamic_lds<stem_pool_kernel<bf16_t>>((int)StemPoolCfg<bf16_t>::LDS);
+    cobevt::allow_dynamic_lds<stem_pool_kernel<float>>((int)StemPoolCfg<float>::LDS);
     // persistent grid: as many workgroups per CU as LDS and the 32-wave limit admit (bf16 2, fp32 1)
     const int nthreads = dtype == 0 ? StemPoolCfg<bf16_t>::NT : StemPoolCfg<float>::NT;
     int per_cu = (int)(163840 / lds);
@@ -628,7 +622,7 @@ extern "C" int cobevt_stem_conv7x7s2_pool(const float* in, const void* wgt, cons
     const unsigned blocks = (unsigned)(nt < 256L * per_cu ? nt : 256L * per_cu);
     if (dtype == 0) hipLaunchKernelGGL(stem_pool_kernel<bf16_t>, dim3(blocks), dim3(StemPoolCfg<bf16_t>::NT), lds, stream, p);
     else hipLaunchKernelGGL(stem_pool_kernel<float>, dim3(blocks), dim3(StemPoolCfg<float>::NT), lds, stream, p);
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }
 
 // C-ABI entry point, see include/cobevt_hip.h: the same launch on uint8 camera frames (N, H, W, 3) + the [3][256] normalisation table
@@ -649,11 +643,8 @@ extern "C" int cobevt_stem_conv7x7s2_pool_u8(const unsigned char* in, const floa
     if (nt > 0x7fffffffL) return COBEVT_ERR_SHAPE;
     p.ntiles = (int)nt;
     const size_t lds = dtype == 0 ? StemPoolCfg<bf16_t>::LDS_U8 : StemPoolCfg<float>::LDS_U8;
-    static cobevt::PerDeviceOnce attr_once;
-    if (attr_once.first()) {
-        (void)hipFuncSetAttribute((const void*)stem_pool_kernel<bf16_t, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)StemPoolCfg<bf16_t>::LDS_U8);
-        (void)hipFuncSetAttribute((const void*)stem_pool_kernel<float, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)StemPoolCfg<float>::LDS_U8);
-    }
+    cobevt::allow_dynamic_lds<stem_pool_kernel<bf16_t, true>>((int)StemPoolCfg<bf16_t>::LDS_U8);
+    cobevt::allow_dynamic_lds<stem_pool_kernel<float, true>>((int)StemPoolCfg<float>::LDS_U8);
     const int nthreads = dtype == 0 ? StemPoolCfg<bf16_t>::NT : StemPoolCfg<float>::NT;
     int per_cu = (int)(163840 / lds);
     if (per_cu > 2048 / nthreads) per_cu = 2048 / nthreads;
@@ -661,7 +652,7 @@ extern "C" int cobevt_stem_conv7x7s2_pool_u8(const unsigned char* in, const floa
     const unsigned blocks = (unsigned)(nt < 256L * per_cu ? nt : 256L * per_cu);
     if (dtype == 0) hipLaunchKernelGGL((stem_pool_kernel<bf16_t, true>), dim3(blocks), dim3(StemPoolCfg<bf16_t>::NT), lds, stream, p);
     else hipLaunchKernelGGL((stem_pool_kernel<float, true>), dim3(blocks), dim3(StemPoolCfg<float>::NT), lds, stream, p);
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }
 
 #ifdef COBEVT_STEM_TRACE

@@ -19,6 +19,7 @@
 // LDS: the attention region (V of 4 heads 80 KB, row-major, read through the transpose read + bias columns 40 KB + key tables) is dead when the chain starts and is reused
 // for its y / hidden / staging tiles; ~130 KB per workgroup, one workgroup per CU (the grid has 160).
 #include "attn_common.hpp"
+#include "wave_ops.hpp"
 
 namespace cobevt {
 
@@ -63,33 +64,6 @@ __device__ unsigned long long g_stage_trace[16 * 4096];
 #else
 #define STAGE_MARK(i) do { } while (0)
 #endif
-
-__device__ __forceinline__ int perm16(int k) { return (k & ~12) | ((k & 4) << 1) | ((k & 8) >> 1); }
-
-__device__ __forceinline__ float xor32_max(float v) {
-    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-}
-__device__ __forceinline__ float xor32_sum(float v) {
-    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-
-// normalise one row held by 8 lanes (16 channels each), C = 128
-__device__ __forceinline__ void normalise128(float (&v)[16], float eps) {
-    float s = 0.f;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) s += v[e];
-    s += __shfl_xor(s, 1, 64); s += __shfl_xor(s, 2, 64); s += __shfl_xor(s, 4, 64);
-    const float mean = s * (1.0f / 128.0f);
-    float q = 0.f;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) { const float d = v[e] - mean; q += d * d; }
-    q += __shfl_xor(q, 1, 64); q += __shfl_xor(q, 2, 64); q += __shfl_xor(q, 4, 64);
-    const float rstd = rsqrtf(q * (1.0f / 128.0f) + eps);
-#pragma unroll
-    for (int e = 0; e < 16; ++e) v[e] = (v[e] - mean) * rstd;
-}
 
 // LDS layout (bytes).  Fixed part: the attention output / LN tile and the token -> row table of the workgroup's 32 queries.
 // Region R is used twice: by the attention phase (V^T, bias columns, key tables) and then by the chain (y, hidden, biases).
@@ -366,7 +340,7 @@ __global__ __launch_bounds__(kThreads, 1) void swap_stage_kernel(SwapStageParams
             __builtin_amdgcn_sched_barrier(0);
         }
         STAGE_MARK(12);
-        const float m_all = xor32_max(mloc);
+        const float m_all = xhalf_max(mloc);
         const float m_safe = (m_all == -INFINITY) ? 0.f : m_all;
         float l_run = 0.f;
         f32x16 ot;
@@ -392,7 +366,7 @@ __global__ __launch_bounds__(kThreads, 1) void swap_stage_kernel(SwapStageParams
                 mfma_kgroup<bf16_t>(va, pb, ot);             // O^T += V^T . P^T : rows = dh, column = query
             }
         }
-        const float inv = 1.0f / xor32_sum(l_run);           // an all-masked row yields NaN like the reference softmax
+        const float inv = 1.0f / xhalf_sum(l_run);           // an all-masked row yields NaN like the reference softmax
 #pragma unroll
         for (int g4 = 0; g4 < 4; ++g4) {                     // registers 4g4.. <-> dh 8 g4 + 4h + 0..3 of head `head`
             uint2 w;
@@ -634,9 +608,7 @@ extern "C" int cobevt_swap_fusion_stage(const void* qkv, const void* x, void* ou
     const dim3 grid((unsigned)(p.map.X * p.map.Y * p.nsplit), (unsigned)p.B);
 #define COBEVT_STAGE_LAUNCH(NP_, NT_)                                                                                               \
     do {                                                                                                                             \
-        static cobevt::PerDeviceOnce once;                                                                                           \
-        if (once.first())                                                                                                            \
-            (void)hipFuncSetAttribute((const void*)swap_stage_kernel<NP_, NT_>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
+        cobevt::allow_dynamic_lds<swap_stage_kernel<NP_, NT_>>(160 * 1024);                                                          \
         hipLaunchKernelGGL((swap_stage_kernel<NP_, NT_>), grid, dim3(kThreads), (size_t)L.total, stream, p);                        \
     } while (0)
 #define COBEVT_STAGE_NT(NP_)                                                                                                         \
@@ -650,5 +622,5 @@ extern "C" int cobevt_swap_fusion_stage(const void* qkv, const void* x, void* ou
     if (p.Hd > 128) { COBEVT_STAGE_NT(2) } else { COBEVT_STAGE_NT(1) }
 #undef COBEVT_STAGE_NT
 #undef COBEVT_STAGE_LAUNCH
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }

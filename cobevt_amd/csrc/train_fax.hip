@@ -11,7 +11,7 @@
 // accumulators once (LDS reduction over its 8 half-waves, then one atomic per word).
 // round_bf16 = 1 (inside a bf16 autocast region): the 1x1 convolution's operands and result and the difference are rounded to bf16 as
 // torch's autocast does (conv in bf16, the subtraction of two bf16 tensors in bf16; norm / division / addition in fp32).
-#include "common.hpp"
+#include "wave_ops.hpp"
 
 namespace cobevt {
 namespace {
@@ -34,13 +34,6 @@ struct BevQueryTrainParams {
     long grid_stride;    // floats between the batch elements' grids (0: one grid for all)
     int B, n, HW, W, round_bf16;
 };
-
-__device__ __forceinline__ float rbf(float v) { return bf2f(f2bf(v)); }
-__device__ __forceinline__ float half_sum(float v) {
-#pragma unroll
-    for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // KD = input channels of the 1x1 embedding convolution: 2 (the BEV grid) or 4 (homogeneous ray directions, fax_modules.py:330-343)
 template <bool BWD, int KD>
@@ -90,7 +83,7 @@ __global__ __launch_bounds__(256) void bev_query_train_kernel(BevQueryTrainParam
             if (cam >= p.n) break;
             float4 v = make_float4(e.x - cc[cam].x, e.y - cc[cam].y, e.z - cc[cam].z, e.w - cc[cam].w);
             if (p.round_bf16) v = make_float4(rbf(v.x), rbf(v.y), rbf(v.z), rbf(v.w));
-            const float r = sqrtf(half_sum(v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w));
+            const float r = sqrtf(half_wave_sum(v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w));
             const float s = r + 1e-7f;
             const size_t row = (((size_t)b * p.n + cam) * p.HW + pix) * kD + 4 * g;
             if constexpr (!BWD) {
@@ -98,7 +91,7 @@ __global__ __launch_bounds__(256) void bev_query_train_kernel(BevQueryTrainParam
                 *(float4*)(p.out + row) = make_float4(v.x * inv + xv.x, v.y * inv + xv.y, v.z * inv + xv.z, v.w * inv + xv.w);
             } else {
                 const float4 dq = *(const float4*)(p.dq + row);
-                const float vd = half_sum(v.x * dq.x + v.y * dq.y + v.z * dq.z + v.w * dq.w);
+                const float vd = half_wave_sum(v.x * dq.x + v.y * dq.y + v.z * dq.z + v.w * dq.w);
                 const float a = 1.f / s, kk = r > 0.f ? vd / (r * s * s) : 0.f;
                 const float4 dv = make_float4(dq.x * a - v.x * kk, dq.y * a - v.y * kk, dq.z * a - v.z * kk, dq.w * a - v.w * kk);
 #pragma unroll
@@ -159,7 +152,7 @@ extern "C" int cobevt_fax_bev_query_train(const float* grid, const float* w, con
     const dim3 grid_dim(pixel_blocks(p.HW, p.B), p.B);
     if (dims[6] == 2) hipLaunchKernelGGL((bev_query_train_kernel<false, 2>), grid_dim, dim3(256), 0, stream, p);
     else hipLaunchKernelGGL((bev_query_train_kernel<false, 4>), grid_dim, dim3(256), 0, stream, p);
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }
 
 extern "C" int cobevt_fax_bev_query_train_bwd(const float* grid, const float* w, const float* bias, const float* c, const float* dq, float* dx,
@@ -177,5 +170,5 @@ extern "C" int cobevt_fax_bev_query_train_bwd(const float* grid, const float* w,
     const dim3 grid_dim(pixel_blocks(p.HW, p.B, 512), p.B);
     if (dims[6] == 2) hipLaunchKernelGGL((bev_query_train_kernel<true, 2>), grid_dim, dim3(256), 0, stream, p);
     else hipLaunchKernelGGL((bev_query_train_kernel<true, 4>), grid_dim, dim3(256), 0, stream, p);
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }

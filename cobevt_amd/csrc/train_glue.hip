@@ -664,7 +664,7 @@ extern "C" int cobevt_channel_sums(const void* x, const float* shift, double* su
         const dim3 grid((unsigned)((C + kThreads - 1) / kThreads), (unsigned)((rows + rpb - 1) / rpb));
         if (dtype == 0) hipLaunchKernelGGL(channel_sums_generic_kernel<bf16_t>, grid, dim3(kThreads), 0, stream, (const bf16_t*)x, sum, sumsq, rows, C, rpb);
         else hipLaunchKernelGGL(channel_sums_generic_kernel<float>, grid, dim3(kThreads), 0, stream, (const float*)x, sum, sumsq, rows, C, rpb);
-        return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+        return cobevt::launch_status();
     }
     if (!scratch || scratch_blocks < 1) return COBEVT_ERR_ARG;
     if (sumsq && sumsq != sum + C) return COBEVT_ERR_ARG;                  // the pair is reduced as one 2 C vector
@@ -684,13 +684,13 @@ extern "C" int cobevt_channel_sums(const void* x, const float* shift, double* su
     } else {
         hipLaunchKernelGGL(reduce_partials_strided_kernel, dim3((n + 3) / 4), dim3(256), 0, stream, scratch, blocks, n, 2 * C, sum, out_f);
     }
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }
 
 extern "C" int cobevt_f64_to_f32(const double* in, float* out, int n, hipStream_t stream) {
     if (!in || !out || n < 1) return COBEVT_ERR_ARG;
     hipLaunchKernelGGL(f64_to_f32_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, in, out, n);
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }
 
 extern "C" int cobevt_bn_finalize(const double* sum, const double* sumsq, const float* gamma, const float* beta, float* running_mean,
@@ -702,7 +702,7 @@ extern "C" int cobevt_bn_finalize(const double* sum, const double* sumsq, const 
     if (shifted && !running_mean) return COBEVT_ERR_ARG;
     hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + 255) / 256), dim3(256), 0, stream, sum, sumsq, gamma, beta, running_mean, running_var,
                        scale, shift, mean, rstd, C, (double)rows, eps, momentum, training, shifted, batches_tracked);
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }
 
 // cobevt_channel_sums (with the square sums, shifted by running_mean when it is given) + cobevt_bn_finalize (training = 1) in two launches
@@ -719,7 +719,7 @@ extern "C" int cobevt_bn_batch_stats(const void* x, const float* gamma, const fl
     else hipLaunchKernelGGL((channel_sums_kernel<float, true>), dim3(blocks), dim3(kThreads), 0, stream, (const float*)x, running_mean, scratch, rows, C, rpb);
     hipLaunchKernelGGL(bn_reduce_finalize_kernel, dim3((C + 3) / 4), dim3(256), 0, stream, scratch, blocks, gamma, beta, running_mean, running_var, scale,
                        shift, mean, rstd, C, (double)rows, eps, momentum, running_mean != nullptr, batches_tracked);
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }
 
 extern "C" int cobevt_bn_apply(const void* x, const void* residual, const float* scale, const float* shift, void* y, int dtype,
@@ -732,13 +732,13 @@ extern "C" int cobevt_bn_apply(const void* x, const void* residual, const float*
         if (dtype == 0) hipLaunchKernelGGL(bn_apply_walk_kernel<bf16_t>, wgrid, dim3(kThreads), 0, stream, (const bf16_t*)x, (const bf16_t*)residual, scale, shift, (bf16_t*)y, items, C, act);
         else if (dtype == 1) hipLaunchKernelGGL(bn_apply_walk_kernel<float>, wgrid, dim3(kThreads), 0, stream, (const float*)x, (const float*)residual, scale, shift, (float*)y, items, C, act);
         else return COBEVT_ERR_ARG;
-        return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+        return cobevt::launch_status();
     }
     const dim3 grid((unsigned)((items + kThreads - 1) / kThreads));
     if (dtype == 0) hipLaunchKernelGGL(bn_apply_kernel<bf16_t>, grid, dim3(kThreads), 0, stream, (const bf16_t*)x, (const bf16_t*)residual, scale, shift, (bf16_t*)y, items, C, act);
     else if (dtype == 1) hipLaunchKernelGGL(bn_apply_kernel<float>, grid, dim3(kThreads), 0, stream, (const float*)x, (const float*)residual, scale, shift, (float*)y, items, C, act);
     else return COBEVT_ERR_ARG;
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }
 
 // dgamma / dbeta: fp64 [2][C] back to back (dgamma, then dbeta), written; grads_f (nullable): the same 2 C values as fp32; scratch: fp64
@@ -767,7 +767,7 @@ extern "C" int cobevt_bn_backward(const void* x, const void* y, const void* dy, 
             hipLaunchKernelGGL(reduce_partials_strided_kernel, dim3((2 * C + 3) / 4), dim3(256), 0, stream, scratch, blocks, 2 * C, 2 * C, dgamma_dbeta, grads_f);
             hipLaunchKernelGGL(bn_bwd_apply_walk_kernel<float>, wgrid, dim3(kThreads), 0, stream, (const float*)x, (const float*)y, (const float*)dy, mean, rstd, gamma, dgamma, dbeta, (float*)dx, (float*)dres, items, C, inv_rows, act, training);
         }
-        return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+        return cobevt::launch_status();
     }
     if (dtype == 0) {
         hipLaunchKernelGGL(bn_bwd_reduce_kernel<bf16_t>, dim3(blocks), dim3(kThreads), 0, stream, (const bf16_t*)x, (const bf16_t*)y, (const bf16_t*)dy, mean, rstd, scratch, rows, C, act, rpb);
@@ -778,7 +778,7 @@ extern "C" int cobevt_bn_backward(const void* x, const void* y, const void* dy, 
         hipLaunchKernelGGL(reduce_partials_strided_kernel, dim3((2 * C + 3) / 4), dim3(256), 0, stream, scratch, blocks, 2 * C, 2 * C, dgamma_dbeta, grads_f);
         hipLaunchKernelGGL(bn_bwd_apply_kernel<float>, grid, dim3(kThreads), 0, stream, (const float*)x, (const float*)y, (const float*)dy, mean, rstd, gamma, dgamma, dbeta, (float*)dx, (float*)dres, items, C, inv_rows, act, training);
     } else return COBEVT_ERR_ARG;
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }
 
 // dx fp32 (N, H, W, C), every element written
@@ -791,7 +791,7 @@ extern "C" int cobevt_maxpool3x3s2_bwd(const void* x, const void* dy, float* dx,
     if (dtype == 0) hipLaunchKernelGGL(maxpool_bwd_kernel<bf16_t>, grid, dim3(kThreads), 0, stream, (const bf16_t*)x, (const bf16_t*)dy, dx, N, H, W, C, Ho, Wo);
     else if (dtype == 1) hipLaunchKernelGGL(maxpool_bwd_kernel<float>, grid, dim3(kThreads), 0, stream, (const float*)x, (const float*)dy, dx, N, H, W, C, Ho, Wo);
     else return COBEVT_ERR_ARG;
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }
 
 // dx (N, H, W, C) in the map's type, every element written
@@ -804,7 +804,7 @@ extern "C" int cobevt_maxpool3x3s2_bwd_t(const void* x, const void* dy, void* dx
     if (dtype == 0) hipLaunchKernelGGL(maxpool_bwd_block_kernel<bf16_t>, grid, dim3(kThreads), 0, stream, (const bf16_t*)x, (const bf16_t*)dy, (bf16_t*)dx, N, H, W, C, Ho, Wo);
     else if (dtype == 1) hipLaunchKernelGGL(maxpool_bwd_block_kernel<float>, grid, dim3(kThreads), 0, stream, (const float*)x, (const float*)dy, (float*)dx, N, H, W, C, Ho, Wo);
     else return COBEVT_ERR_ARG;
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }
 
 extern "C" int cobevt_group_mean(const void* in, void* out, int dtype, long B, int n, long inner, int backward, hipStream_t stream) {
@@ -815,7 +815,7 @@ extern "C" int cobevt_group_mean(const void* in, void* out, int dtype, long B, i
     if (dtype == 0) hipLaunchKernelGGL(group_mean_kernel<bf16_t>, grid, dim3(kThreads), 0, stream, (const bf16_t*)in, (bf16_t*)out, pieces, inner / 8, n, backward);
     else if (dtype == 1) hipLaunchKernelGGL(group_mean_kernel<float>, grid, dim3(kThreads), 0, stream, (const float*)in, (float*)out, pieces, inner / 8, n, backward);
     else return COBEVT_ERR_ARG;
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }
 
 // inverse = 0: in (N, 2Ho, 2Wo, C) -> out (N, Ho, Wo, 4C) [nn.PixelUnshuffle(2)] ; inverse = 1: in (N, Ho, Wo, 4C) -> out (N, 2Ho, 2Wo, C)
@@ -827,7 +827,7 @@ extern "C" int cobevt_pixel_unshuffle2_nhwc(const void* in, void* out, int dtype
     if (dtype == 0) hipLaunchKernelGGL(pixel_unshuffle_kernel<uint16_t>, grid, dim3(kThreads), 0, stream, (const uint16_t*)in, (uint16_t*)out, total, Ho, Wo, C, inverse);
     else if (dtype == 1) hipLaunchKernelGGL(pixel_unshuffle_kernel<float>, grid, dim3(kThreads), 0, stream, (const float*)in, (float*)out, total, Ho, Wo, C, inverse);
     else return COBEVT_ERR_ARG;
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }
 
 // backward = 0: in (N, H, W, C) -> out (N, 2H, 2W, C) nearest ; backward = 1: in = dy (N, 2H, 2W, C) -> out = dx (N, H, W, C)
@@ -839,7 +839,7 @@ extern "C" int cobevt_upsample_nearest2_nhwc(const void* in, void* out, int dtyp
     if (dtype == 0) hipLaunchKernelGGL(upsample2_kernel<bf16_t>, grid, dim3(kThreads), 0, stream, (const bf16_t*)in, (bf16_t*)out, items, H, W, C, backward);
     else if (dtype == 1) hipLaunchKernelGGL(upsample2_kernel<float>, grid, dim3(kThreads), 0, stream, (const float*)in, (float*)out, items, H, W, C, backward);
     else return COBEVT_ERR_ARG;
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }
 
 // dout (B, L, H, W, C) fp32 -> dx (agents, H, W, C) fp32 (zeroed by the caller); record_len as for cobevt_sttf_warp (nullable: agent = b * L + l)
@@ -850,5 +850,5 @@ extern "C" int cobevt_sttf_warp_bwd(const float* dout, const float* tmat, const 
     const long items = (long)H * W * (C >> 3);
     const dim3 grid((unsigned)((items + kThreads - 1) / kThreads), (unsigned)(B * L));
     hipLaunchKernelGGL(sttf_warp_bwd_kernel, grid, dim3(kThreads), 0, stream, dout, tmat, record_len, dx, B, L, H, W, C, discrete_ratio, downsample_rate);
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }

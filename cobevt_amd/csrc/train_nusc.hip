@@ -166,7 +166,7 @@ extern "C" int cobevt_swish(const void* x, const void* dy, void* out, int dtype,
     if (dtype == 0) hipLaunchKernelGGL(swish_kernel<bf16_t>, grid, dim3(kThreads), 0, stream, (const bf16_t*)x, (const bf16_t*)dy, (bf16_t*)out, groups);
     else if (dtype == 1) hipLaunchKernelGGL(swish_kernel<float>, grid, dim3(kThreads), 0, stream, (const float*)x, (const float*)dy, (float*)out, groups);
     else return COBEVT_ERR_ARG;
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }
 
 extern "C" int cobevt_depthwise_wgrad(const void* x, const void* dy, float* dw, const int* dims, hipStream_t stream) {
@@ -188,7 +188,7 @@ extern "C" int cobevt_depthwise_wgrad(const void* x, const void* dy, float* dw, 
     else if (dtype == 1) { if (k == 3) COBEVT_DWG(float, 3); else COBEVT_DWG(float, 5); }
     else return COBEVT_ERR_ARG;
 #undef COBEVT_DWG
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }
 
 extern "C" int cobevt_resize_bilinear_bwd(const void* dy, float* dx, int dtype, int N, int H, int W, int C, int Ho, int Wo, hipStream_t stream) {
@@ -200,7 +200,7 @@ extern "C" int cobevt_resize_bilinear_bwd(const void* dy, float* dx, int dtype, 
     if (dtype == 0) hipLaunchKernelGGL(resize_bilinear_bwd_kernel<bf16_t>, grid, dim3(kThreads), 0, stream, (const bf16_t*)dy, dx, items, H, W, C, Ho, Wo);
     else if (dtype == 1) hipLaunchKernelGGL(resize_bilinear_bwd_kernel<float>, grid, dim3(kThreads), 0, stream, (const float*)dy, dx, items, H, W, C, Ho, Wo);
     else return COBEVT_ERR_ARG;
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }
 
 extern "C" int cobevt_sigmoid_focal_loss_bwd(const float* pred, const float* label, const unsigned char* visibility, const unsigned int* label_mask,
@@ -213,5 +213,5 @@ extern "C" int cobevt_sigmoid_focal_loss_bwd(const float* pred, const float* lab
     const dim3 grid((hw + kThreads - 1) / kThreads, N);
     hipLaunchKernelGGL(focal_bwd_kernel, grid, dim3(kThreads), 0, stream, pred, label, visibility, label_mask, stats, gscale, dpred, C, NL, hw,
                        min_visibility, alpha, gamma, soft_label);
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }

@@ -211,7 +211,7 @@ extern "C" int cobevt_conv_weight_rows(const float* w, void* rows_fwd, void* row
     if (dtype == 0) hipLaunchKernelGGL(conv_weight_rows_kernel<bf16_t>, grid, dim3(kThreads), 0, stream, w, (bf16_t*)rows_fwd, (bf16_t*)rows_dgrad, Cout, Cin, kh, kw, kpf, kpd);
     else if (dtype == 1) hipLaunchKernelGGL(conv_weight_rows_kernel<float>, grid, dim3(kThreads), 0, stream, w, (float*)rows_fwd, (float*)rows_dgrad, Cout, Cin, kh, kw, kpf, kpd);
     else return COBEVT_ERR_ARG;
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }
 
 static bool conv3_job(Conv3OperandJob& j, void* frag, void* rows3, int Cout, int Cin, int dgrad) {
@@ -236,7 +236,7 @@ extern "C" int cobevt_conv3_weight_operands(const float* w, void* frag, void* ro
     const long total = a.nfrag + a.nrows;
     if (total > 0x7fffffffL * (long)kThreads) return COBEVT_ERR_SHAPE;
     hipLaunchKernelGGL(conv3_weight_operands_kernel, dim3((unsigned)((total + kThreads - 1) / kThreads)), dim3(kThreads), 0, stream, w, a, b, Cin);
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }
 
 // both directions in one launch: outs = [fwd frag, fwd rows3, dgrad frag, dgrad rows3], each nullable
@@ -250,7 +250,7 @@ extern "C" int cobevt_conv3_weight_operands2(const float* w, void* const* outs, 
     const long total = a.nfrag + a.nrows + b.nfrag + b.nrows;
     if (total > 0x7fffffffL * (long)kThreads) return COBEVT_ERR_SHAPE;
     hipLaunchKernelGGL(conv3_weight_operands_kernel, dim3((unsigned)((total + kThreads - 1) / kThreads)), dim3(kThreads), 0, stream, w, a, b, Cin);
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }
 
 extern "C" int cobevt_linear_weight_frags(const float* w, void* frag, void* frag_t, const int* dims, hipStream_t stream) {
@@ -263,7 +263,7 @@ extern "C" int cobevt_linear_weight_frags(const float* w, void* frag, void* frag
     const long pf = frag ? Np * Kp / 8 : 0, pt = frag_t ? Np * Kp / 8 : 0;
     hipLaunchKernelGGL(linear_weight_frags_kernel, dim3((unsigned)((pf + pt + kThreads - 1) / kThreads)), dim3(kThreads), 0, stream, w, (uint4*)frag,
                        (uint4*)frag_t, N, K, pf, pt);
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }
 
 extern "C" int cobevt_wgrad_block_operand(const void* src, void* dst, const int* dims, hipStream_t stream) {
@@ -277,5 +277,5 @@ extern "C" int cobevt_wgrad_block_operand(const void* src, void* dst, const int*
     const dim3 grid((unsigned)((items + kThreads - 1) / kThreads));
     if (g8) hipLaunchKernelGGL(wgrad_block8_kernel, grid, dim3(kThreads), 0, stream, (const uint16_t*)src, (uint16_t*)dst, items, H, W, C, Hp, NB, pt, pl, P, sx);
     else hipLaunchKernelGGL(wgrad_block1_kernel, grid, dim3(kThreads), 0, stream, (const uint16_t*)src, (uint16_t*)dst, items, H, W, C, Hp, NB, pt, pl, P, sx);
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }

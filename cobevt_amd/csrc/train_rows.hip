@@ -3,34 +3,16 @@
 // swap_fusion_modules.py:275-279, fax_modules.py:189-191,309-313) under train_camera.py:143-179.  HBM-bound elementwise work:
 // one wave per row, 16-byte accesses, the per-channel sums (dgamma, dbeta) accumulated in registers over a workgroup's rows
 // and added to the global fp32 vectors once per workgroup.
-#include "common.hpp"
+#include "wave_ops.hpp"
 
 namespace cobevt {
 namespace {
 
 constexpr int kLnMaxPerLane = 4;                         // float4 groups per lane: C <= 64 * 4 * 4 = 1024
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // y = LN(x) gamma + beta.  dx = rstd (g - mean(g) - xhat mean(g xhat)), g = dy gamma; dgamma += dy xhat; dbeta += dy.
 // x / dy / dx are fp32 or bf16 each (xb / db / ob: 1 = bf16) - inside a bf16 autocast region the residual stream is fp32 while the
 // gradient arriving from a projection's input gradient is bf16 (train_camera.py:157-160); the arithmetic is fp32 either way.
-__device__ __forceinline__ float4 ld4(const void* p, int bf, size_t i) {
-    if (bf) {
-        const uint2 u = *(const uint2*)((const uint16_t*)p + i);
-        return make_float4(__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u), __uint_as_float(u.y << 16), __uint_as_float(u.y & 0xffff0000u));
-    }
-    return *(const float4*)((const float*)p + i);
-}
-__device__ __forceinline__ void st4(void* p, int bf, size_t i, const float4& v) {
-    if (bf) *(uint2*)((uint16_t*)p + i) = make_uint2(pack_bf2(v.x, v.y), pack_bf2(v.z, v.w));
-    else *(float4*)((float*)p + i) = v;
-}
-
 __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const void* __restrict__ x, const void* __restrict__ dy,
                                                             const float* __restrict__ gamma, void* __restrict__ dx,
                                                             float* __restrict__ dgamma, float* __restrict__ dbeta, int rows, int C,
@@ -56,11 +38,11 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const void* __restri
         for (int i = 0; i < kLnMaxPerLane; ++i) {
             const int g = lane + 64 * i;
             const bool ok = g < groups;
-            xv[i] = ok ? ld4(x, xb, (size_t)row * C + 4 * g) : make_float4(0.f, 0.f, 0.f, 0.f);
-            dv[i] = ok ? ld4(dy, db_, (size_t)row * C + 4 * g) : make_float4(0.f, 0.f, 0.f, 0.f);
+            xv[i] = ok ? ld4q(x, (size_t)row * C + 4 * g, xb) : make_float4(0.f, 0.f, 0.f, 0.f);
+            dv[i] = ok ? ld4q(dy, (size_t)row * C + 4 * g, db_) : make_float4(0.f, 0.f, 0.f, 0.f);
             s += xv[i].x + xv[i].y + xv[i].z + xv[i].w;
         }
-        const float mean = wave_sum(s) * invC;
+        const float mean = wave_sum_xor(s, 64) * invC;
         float v = 0.f;
 #pragma unroll
         for (int i = 0; i < kLnMaxPerLane; ++i) {
@@ -69,7 +51,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const void* __restri
                 v += a * a + b * b + c * c + d * d;
             }
         }
-        const float rstd = 1.f / sqrtf(wave_sum(v) * invC + eps);
+        const float rstd = 1.f / sqrtf(wave_sum_xor(v, 64) * invC + eps);
         float sg = 0.f, sgx = 0.f;
 #pragma unroll
         for (int i = 0; i < kLnMaxPerLane; ++i) {
@@ -84,7 +66,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const void* __restri
                 sgx += dv[i].x * xv[i].x + dv[i].y * xv[i].y + dv[i].z * xv[i].z + dv[i].w * xv[i].w;
             }
         }
-        const float mg = wave_sum(sg) * invC, mgx = wave_sum(sgx) * invC;
+        const float mg = wave_sum_xor(sg, 64) * invC, mgx = wave_sum_xor(sgx, 64) * invC;
 #pragma unroll
         for (int i = 0; i < kLnMaxPerLane; ++i) {
             const int g = lane + 64 * i;
@@ -92,7 +74,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const void* __restri
                 float4 o;
                 o.x = rstd * (dv[i].x - mg - xv[i].x * mgx); o.y = rstd * (dv[i].y - mg - xv[i].y * mgx);
                 o.z = rstd * (dv[i].z - mg - xv[i].z * mgx); o.w = rstd * (dv[i].w - mg - xv[i].w * mgx);
-                st4(dx, ob, (size_t)row * C + 4 * g, o);
+                st4q(dx, (size_t)row * C + 4 * g, ob, o);
             }
         }
     }
@@ -115,12 +97,6 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const void* __restri
 
 // C <= 128 (the FAX / fusion width): a row is 32 float4 groups, so a whole wave per row leaves half of it idle and a row per HALF-wave
 // doubles the rows in flight (the 81,920 x 128 level-0 rows took 57 us per launch, 1.9 TB/s).  One float4 per lane, reductions inside 32 lanes.
-__device__ __forceinline__ float half_wave_sum(float v) {
-#pragma unroll
-    for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // NW waves per workgroup: 16 on big inputs - every workgroup ends in 2 C atomics on the SAME words, and 1,024 four-wave workgroups made the
 // 81,920-row launches 49 us for 105 MB (a serialised tail of ~1,000 atomics per word); the same waves in a quarter of the workgroups
 template <int NW>
@@ -144,10 +120,10 @@ __global__ __launch_bounds__(NW * 64) void layernorm_bwd_narrow_kernel(const voi
         const int rowb = row + HW;
         const bool okb = rowb < row1;
         float4 xv[2], dv[2];
-        xv[0] = ok ? ld4(x, xb, (size_t)row * C + 4 * g) : make_float4(0.f, 0.f, 0.f, 0.f);
-        dv[0] = ok ? ld4(dy, db_, (size_t)row * C + 4 * g) : make_float4(0.f, 0.f, 0.f, 0.f);
-        xv[1] = (ok && okb) ? ld4(x, xb, (size_t)rowb * C + 4 * g) : make_float4(0.f, 0.f, 0.f, 0.f);
-        dv[1] = (ok && okb) ? ld4(dy, db_, (size_t)rowb * C + 4 * g) : make_float4(0.f, 0.f, 0.f, 0.f);
+        xv[0] = ok ? ld4q(x, (size_t)row * C + 4 * g, xb) : make_float4(0.f, 0.f, 0.f, 0.f);
+        dv[0] = ok ? ld4q(dy, (size_t)row * C + 4 * g, db_) : make_float4(0.f, 0.f, 0.f, 0.f);
+        xv[1] = (ok && okb) ? ld4q(x, (size_t)rowb * C + 4 * g, xb) : make_float4(0.f, 0.f, 0.f, 0.f);
+        dv[1] = (ok && okb) ? ld4q(dy, (size_t)rowb * C + 4 * g, db_) : make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
             const float mean = half_wave_sum(xv[u].x + xv[u].y + xv[u].z + xv[u].w) * invC;
@@ -165,7 +141,7 @@ __global__ __launch_bounds__(NW * 64) void layernorm_bwd_narrow_kernel(const voi
             if (ok && (u == 0 || okb)) {
                 const float4 o = make_float4(rstd * (gv.x - mg - xh.x * mgx), rstd * (gv.y - mg - xh.y * mgx), rstd * (gv.z - mg - xh.z * mgx),
                                              rstd * (gv.w - mg - xh.w * mgx));
-                st4(dx, ob, (size_t)(u ? rowb : row) * C + 4 * g, o);
+                st4q(dx, (size_t)(u ? rowb : row) * C + 4 * g, ob, o);
             }
         }
     }
@@ -230,7 +206,7 @@ __global__ __launch_bounds__(256) void layernorm_fwd_mixed_narrow_kernel(const v
     const int g = lane & 31;
     const int row = blockIdx.x * 8 + wave * 2 + (lane >> 5);
     const bool ok = g < (C >> 2) && row < rows;
-    const float4 xv = ok ? ld4(x, xb, (size_t)row * C + 4 * g) : make_float4(0.f, 0.f, 0.f, 0.f);
+    const float4 xv = ok ? ld4q(x, (size_t)row * C + 4 * g, xb) : make_float4(0.f, 0.f, 0.f, 0.f);
     const float invC = 1.f / (float)C;
     const float mean = half_wave_sum(xv.x + xv.y + xv.z + xv.w) * invC;
     const float a = xv.x - mean, b = xv.y - mean, c = xv.z - mean, d = xv.w - mean;
@@ -238,7 +214,7 @@ __global__ __launch_bounds__(256) void layernorm_fwd_mixed_narrow_kernel(const v
     if (!ok) return;
     const float4 ga = gamma ? *(const float4*)(gamma + 4 * g) : make_float4(1.f, 1.f, 1.f, 1.f);
     const float4 be = beta ? *(const float4*)(beta + 4 * g) : make_float4(0.f, 0.f, 0.f, 0.f);
-    st4(y, yb, (size_t)row * C + 4 * g, make_float4(a * rstd * ga.x + be.x, b * rstd * ga.y + be.y, c * rstd * ga.z + be.z, d * rstd * ga.w + be.w));
+    st4q(y, (size_t)row * C + 4 * g, yb, make_float4(a * rstd * ga.x + be.x, b * rstd * ga.y + be.y, c * rstd * ga.z + be.z, d * rstd * ga.w + be.w));
 }
 
 // y = LN(x) gamma + beta with x fp32 | bf16 and y fp32 | bf16 (one wave per row, the statistics in fp32 from the row in registers):
@@ -256,11 +232,11 @@ __global__ __launch_bounds__(256) void layernorm_fwd_mixed_kernel(const void* __
 #pragma unroll
     for (int i = 0; i < kLnMaxPerLane; ++i) {
         const int g = lane + 64 * i;
-        xv[i] = g < groups ? ld4(x, xb, (size_t)row * C + 4 * g) : make_float4(0.f, 0.f, 0.f, 0.f);
+        xv[i] = g < groups ? ld4q(x, (size_t)row * C + 4 * g, xb) : make_float4(0.f, 0.f, 0.f, 0.f);
         s += xv[i].x + xv[i].y + xv[i].z + xv[i].w;
     }
     const float invC = 1.f / (float)C;
-    const float mean = wave_sum(s) * invC;
+    const float mean = wave_sum_xor(s, 64) * invC;
     float v = 0.f;
 #pragma unroll
     for (int i = 0; i < kLnMaxPerLane; ++i) {
@@ -269,7 +245,7 @@ __global__ __launch_bounds__(256) void layernorm_fwd_mixed_kernel(const void* __
             v += a * a + b * b + c * c + d * d;
         }
     }
-    const float rstd = 1.f / sqrtf(wave_sum(v) * invC + eps);
+    const float rstd = 1.f / sqrtf(wave_sum_xor(v, 64) * invC + eps);
 #pragma unroll
     for (int i = 0; i < kLnMaxPerLane; ++i) {
         const int g = lane + 64 * i;
@@ -279,7 +255,7 @@ __global__ __launch_bounds__(256) void layernorm_fwd_mixed_kernel(const void* __
             float4 o;
             o.x = (xv[i].x - mean) * rstd * ga.x + be.x; o.y = (xv[i].y - mean) * rstd * ga.y + be.y;
             o.z = (xv[i].z - mean) * rstd * ga.z + be.z; o.w = (xv[i].w - mean) * rstd * ga.w + be.w;
-            st4(y, yb, (size_t)row * C + 4 * g, o);
+            st4q(y, (size_t)row * C + 4 * g, yb, o);
         }
     }
 }
@@ -558,11 +534,11 @@ extern "C" int cobevt_layernorm_bwd(const float* x, const float* dy, const float
             hipLaunchKernelGGL(layernorm_bwd_narrow_kernel<4>, dim3((rows + rpb - 1) / rpb), dim3(256), 0, stream, (const void*)x, (const void*)dy,
                                gamma, (void*)dx, dgamma, dbeta, rows, C, eps, rpb, 0, 0, 0);
         }
-        return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+        return cobevt::launch_status();
     }
     hipLaunchKernelGGL(layernorm_bwd_kernel, dim3(blocks), dim3(256), 0, stream, (const void*)x, (const void*)dy, gamma, (void*)dx, dgamma, dbeta, rows, C,
                        eps, rpb, 0, 0, 0);
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }
 
 // dtypes: [x, dy, dx], 0 = bf16, 1 = fp32 each
@@ -584,11 +560,11 @@ extern "C" int cobevt_layernorm_bwd_t(const void* x, const void* dy, const float
             hipLaunchKernelGGL(layernorm_bwd_narrow_kernel<4>, dim3((rows + rpb - 1) / rpb), dim3(256), 0, stream, x, dy, gamma, dx, dgamma, dbeta, rows,
                                C, eps, rpb, dtypes[0] == 0, dtypes[1] == 0, dtypes[2] == 0);
         }
-        return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+        return cobevt::launch_status();
     }
     hipLaunchKernelGGL(layernorm_bwd_kernel, dim3(blocks), dim3(256), 0, stream, x, dy, gamma, dx, dgamma, dbeta, rows, C, eps, rpb,
                        dtypes[0] == 0, dtypes[1] == 0, dtypes[2] == 0);
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }
 
 // dtypes: [x, y], 0 = bf16, 1 = fp32 each
@@ -601,7 +577,7 @@ extern "C" int cobevt_layernorm_fwd_t(const void* x, const float* gamma, const f
                                      dtypes[0] == 0, dtypes[1] == 0);
     else hipLaunchKernelGGL(layernorm_fwd_mixed_kernel, dim3((rows + 3) / 4), dim3(256), 0, stream, x, gamma, beta, y, rows, C, eps, dtypes[0] == 0,
                             dtypes[1] == 0);
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }
 
 // bf16 x / dy / out: out = GELU(x) (dy null) or dy * GELU'(x); n % 8 == 0
@@ -610,7 +586,7 @@ extern "C" int cobevt_gelu_bf16(const void* x, const void* dy, void* out, long n
     if (n < 8 || n % 8) return COBEVT_ERR_SHAPE;
     const long n8 = n / 8;
     hipLaunchKernelGGL(gelu_bf16_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, stream, (const uint4*)x, (const uint4*)dy, (uint4*)out, n8);
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }
 
 extern "C" int cobevt_gelu(const float* x, const float* dy, float* out, long n, hipStream_t stream) {
@@ -618,7 +594,7 @@ extern "C" int cobevt_gelu(const float* x, const float* dy, float* out, long n, 
     if (n < 4 || n % 4) return COBEVT_ERR_SHAPE;
     const long n4 = n / 4;
     hipLaunchKernelGGL(gelu_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream, x, dy, out, n4);
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }
 
 extern "C" int cobevt_conv_wgrad(const void* x, const void* dy, float* dw, const int* dims, hipStream_t stream) {
@@ -642,7 +618,7 @@ extern "C" int cobevt_conv_wgrad(const void* x, const void* dy, float* dw, const
     const dim3 grid(tiles_o, tiles_i * ntap, (unsigned)chunks);
     if (dims[10] == 0) hipLaunchKernelGGL(conv_wgrad_kernel<bf16_t>, grid, dim3(256), 0, stream, p);
     else hipLaunchKernelGGL(conv_wgrad_kernel<float>, grid, dim3(256), 0, stream, p);
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }
 
 extern "C" int cobevt_conv_wgrad_blocked(const void* xb, const void* db, float* dw, const int* dims, hipStream_t stream) {
@@ -692,5 +668,5 @@ extern "C" int cobevt_conv_wgrad_blocked(const void* xb, const void* db, float* 
         if (p.k == 3) hipLaunchKernelGGL((conv_wgrad16_kernel<3, false>), grid, dim3(256), 0, stream, p);
         else hipLaunchKernelGGL((conv_wgrad16_kernel<1, false>), grid, dim3(256), 0, stream, p);
     }
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }

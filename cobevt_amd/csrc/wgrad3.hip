@@ -14,12 +14,10 @@
 // per output row); everything is wave-private, so there is no barrier in the loop.  The four waves of a workgroup split the pixels; their
 // accumulators are added through LDS and the workgroup's tile goes to a partial buffer [chunk][tile] that a second launch sums into dW
 // (plain stores: deterministic, no zero fill of dW, no atomics).
-#include "common.hpp"
+#include "wave_ops.hpp"
 
 namespace cobevt {
 namespace {
-
-typedef short v4s __attribute__((ext_vector_type(4)));
 
 struct Wgrad3Params {
     const bf16_t* x;     // (N, H, W, Cin)
@@ -30,11 +28,6 @@ struct Wgrad3Params {
     int units;           // N * nseg * H  (image, segment, row) triples, rows fastest
     int nchunks;
 };
-
-__device__ __forceinline__ uint2 tr_read(const unsigned char* lds) {
-    const v4s r = __builtin_amdgcn_ds_read_tr16_b64_v4i16((v4s __attribute__((address_space(3)))*)lds);
-    return __builtin_bit_cast(uint2, r);
-}
 
 template <int WS>
 __global__ __launch_bounds__(256, 2) void conv_wgrad3_tr_kernel(Wgrad3Params p) {
@@ -367,7 +360,7 @@ extern "C" int cobevt_conv_wgrad3(const void* x, const void* dy, float* dw, floa
     const long tile_elems = (long)p.Cout * p.Cin * 9;
     hipLaunchKernelGGL(conv_wgrad3_reduce_kernel, dim3((unsigned)(tile_elems / 64)), dim3(256), 0, stream, scratch, dw, chunks, tile_elems,
                        p.Cin / 32, p.Cin);
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }
 
 extern "C" int cobevt_linear_wgrad_chunks(const long* dims) {
@@ -398,5 +391,5 @@ extern "C" int cobevt_linear_wgrad(const void* x, const void* dy, float* dw, flo
     hipLaunchKernelGGL(linear_wgrad_tr_kernel, dim3(tiles, chunks), dim3(1024), 0, stream, p);
     const long elems = (long)p.Cout * p.Cin;
     hipLaunchKernelGGL(linear_wgrad_reduce_kernel, dim3((unsigned)(elems / 64)), dim3(256), 0, stream, scratch, dw, chunks, elems, p.TCn, p.Cin);
-    return hipGetLastError() == hipSuccess ? COBEVT_OK : COBEVT_ERR_LAUNCH;
+    return cobevt::launch_status();
 }

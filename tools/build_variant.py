@@ -16,16 +16,10 @@ name, flags = sys.argv[1], sys.argv[2:]
 out = os.path.join(ROOT, "tools", "_probe", "libs", name)
 os.makedirs(out, exist_ok=True)
 lib = os.path.join(out, "libcobevt_hip.so")
-procs, objs = [], []
-for src in b.SOURCES:
-    o = os.path.join(out, src.replace(".hip", ".o"))
-    objs.append(o)
-    procs.append((src, subprocess.Popen([b._hipcc()] + b.FLAGS + flags + ["-c", os.path.join(b.CSRC, src), "-o", o],
-                                        stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))
-for src, p in procs:
-    o_, _ = p.communicate()
-    if p.returncode:
-        raise SystemExit("hipcc failed for %s:\n%s" % (src, o_.decode(errors="replace")))
+try:
+    objs = b.compile_objects(out, flags, force=True, verbose=False)
+except RuntimeError as e:
+    raise SystemExit(str(e))
 subprocess.check_call([b._hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib] + objs)
 for o in objs:
     os.remove(o)
