@@ -1476,6 +1476,195 @@ def conv2d_weight(x, weight, bias, stride=1, pad=0):
     return Conv2dFn.apply(x, _master(weight).contiguous(), bias, stride, pad)
 
 
+# ----------------------------------------------------------------------------------------------
+# the LiDAR pillar front end in train() mode (csrc/train_pillar.hip)
+# ----------------------------------------------------------------------------------------------
+_PILLAR_STAT_DOUBLES = 512
+
+
+def _pillar_mode(norm):
+    """0 batch statistics (norm.training, or a norm without running statistics), 1 frozen running statistics, 2 no norm"""
+    if norm is None:
+        return 2
+    if norm.training or not norm.track_running_stats or norm.running_mean is None:
+        if norm.training and norm.track_running_stats and norm.momentum is None:
+            raise CobevtHipError("BatchNorm1d(momentum=None): the pillar training kernels keep an exponential running average and need a "
+                                 "numeric momentum")
+        return 0
+    return 1
+
+
+def pillar_train_stats(weight, gamma, beta, vf, npts, coords, record_len, norm, cfg):
+    """The statistics pass of PillarVfeFn (cobevt_pillar_train_stats: compaction of the valid pillars, fp64 sums, the finishing launch
+    incl. the running-statistics update) -> the state the forward and the backward take: the folded operands `wf` (K, 64) / `sf` (64) for
+    the inference operator, the valid pillars' order / destination rows / count, and the fp64 statistics block."""
+    geom, use_abs, dist, grid, max_cav, num_agents = cfg
+    _need_cuda(weight, gamma, beta, vf, npts, coords, record_len)
+    mode = _pillar_mode(norm)
+    if vf.dtype != torch.float32 or vf.dim() != 3 or not vf.is_contiguous():
+        raise CobevtHipError("pillar VFE training: voxel_features must be contiguous fp32 (P, T, 4)")
+    p, t, f = vf.shape
+    k = (4 if use_abs else 1) + 6 + (1 if dist else 0)
+    if f != 4 or t < 1 or t > ops.PILLAR_MAX_POINTS or tuple(weight.shape) != (ops.PILLAR_CHANNELS, k):
+        raise CobevtHipError("pillar VFE training: F = 4, 1 <= T <= %d and a (%d, %d) weight are supported, got F = %d, T = %d, weight %s"
+                             % (ops.PILLAR_MAX_POINTS, ops.PILLAR_CHANNELS, k, f, t, tuple(weight.shape)))
+    npts = ops._index_i32(npts, "pillar VFE training: voxel_num_points", ())
+    coords = ops._index_i32(coords, "pillar VFE training: voxel_coords", (4,))
+    if npts.shape[0] != p or coords.shape[0] != p:
+        raise CobevtHipError("pillar VFE training: voxel_num_points (P) and voxel_coords (P, 4) must match voxel_features' P = %d" % p)
+    dev = vf.device
+    w = _f32c(weight.detach(), "weight")
+    g = None if gamma is None else _f32c(gamma.detach(), "gamma")
+    b = None if beta is None else _f32c(beta.detach(), "beta")
+    rows = grid is None
+    ny, nx = (0, 0) if rows else (int(grid[0]), int(grid[1]))
+    rl = None
+    if not rows and record_len is not None:
+        if record_len.dtype != torch.int32 or record_len.dim() != 1 or not record_len.is_contiguous() or max_cav is None:
+            raise CobevtHipError("pillar VFE training: record_len must be int32 (B,) on the device, with max_cav given")
+        rl = record_len
+    if not rows and rl is None and num_agents is None:
+        raise CobevtHipError("pillar VFE training: num_agents (a host integer) is required without record_len")
+    nb = 0 if rl is None else rl.shape[0]
+    n = 0 if rows else (0x7fffffff if num_agents is None else int(num_agents))
+    dims = _ints([p, t, f, k, int(bool(use_abs)), int(bool(dist)), ops.FP32, int(rows), n, nb, int(max_cav or 0), ny, nx])
+    gm = (ctypes.c_float * 6)(*[float(v) for v in geom])
+    lib = _L.load("")
+    n_stat, n_bwd = ctypes.c_long(0), ctypes.c_long(0)
+    _L.check(lib.cobevt_pillar_train_scratch(p, ctypes.byref(n_stat), ctypes.byref(n_bwd)), "cobevt_pillar_train_scratch")
+    order = torch.empty(max(p, 1), device=dev, dtype=torch.int32)
+    dst = torch.empty(max(p, 1), device=dev, dtype=torch.int64)
+    count = torch.empty(1, device=dev, dtype=torch.int32)
+    partial = torch.empty(n_stat.value, device=dev, dtype=torch.float64)
+    wf = torch.empty((k, ops.PILLAR_CHANNELS), device=dev, dtype=torch.float32)
+    sf = torch.empty(ops.PILLAR_CHANNELS, device=dev, dtype=torch.float32)
+    stat = torch.empty(_PILLAR_STAT_DOUBLES, device=dev, dtype=torch.float64)
+    track = mode == 0 and norm.track_running_stats and norm.running_mean is not None
+    rm = norm.running_mean if (track or mode == 1) else None
+    rv = norm.running_var if (track or mode == 1) else None
+    nbt = norm.num_batches_tracked if track else None
+    eps = 0.0 if norm is None else norm.eps
+    momentum = 0.0 if (norm is None or norm.momentum is None) else norm.momentum
+    rc = lib.cobevt_pillar_train_stats(_p(vf), _p(npts), _p(coords), _p(rl), _p(w), _p(g), _p(b), _p(rm), _p(rv), _p(nbt), _p(order),
+                                       _p(dst), _p(count), _p(partial), _p(wf), _p(sf), _p(stat), dims, gm, mode, ctypes.c_float(eps),
+                                       ctypes.c_float(momentum), _stream())
+    _L.check(rc, "cobevt_pillar_train_stats")
+    if track:
+        # written through raw pointers: bump the version counters (plans folded from the running statistics, graph fingerprints)
+        for tns in (norm.running_mean, norm.running_var, norm.num_batches_tracked):
+            if tns is not None:
+                torch.autograd.graph.increment_version(tns)
+    return {"tensors": (vf, npts, coords, order, dst, count, wf, sf, w, g, stat), "rl": rl, "dims": dims, "geom": gm, "mode": mode,
+            "n_bwd": int(n_bwd.value), "k": k, "has_g": gamma is not None, "has_b": beta is not None}
+
+
+def pillar_train_forward(state, cfg):
+    """the forward IS the inference operator (csrc/pillar_vfe.hip) on the folded operands: -> rows (P, 64) | (canvas, cav_mask), fp32"""
+    geom, use_abs, dist, grid, max_cav, num_agents = cfg
+    vf, npts, coords, _, _, _, wf, sf = state["tensors"][:8]
+    if grid is None:
+        return ops.pillar_vfe_rows(vf, npts, coords, wf, sf, geom, torch.float32, use_absolute_xyz=use_abs, with_distance=dist), None
+    return ops.pillar_vfe_scatter(vf, npts, coords, wf, sf, geom, grid, torch.float32, use_absolute_xyz=use_abs, with_distance=dist,
+                                  record_len=state["rl"], max_cav=max_cav, num_agents=num_agents)
+
+
+def pillar_train_backward(tensors, dims, gm, mode, n_bwd, k, has_g, has_b, dout):
+    """cobevt_pillar_train_bwd: dout = the gradient of the rows / of the canvas (contiguous fp32) -> (d weight, d gamma, d beta | d bias)"""
+    vf, npts, coords, order, dst, count, wf, sf, w, g, stat = tensors
+    dev = vf.device
+    partial = torch.empty(n_bwd, device=dev, dtype=torch.float32)
+    dw = torch.empty((ops.PILLAR_CHANNELS, k), device=dev, dtype=torch.float32)
+    dg = torch.empty(ops.PILLAR_CHANNELS, device=dev, dtype=torch.float32) if has_g else None
+    db = torch.empty(ops.PILLAR_CHANNELS, device=dev, dtype=torch.float32) if has_b else None
+    rc = _L.load("").cobevt_pillar_train_bwd(_p(vf), _p(npts), _p(coords), _p(order), _p(dst), _p(count), _p(wf), _p(sf), _p(w), _p(g),
+                                           _p(stat), _p(dout), _p(partial), _p(dw), _p(dg), _p(db), dims, gm, mode, _stream())
+    _L.check(rc, "cobevt_pillar_train_bwd")
+    return dw, dg, db
+
+
+class PillarVfeFn(torch.autograd.Function):
+    """PillarVFE with one PFN layer in train() mode: Linear -> BatchNorm1d -> ReLU -> max over T (pillar_vfe.py:31-53), fused with the
+    point decoration and (canvas form) PointPillarScatter + regroup.  weight (64, K); gamma / beta the BatchNorm1d's affine pair, or
+    (None, bias) without a norm; `norm` the nn.BatchNorm1d container (its own .training flag picks batch or running statistics; its three
+    buffers are updated in place by the kernel) | None.  cfg = (geom, use_absolute_xyz, with_distance, grid | None, max_cav, num_agents):
+    grid None = rows form -> (P, 64); else -> (canvas (B, max_cav, ny, nx, 64) | (num_agents, ny, nx, 64), cav_mask | None).
+    The statistics run over the rows of exactly the pillars the inference operator writes.  fp32 in and out under any autocast; no
+    gradient with respect to the points.  Three steps: pillar_train_stats, pillar_train_forward, and pillar_train_backward in backward."""
+
+    @staticmethod
+    @_amp_fwd
+    def forward(ctx, weight, gamma, beta, vf, npts, coords, record_len, norm, cfg):
+        if vf.requires_grad:
+            raise CobevtHipError("pillar VFE training: no gradient with respect to voxel_features is offered (detach the points)")
+        state = pillar_train_stats(weight, gamma, beta, vf, npts, coords, record_len, norm, cfg)
+        out, cav = pillar_train_forward(state, cfg)
+        ctx.save_for_backward(*[t for t in state["tensors"] if t is not None])
+        ctx.has_gamma_tensor = state["tensors"][9] is not None
+        ctx.cfg = (state["dims"], state["geom"], state["mode"], state["n_bwd"], state["k"], tuple(out.shape), state["has_g"], state["has_b"])
+        if cfg[3] is None:
+            return out
+        if cav is None:
+            return out, None
+        ctx.mark_non_differentiable(cav)
+        return out, cav
+
+    @staticmethod
+    @_amp_bwd
+    def backward(ctx, dout, dcav=None):
+        saved = list(ctx.saved_tensors)
+        if not ctx.has_gamma_tensor:
+            saved.insert(9, None)
+        dims, gm, mode, n_bwd, k, shape, has_g, has_b = ctx.cfg
+        if tuple(dout.shape) != shape:
+            raise CobevtHipError("pillar VFE backward: gradient of shape %s for an output of shape %s" % (tuple(dout.shape), shape))
+        dw, dg, db = pillar_train_backward(tuple(saved), dims, gm, mode, n_bwd, k, has_g, has_b, _f32c(dout.float(), "dout"))
+        return dw, dg, db, None, None, None, None, None, None
+
+
+def pillar_vfe(pfn, vf, npts, coords, geom, use_absolute_xyz, with_distance, grid=None, record_len=None, max_cav=None, num_agents=None):
+    """the PFNLayer container `pfn` (host/pillar_vfe.py) in train() mode through PillarVfeFn: rows form (grid None) -> (P, 64); canvas
+    form -> (canvas, cav_mask)"""
+    cfg = (tuple(float(v) for v in geom), bool(use_absolute_xyz), bool(with_distance), None if grid is None else (int(grid[0]), int(grid[1])),
+           None if max_cav is None else int(max_cav), None if num_agents is None else int(num_agents))
+    if vf.requires_grad:
+        raise CobevtHipError("pillar VFE training: no gradient with respect to voxel_features is offered (detach the points)")
+    if pfn.use_norm:
+        _pillar_mode(pfn.norm)           # momentum=None raises before anything is launched
+        return PillarVfeFn.apply(pfn.linear.weight, pfn.norm.weight, pfn.norm.bias, vf, npts, coords, record_len, pfn.norm, cfg)
+    return PillarVfeFn.apply(pfn.linear.weight, None, pfn.linear.bias, vf, npts, coords, record_len, None, cfg)
+
+
+class ScatterRowsFn(torch.autograd.Function):
+    """PointPillarScatter (ops.scatter_rows) with its adjoint: rows (P, C) fp32 -> (num_agents, ny, nx, C) channels-last; the backward
+    gathers every row's cell of the canvas gradient (cobevt_gather_rows), zero for the rows the scatter skips"""
+
+    @staticmethod
+    @_amp_fwd
+    def forward(ctx, rows, coords, num_agents, grid):
+        _need_cuda(rows, coords)
+        rows = _f32c(rows, "pillar_features")
+        coords = ops._index_i32(coords, "scatter_rows: voxel_coords", (4,))
+        out = ops.scatter_rows(rows, coords, num_agents, grid)
+        ctx.save_for_backward(coords)
+        ctx.cfg = (tuple(rows.shape), int(num_agents), int(grid[0]), int(grid[1]))
+        return out
+
+    @staticmethod
+    @_amp_bwd
+    def backward(ctx, dcanvas):
+        (coords,) = ctx.saved_tensors
+        (p, c), n, ny, nx = ctx.cfg
+        dcanvas = _f32c(dcanvas.float(), "d canvas")
+        drows = torch.empty((p, c), device=dcanvas.device, dtype=torch.float32)
+        rc = _L.load("").cobevt_gather_rows(_p(dcanvas), _p(coords), _p(drows), ops.FP32, p, c, n, ny, nx, _stream())
+        _L.check(rc, "cobevt_gather_rows")
+        return drows, None, None, None
+
+
+def scatter_rows(rows, coords, num_agents, grid):
+    return ScatterRowsFn.apply(rows, coords, int(num_agents), (int(grid[0]), int(grid[1])))
+
+
 def _env_flags():
     """COBEVT_TRAIN_FLAGS="USE_TORCH_OPERAND_PREP=1,USE_WGRAD_BLOCKED=0": the module's USE_* switches from the environment (same-job A/B
     runs of tools/train_probe.py; never set in production)"""

@@ -5,13 +5,15 @@ forward(batch_dict) -> batch_dict['pillar_features'].
 The HIP operator (csrc/pillar_vfe.hip) implements ONE PFN layer of 64 output channels on pillars of at most 32 points with 4 point
 features; every other configuration raises CobevtHipError at construction.  The eval-mode BatchNorm1d (eps as stored) is folded into
 the bias-free Linear when the plan is built: W (K, 64), shift (64), both fp32 - the operator's arithmetic is fp32 in every compute
-mode, only its store converts."""
+mode, only its store converts.  In train() mode the forward runs host/training.pillar_vfe: BatchNorm1d on batch statistics (or, after
+norm.eval(), the frozen running ones) with HIP kernels in both directions (csrc/train_pillar.hip), parameter gradients only."""
 import torch
 import torch.nn as nn
 
 from .. import ops
 from ..lib import CobevtHipError
 from . import runtime as rt
+from . import training
 from .runtime import HipModule
 
 
@@ -97,7 +99,10 @@ class PillarVFE(HipModule):
 
     def forward(self, batch_dict):
         """batch_dict: voxel_features (P, T, 4) fp32, voxel_num_points (P,), voxel_coords (P, 4) [n, z, y, x] ->
-        batch_dict['pillar_features'] (P, 64), always two-dimensional (the reference's squeeze() collapses P = 1)"""
+        batch_dict['pillar_features'] (P, 64), always two-dimensional (the reference's squeeze() collapses P = 1).  train(): fp32,
+        differentiable in the layer's parameters (not in the points)"""
+        if self.training and training.lidar_trains(self.pfn_layers[0], batch_dict["voxel_features"]):
+            return training.pillar_vfe(self, batch_dict)
         vf, npts, coords = batch_dict["voxel_features"], batch_dict["voxel_num_points"], batch_dict["voxel_coords"]
         self._require_inference(vf, npts, coords)
         w, shift = self.pfn_layers[0].folded()

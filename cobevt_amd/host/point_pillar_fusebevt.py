@@ -9,12 +9,14 @@ num_filters: [64]}; point_pillar_scatter {num_features: 64, grid_size: [nx, ny, 
 forward(batch_dict): batch_dict['processed_lidar'] = {voxel_features (P, T <= 32, 4) fp32, voxel_coords (P, 4) [n, z, y, x],
 voxel_num_points (P,)} and batch_dict['record_len'] (B,) -> {'fused_feature': (B, 64, ny, nx)} fp32.  The front end is ONE operator
 call (two launches) from the voxels straight into the (B, max_cav, ny, nx, 64) canvas FuseBEVT reads; rows whose batch index is
-negative are skipped, which is how a caller pads P to a fixed size for graph replay."""
+negative are skipped, which is how a caller pads P to a fixed size for graph replay.  In train() mode the forward is the differentiable
+graph of host/training.point_pillar_fusebevt (batch statistics over the pillars the operator writes; parameter gradients)."""
 import torch
 
 from .. import ops
 from ..lib import CobevtHipError
 from . import runtime as rt
+from . import training
 from .pillar_vfe import PillarVFE
 from .point_pillar_scatter import PointPillarScatter
 from .runtime import HipModule
@@ -51,6 +53,8 @@ class PointPillarFuseBEVT(HipModule):
                                       with_distance=self.pillar_vfe.with_distance, record_len=rl, max_cav=self.max_cav, out=out)
 
     def forward(self, batch_dict):
+        if self.training and training.lidar_trains(self.pillar_vfe.pfn_layers[0], batch_dict["processed_lidar"]["voxel_features"]):
+            return training.point_pillar_fusebevt(self, batch_dict)
         self._require_inference()
         x, cav_mask = self.front_end(batch_dict)
         b, l, h, w, _ = x.shape

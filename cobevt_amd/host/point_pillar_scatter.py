@@ -3,6 +3,7 @@ cell z + y * nx + x of agent n (y is the row).  The map is channels-last on the 
 from .. import ops
 from ..lib import CobevtHipError
 from . import runtime as rt
+from . import training
 from .runtime import HipModule
 
 
@@ -21,7 +22,9 @@ class PointPillarScatter(HipModule):
         NCHW view of a channels-last tensor in the caller's dtype.  N is batch_dict['batch_size'] when present (a host integer: no
         synchronisation); otherwise it is derived as the reference derives it, `coords[:, 0].max() + 1` - the ONE synchronising
         path of the LiDAR front end.  Every cell without a pillar is exactly 0; rows with n outside [0, N) or y / x outside the
-        grid are skipped."""
+        grid are skipped.  train(): the same map in fp32, differentiable in pillar_features (the backward gathers each row's cell)."""
+        if self.training and training.lidar_trains(None, batch_dict["pillar_features"].detach()):
+            return training.point_pillar_scatter(self, batch_dict)
         rows, coords = batch_dict["pillar_features"], batch_dict["voxel_coords"]
         self._require_inference(rows, coords)
         if rows.dim() != 2 or rows.shape[1] != self.num_bev_features:

@@ -14,6 +14,15 @@ from ..lib import CobevtHipError
 from .runtime import GraphOwner
 
 
+def _to_static(v, device):
+    """a batch entry as a static buffer: tensors cloned onto the device, nested dicts (PointPillarFuseBEVT's 'processed_lidar') entry by entry"""
+    if torch.is_tensor(v):
+        return v.to(device).clone()
+    if isinstance(v, dict):
+        return {k: _to_static(x, device) for k, x in v.items()}
+    return v
+
+
 def _state_tensors(optimizer):
     for st in optimizer.state.values():
         for v in st.values():
@@ -24,7 +33,8 @@ def _state_tensors(optimizer):
 class CapturedTrainStep(GraphOwner):
     """step(batch) == one eager training step on `batch`, returning the (static) loss tensor.
 
-    model      a HipModule in train() mode on a ROCm device (CorpBEVT / FaxFusedTransformer)
+    model      a HipModule in train() mode on a ROCm device (CorpBEVT / FaxFusedTransformer / PointPillarFuseBEVT, whose voxel
+               tensors sit in the nested 'processed_lidar' dict: pad P to a fixed size with rows of agent index -1)
     criterion  callable (output_dict, batch) -> scalar loss (e.g. VanillaSegLoss via a lambda picking the ground-truth keys)
     optimizer  torch.optim.SGD, or Adam / AdamW built with capturable=True
     example_batch  dict of tensors with the shapes every later batch will have
@@ -52,7 +62,7 @@ class CapturedTrainStep(GraphOwner):
         self.model, self.criterion, self.optimizer, self.reducer = model, criterion, optimizer, reducer
         self.autocast_dtype = autocast_dtype
         self.device = p0.device
-        self.static_batch = {k: (v.to(self.device).clone() if torch.is_tensor(v) else v) for k, v in example_batch.items()}
+        self.static_batch = _to_static(dict(example_batch), self.device)
         if "record_len" in example_batch:          # the agent counts shape the graph: read them on the host once, before the capture
             self.static_batch["record_len_host"] = [int(v) for v in example_batch["record_len"]]
         self.loss = None
@@ -141,10 +151,14 @@ class CapturedTrainStep(GraphOwner):
         # the capture itself did not run anything: parameters, optimizer state and BatchNorm statistics are still the restored ones
 
     # ------------------------------------------------------------------------------------------------------------------
-    def load(self, batch):
-        """copy a new batch into the static buffers (shapes fixed at capture)"""
+    def load(self, batch, _static=None, _prefix=""):
+        """copy a new batch into the static buffers (shapes fixed at capture); nested dicts are copied entry by entry"""
+        static = self.static_batch if _static is None else _static
         for k, v in batch.items():
-            dst = self.static_batch.get(k)
+            dst = static.get(k)
+            if isinstance(v, dict) and isinstance(dst, dict):
+                self.load(v, dst, _prefix + k + ".")
+                continue
             if k == "record_len" and torch.is_tensor(v) and not v.is_cuda \
                     and [int(x) for x in v] != self.static_batch["record_len_host"]:
                 raise CobevtHipError("CapturedTrainStep captured record_len %s, got %s (capture a new step per agent-count pattern)"
@@ -153,7 +167,7 @@ class CapturedTrainStep(GraphOwner):
                 continue
             if tuple(v.shape) != tuple(dst.shape):
                 raise CobevtHipError("CapturedTrainStep captured %s of shape %s, got %s (capture a new step for a new shape)"
-                                     % (k, tuple(dst.shape), tuple(v.shape)))
+                                     % (_prefix + k, tuple(dst.shape), tuple(v.shape)))
             dst.copy_(v, non_blocking=True)
 
     def step(self, batch=None):

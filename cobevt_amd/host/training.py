@@ -8,7 +8,7 @@ own nn.Parameter containers, so optimizers, state_dicts and the gradient all-red
 reference's names.
 
 Covered: swap Attention / PreNormResidual / FeedForward / SwapFusionBlock(Mask) / SwapFusionEncoder
-(swap_fusion_modules.py:13-286, base_transformer.py:102-124), FAX CrossWinAttention, CrossViewSwapAttention and the global
+(swap_fusion_modules.py:13-286, base_transformer.py:102-124), the LiDAR pillar front end and PointPillarFuseBEVT, FAX CrossWinAttention, CrossViewSwapAttention and the global
 Attention (fax_modules.py:93-441).  The 3x3-convolutional parts (encoders, decoder, Bottlenecks, down-sampling blocks) have no
 backward kernels yet: their modules keep raising in train() mode.
 """
@@ -93,12 +93,77 @@ def swap_fusion_block(block, x, mask):
 def swap_fusion_encoder(enc, x, mask):
     """SwapFusionEncoder.forward (:266-286): x (b, m, d, h, w), mask (b, h, w, 1, m) | None -> (b, d, h, w)."""
     _check(x)
-    y = to_blhwc(x)
+    return swap_fusion_encoder_blhwc(enc, to_blhwc(x), mask)
+
+
+def swap_fusion_encoder_blhwc(enc, y, mask):
+    """the body of swap_fusion_encoder from the channels-last tensor y (b, m, h, w, d) -> (b, d, h, w)"""
     for layer in enc.layers:
         y = run_stages(layer.stages(), y, lambda i: mask if layer.uses_mask else None)
     y = y.mean(dim=1)                                                        # Reduce('b m d h w -> b d h w', 'mean')
     y = ag.linear(ag.layernorm(y.contiguous(), enc.mlp_head[2], for_projection=True), enc.mlp_head[3])
     return y.permute(0, 3, 1, 2)
+
+
+# ----------------------------------------------------------------------------------------------
+# the LiDAR pillar front end (sub_modules/pillar_vfe.py, point_pillar_scatter.py) and PointPillarFuseBEVT in train() mode
+# ----------------------------------------------------------------------------------------------
+def _lidar(batch_dict):
+    return batch_dict["voxel_features"], batch_dict["voxel_num_points"], batch_dict["voxel_coords"]
+
+
+def lidar_trains(pfn, voxel_features):
+    """Whether a train() forward of the pillar front end takes the differentiable graph: it does for tensors on a ROCm device.  What
+    that graph cannot do raises here, before anything is launched: a gradient with respect to the points, a cumulative running
+    average.  There is no CPU path; on CPU tensors the caller goes on to its stand-alone forward, whose train() refusal names .eval()
+    and this module."""
+    if voxel_features.requires_grad:
+        raise CobevtHipError("pillar VFE training: no gradient with respect to voxel_features is offered (detach the points)")
+    if pfn is not None and pfn.use_norm:
+        ag._pillar_mode(pfn.norm)
+    return voxel_features.is_cuda
+
+
+def pillar_vfe(vfe, batch_dict):
+    """PillarVFE.forward in train() mode (pillar_vfe.py:105-146 over PFNLayer.forward :31-53): batch statistics over the rows of the
+    pillars with voxel_num_points > 0 (a pillar without points gives a zero row and stays out of the statistics; the reference divides
+    by zero there) -> batch_dict['pillar_features'] (P, 64) fp32"""
+    vf, npts, coords = _lidar(batch_dict)
+    batch_dict["pillar_features"] = ag.pillar_vfe(vfe.pfn_layers[0], vf, npts, coords, vfe.geom(), vfe.use_absolute_xyz, vfe.with_distance)
+    return batch_dict
+
+
+def point_pillar_scatter(sc, batch_dict):
+    """PointPillarScatter.forward in train() mode: differentiable in pillar_features -> batch_dict['spatial_features'] (N, C, ny, nx) fp32"""
+    rows, coords = batch_dict["pillar_features"], batch_dict["voxel_coords"]
+    if rows.dim() != 2 or rows.shape[1] != sc.num_bev_features:
+        raise CobevtHipError("PointPillarScatter: pillar_features must be (P, %d), got %s" % (sc.num_bev_features, tuple(rows.shape)))
+    if "batch_size" in batch_dict:
+        batch_size = int(batch_dict["batch_size"])
+    else:
+        batch_size = int(coords[:, 0].max().int().item()) + 1              # point_pillar_scatter.py:18 (host synchronisation)
+    canvas = ag.scatter_rows(rows.float(), coords, batch_size, (sc.ny, sc.nx))
+    batch_dict["spatial_features"] = canvas.permute(0, 3, 1, 2)
+    return batch_dict
+
+
+def point_pillar_fusebevt(model, batch_dict):
+    """PointPillarFuseBEVT.forward in train() mode: ONE front-end Function (statistics pass, the inference operator on the folded
+    operands; its backward reads the canvas gradient at each pillar's cell) straight into the (B, max_cav, ny, nx, 64) canvas, the
+    agent mask as the inference forward builds it, then the SwapFusionEncoder graph -> {'fused_feature': (B, 64, ny, nx)}.
+    The batch statistics run over exactly the pillars the inference operator writes: agent index inside record_len's agents and a
+    regrouped slot < max_cav, y / x inside the grid, voxel_num_points > 0.  With every pillar valid that is the reference's module;
+    the one deviation: the pillars of agents beyond max_cav, which the canvas drops, do not enter the statistics either.
+    Precondition (not checked): cell coordinates are unique per agent."""
+    vf, npts, coords = _lidar(batch_dict["processed_lidar"])
+    vfe, sc = model.pillar_vfe, model.scatter
+    rl = torch.as_tensor(batch_dict["record_len"]).to(device=vf.device, dtype=torch.int32)
+    x, cav_mask = ag.pillar_vfe(vfe.pfn_layers[0], vf, npts, coords, vfe.geom(), vfe.use_absolute_xyz, vfe.with_distance,
+                                grid=(sc.ny, sc.nx), record_len=rl, max_cav=model.max_cav)
+    b, l, h, w, _ = x.shape
+    com_mask = cav_mask[:, None, None, None, :].expand(b, h, w, 1, l).contiguous()
+    fused = swap_fusion_encoder_blhwc(model.fusion_net, x, com_mask)           # (B, 64, ny, nx)-shaped
+    return {"fused_feature": fused.float()}
 
 
 def _project(seq, t):

@@ -139,6 +139,10 @@ SIGNATURES = {
     "cobevt_channel_gate_nhwc": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]),
     "cobevt_pillar_vfe": (ctypes.c_int, [_vp] * 8 + [_c_int_p, _c_float_p, _vp]),
     "cobevt_scatter_rows": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_long] + [ctypes.c_int] * 4 + [_vp]),
+    "cobevt_pillar_train_scratch": (ctypes.c_int, [ctypes.c_long, _c_long_p, _c_long_p]),
+    "cobevt_pillar_train_stats": (ctypes.c_int, [_vp] * 17 + [_c_int_p, _c_float_p, ctypes.c_int, ctypes.c_float, ctypes.c_float, _vp]),
+    "cobevt_pillar_train_bwd": (ctypes.c_int, [_vp] * 16 + [_c_int_p, _c_float_p, ctypes.c_int, _vp]),
+    "cobevt_gather_rows": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_long] + [ctypes.c_int] * 4 + [_vp]),
 }
 
 _libs = {}

@@ -766,6 +766,40 @@ int cobevt_pillar_vfe(const float* voxel_features, const int* voxel_num_points, 
 int cobevt_scatter_rows(const void* rows, const int* voxel_coords, void* out, int dtype, long P, int C, int N, int ny, int nx,
                         hipStream_t stream);
 
+/*
+ * Train mode of the pillar front end (csrc/train_pillar.hip): Linear -> BatchNorm1d on BATCH statistics -> ReLU -> max over T
+ * (pillar_vfe.py:31-53 in train()).  The statistics run over the rows of exactly the pillars cobevt_pillar_vfe writes (rows form:
+ * voxel_num_points > 0), masked all-zero rows included, and are formed from sum(f) and the K x K Gram matrix of the decorated features
+ * in fp64 - no (P, T, 64) tensor.  dims / geom as for cobevt_pillar_vfe (dims[6], the dtype, is ignored: fp32).  No host read, no
+ * floating-point atomics: results are bitwise reproducible and do not depend on where skipped rows sit in the batch.
+ *
+ * cobevt_pillar_train_scratch: element counts of `partial` (fp64) for _stats and of `partial` (fp32) for _bwd at P pillars.
+ *
+ * cobevt_pillar_train_stats, mode 0 batch statistics | 1 frozen running statistics | 2 no norm (gamma NULL, beta = the Linear's bias):
+ *   w (64, K) the Linear's weight; order (P) int32, dst (P) int64, count (1) int32: the valid pillars in index order, their
+ *   destination rows and their number (written in every mode); w_folded (K, 64), shift_folded (64): the operands cobevt_pillar_vfe
+ *   takes for the forward; stat (512) fp64: M = count x T, sum(f), the Gram matrix, mean, rstd, biased variance, for the backward.
+ *   Mode 0 also updates running_mean / running_var (the latter with M / (M - 1)) at `momentum` and adds 1 to num_batches_tracked
+ *   (int64), all three optional; with zero valid pillars nothing is updated.
+ *
+ * cobevt_pillar_train_bwd: dout = gradient of the canvas (or of the dense rows), fp32, read at every valid pillar's destination row
+ *   where its maximum is positive, applied at the winning row (lowest index on ties).  dw (64, K), dgamma (64), dbeta (64; d bias in
+ *   mode 2) fp32; the other arguments as _stats left them.
+ */
+int cobevt_pillar_train_scratch(long P, long* stats_doubles, long* bwd_floats);
+int cobevt_pillar_train_stats(const float* voxel_features, const int* voxel_num_points, const int* voxel_coords, const int* record_len,
+                              const float* w, const float* gamma, const float* beta, float* running_mean, float* running_var,
+                              long* num_batches_tracked, int* order, long* dst, int* count, double* partial, float* w_folded,
+                              float* shift_folded, double* stat, const int* dims, const float* geom, int mode, float eps, float momentum,
+                              hipStream_t stream);
+int cobevt_pillar_train_bwd(const float* voxel_features, const int* voxel_num_points, const int* voxel_coords, const int* order,
+                            const long* dst, const int* count, const float* w_folded, const float* shift_folded, const float* w,
+                            const float* gamma, const double* stat, const float* dout, float* partial, float* dw, float* dgamma,
+                            float* dbeta, const int* dims, const float* geom, int mode, hipStream_t stream);
+/* backward of cobevt_scatter_rows: rows (P, C) <- the canvas gradient (N, ny, nx, C) at each row's cell; zero for skipped rows */
+int cobevt_gather_rows(const void* canvas, const int* voxel_coords, void* rows, int dtype, long P, int C, int N, int ny, int nx,
+                       hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,7 +6,9 @@ events, median over `--steps` such batches:
   * front end + FuseBEVT (PointPillarFuseBEVT.forward with bench.py's LIDAR_ARGS encoder), and that encoder alone on the canvas;
   * for comparison, the restatement (tests/pillar_ref.py) run as torch ops on the same GPU, eager.
 The front end's bytes moved / time is set against the stream-copy bandwidth bench.box_calibration measures in the same run.
-Usage (GPU box): python tools/pillar_probe.py [--steps 20] [--dtype bf16]"""
+--train: the train-mode front end (csrc/train_pillar.hip) at the same shape in fp32 instead - the statistics pass, the forward and the
+backward each as its own captured graph, and the torch restatement's (tests/pillar_train_ref.py) forward + backward on the same GPU.
+Usage (GPU box): python tools/pillar_probe.py [--steps 20] [--dtype bf16] [--train]"""
 import argparse
 import os
 import sys
@@ -20,6 +22,8 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import bench  # noqa: E402
 import cases_pillar as cp  # noqa: E402
 import pillar_ref as pr  # noqa: E402
+import pillar_train_ref as ptr  # noqa: E402
+from cobevt_amd import autograd as ag  # noqa: E402
 from cobevt_amd import host, ops  # noqa: E402
 from cobevt_amd.host import pipeline  # noqa: E402
 from cobevt_amd.synth import fill_module_  # noqa: E402
@@ -27,6 +31,7 @@ from cobevt_amd.synth import fill_module_  # noqa: E402
 ap = argparse.ArgumentParser()
 ap.add_argument("--steps", type=int, default=20)
 ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
+ap.add_argument("--train", action="store_true", help="time the train-mode statistics pass, forward and backward instead")
 args = ap.parse_args()
 dev = torch.device("cuda")
 torch.set_grad_enabled(False)
@@ -109,5 +114,59 @@ def main():
           % (us_torch, us_torch / us_front, err))
 
 
+def train():
+    host.set_compute_dtype("fp32")
+    margs = cp.model_args(grid=GRID, max_cav=8, fusion=dict(bench.LIDAR_ARGS))
+    m = fill_module_(host.PointPillarFuseBEVT(margs), 0).train().to(dev)
+    vox = {k: v.to(dev) for k, v in cp.voxels(counts=COUNTS, grid=GRID, stride=40503, tag="full").items()}
+    rl = torch.tensor([8], dtype=torch.int32, device=dev)
+    vf, coords, npts = vox["voxel_features"], vox["voxel_coords"], vox["voxel_num_points"]
+    p, t = vf.shape[:2]
+    vfe, pfn = m.pillar_vfe, m.pillar_vfe.pfn_layers[0]
+    cfg = (vfe.geom(), vfe.use_absolute_xyz, vfe.with_distance, GRID, 8, None)
+
+    def stats(a, b, c, r):
+        return ag.pillar_train_stats(pfn.linear.weight, pfn.norm.weight, pfn.norm.bias, a, c, b, r, pfn.norm, cfg)
+    state = stats(vf, coords, npts, rl)
+    canvas, _ = ag.pillar_train_forward(state, cfg)
+    dcanvas = torch.randn(canvas.shape, device=dev, generator=torch.Generator(dev).manual_seed(0))
+    bwd_args = (state["dims"], state["geom"], state["mode"], state["n_bwd"], state["k"], True, True)
+    g_stats = pipeline.CapturedCall(lambda a, b, c, r: stats(a, b, c, r)["tensors"][6], vf, coords, npts, rl)
+    g_fwd = pipeline.CapturedCall(lambda w_, s_: ag.pillar_train_forward(dict(state, tensors=state["tensors"][:6] + (w_, s_)), cfg)[0],
+                                  state["tensors"][6], state["tensors"][7])
+    g_bwd = pipeline.CapturedCall(lambda d: ag.pillar_train_backward(state["tensors"], *bwd_args, d)[0], dcanvas)
+    us_stats, us_fwd, us_bwd = timed(g_stats.step, args.steps), timed(g_fwd.step, args.steps), timed(g_bwd.step, args.steps)
+
+    # the torch restatement, forward + backward, eager fp32 on this GPU; and the operator's step against it
+    sd = {k: v.detach().clone() for k, v in m.state_dict().items()}
+
+    def torch_step():
+        prm = ptr.params(sd, "pillar_vfe.pfn_layers.0.", True)
+        with torch.enable_grad():
+            x, _ = ptr.canvas(prm, vf, npts, coords, cfg[0], GRID[0], GRID[1], [8], 8)
+            (x * dcanvas).sum().backward()
+        return x.detach(), prm
+    ref, prm = torch_step()
+    us_torch = timed(torch_step, max(3, args.steps // 5), warm=1, batch=1)
+    dw = ag.pillar_train_backward(state["tensors"], *bwd_args, dcanvas)[0]
+    torch.cuda.synchronize()
+    e_fwd = float((canvas - ref).abs().max() / ref.abs().max())
+    e_dw = float((dw - prm["linear.weight"].grad).abs().max() / prm["linear.weight"].grad.abs().max())
+    total = us_stats + us_fwd + us_bwd
+    print("box: %s" % torch.cuda.get_device_name(0))
+    print("shape: %d pillars x T = %d over 8 agents, canvas (1, 8, %d, %d, 64) fp32 = %.1f MB, voxels %.1f MB; train mode, batch statistics"
+          % (p, t, GRID[0], GRID[1], canvas.numel() * 4 / 1e6, 16 * p * t / 1e6))
+    print("statistics pass (compaction + fp64 sums + finish, one graph): %8.1f us   one %.1f MB read" % (us_stats, 16 * p * t / 1e6))
+    print("forward (the inference operator on the folded operands, fp32): %7.1f us" % us_fwd)
+    print("backward (recompute + winners + partials, finish, one graph): %8.1f us" % us_bwd)
+    print("training front end, sum of the three:                         %8.1f us" % total)
+    print("restatement forward + backward as torch ops on this GPU:      %8.1f us   (eager, fp32; %.0fx); operator against it: "
+          "forward max-rel %.2e, d linear.weight %.2e" % (us_torch, us_torch / total, e_fwd, e_dw))
+
+
 if __name__ == "__main__":
-    main()
+    if args.train:
+        torch.set_grad_enabled(False)
+        train()
+    else:
+        main()
