@@ -4,7 +4,11 @@ fusion_modules/swap_fusion_modules.py.  OpenCOOD projects every agent's points i
 no STTF warp here.
 
 args: voxel_size [x, y, z]; lidar_range [x0, y0, z0, x1, y1, z1]; max_cav; pillar_vfe {use_norm, with_distance, use_absolute_xyz,
-num_filters: [64]}; point_pillar_scatter {num_features: 64, grid_size: [nx, ny, 1]}; fax_fusion: SwapFusionEncoder's arguments.
+num_filters: [64]}; point_pillar_scatter {num_features: 64, grid_size: [nx, ny, 1]}; fax_fusion: SwapFusionEncoder's arguments;
+optionally preprocess {args: {voxel_size, max_points_per_voxel, max_voxel_train, max_voxel_test}, cav_lidar_range}: SpVoxelPreprocessor's
+arguments (its grid must be the scatter's).  With it a batch may carry raw points, batch_dict['lidar_points'] (M, 4) fp32 and
+batch_dict['lidar_point_offsets'] (N + 1,) on the device, INSTEAD of processed_lidar: the forward voxelises them on the device
+(ops.voxelize_points, voxel cap by train() / eval()) and continues with that dict, in both modes.
 
 forward(batch_dict): batch_dict['processed_lidar'] = {voxel_features (P, T <= 32, 4) fp32, voxel_coords (P, 4) [n, z, y, x],
 voxel_num_points (P,)} and batch_dict['record_len'] (B,) -> {'fused_feature': (B, 64, ny, nx)} fp32.  The front end is ONE operator
@@ -20,6 +24,7 @@ from . import training
 from .pillar_vfe import PillarVFE
 from .point_pillar_scatter import PointPillarScatter
 from .runtime import HipModule
+from .sp_voxel_preprocessor import SpVoxelPreprocessor
 from .swap_fusion_modules import SwapFusionEncoder
 
 
@@ -30,6 +35,9 @@ class PointPillarFuseBEVT(HipModule):
         vfe_cfg = dict(args["pillar_vfe"])
         if "max_points_per_voxel" in args and "max_points_per_voxel" not in vfe_cfg:
             vfe_cfg["max_points_per_voxel"] = args["max_points_per_voxel"]
+        pre = args.get("preprocess")
+        if pre is not None and "max_points_per_voxel" not in vfe_cfg:
+            vfe_cfg["max_points_per_voxel"] = pre["args"]["max_points_per_voxel"]
         self.pillar_vfe = PillarVFE(vfe_cfg, num_point_features=4, voxel_size=args["voxel_size"],
                                     point_cloud_range=args["lidar_range"])
         self.scatter = PointPillarScatter(args["point_pillar_scatter"])
@@ -40,10 +48,33 @@ class PointPillarFuseBEVT(HipModule):
                                  "PFN layer's %d channels" % c)
         if self.max_cav < 1:
             raise CobevtHipError("PointPillarFuseBEVT: max_cav must be at least 1")
+        # plain objects without parameters: the state_dict is the same with and without `preprocess`
+        self.preprocessors = None
+        if pre is not None:
+            self.preprocessors = {train: SpVoxelPreprocessor(pre, train) for train in (False, True)}
+            grid = tuple(self.preprocessors[False].grid_size)
+            if grid != (self.scatter.nx, self.scatter.ny, self.scatter.nz):
+                raise CobevtHipError("PointPillarFuseBEVT: preprocess gives the grid %r (round((cav_lidar_range hi - lo) / voxel_size)), "
+                                     "point_pillar_scatter.grid_size is %r" % (list(grid), [self.scatter.nx, self.scatter.ny, self.scatter.nz]))
+
+    def with_voxels(self, batch_dict):
+        """batch_dict as it is when it carries processed_lidar; otherwise a copy with processed_lidar voxelised from lidar_points /
+        lidar_point_offsets on the device"""
+        if "processed_lidar" in batch_dict:
+            return batch_dict
+        if "lidar_points" not in batch_dict or "lidar_point_offsets" not in batch_dict:
+            raise CobevtHipError("PointPillarFuseBEVT: the batch carries neither processed_lidar nor lidar_points + lidar_point_offsets")
+        if self.preprocessors is None:
+            raise CobevtHipError("PointPillarFuseBEVT: lidar_points need the model's args['preprocess'] section (voxel_size, "
+                                 "max_points_per_voxel, max_voxel_train / max_voxel_test, cav_lidar_range); without it pass processed_lidar")
+        out = dict(batch_dict)
+        out["processed_lidar"] = self.preprocessors[bool(self.training)].preprocess_batch(batch_dict["lidar_points"],
+                                                                                          batch_dict["lidar_point_offsets"])
+        return out
 
     def front_end(self, batch_dict, out=None):
         """voxels -> (canvas (B, max_cav, ny, nx, 64) in the compute dtype, cav_mask (B, max_cav) fp32): one operator call"""
-        lidar = batch_dict["processed_lidar"]
+        lidar = self.with_voxels(batch_dict)["processed_lidar"]
         vf, coords, npts = lidar["voxel_features"], lidar["voxel_coords"], lidar["voxel_num_points"]
         self._require_inference(vf, coords, npts)
         rl = torch.as_tensor(batch_dict["record_len"]).to(device=vf.device, dtype=torch.int32)
@@ -53,6 +84,7 @@ class PointPillarFuseBEVT(HipModule):
                                       with_distance=self.pillar_vfe.with_distance, record_len=rl, max_cav=self.max_cav, out=out)
 
     def forward(self, batch_dict):
+        batch_dict = self.with_voxels(batch_dict)
         if self.training and training.lidar_trains(self.pillar_vfe.pfn_layers[0], batch_dict["processed_lidar"]["voxel_features"]):
             return training.point_pillar_fusebevt(self, batch_dict)
         self._require_inference()

@@ -143,6 +143,8 @@ SIGNATURES = {
     "cobevt_pillar_train_stats": (ctypes.c_int, [_vp] * 17 + [_c_int_p, _c_float_p, ctypes.c_int, ctypes.c_float, ctypes.c_float, _vp]),
     "cobevt_pillar_train_bwd": (ctypes.c_int, [_vp] * 16 + [_c_int_p, _c_float_p, ctypes.c_int, _vp]),
     "cobevt_gather_rows": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_long] + [ctypes.c_int] * 4 + [_vp]),
+    "cobevt_voxelize_scratch": (ctypes.c_int, [_c_long_p, _c_long_p]),
+    "cobevt_voxelize_points": (ctypes.c_int, [_vp] * 7 + [_c_long_p, _c_float_p, _vp]),
 }
 
 _libs = {}

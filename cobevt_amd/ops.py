@@ -8,6 +8,7 @@ import ctypes
 import os
 import math
 
+import numpy as np
 import torch
 
 from . import lib as _L
@@ -1195,6 +1196,87 @@ def scatter_rows(rows, voxel_coords, num_agents, grid, out=None):
     rc = _L.load().cobevt_scatter_rows(_p(rows), _p(coords), _p(out), dcode(rows.dtype), p, c, n, ny, nx, _stream())
     _L.check(rc, "cobevt_scatter_rows")
     return out
+
+
+def voxel_grid_size(lidar_range, voxel_size):
+    """(nx, ny, nz) = round((range_hi - range_lo) / voxel_size) in fp32, as spconv's VoxelGenerator forms it"""
+    r = np.asarray(lidar_range, dtype=np.float32).reshape(-1)
+    v = np.asarray(voxel_size, dtype=np.float32).reshape(-1)
+    if r.shape != (6,) or v.shape != (3,) or not bool(np.all(v > 0)) or not bool(np.all(np.isfinite(r))):
+        raise CobevtHipError("voxelize_points: lidar_range = [x0, y0, z0, x1, y1, z1] and voxel_size = [vx, vy, vz] > 0, got %s / %s"
+                             % (list(lidar_range), list(voxel_size)))
+    return tuple(int(g) for g in np.round((r[3:] - r[:3]) / v).astype(np.int64))
+
+
+def voxelize_workspace_ints(num_points, num_agents, grid, max_points, max_voxels):
+    """int32 elements of voxelize_points' workspace for M points of N agents on an (nx, ny, nz) grid (cobevt_voxelize_scratch)"""
+    dims = (ctypes.c_long * 9)(int(num_points), int(num_agents), int(max_points), int(max_voxels), int(grid[0]), int(grid[1]), int(grid[2]), 0, 0)
+    need = ctypes.c_long(0)
+    _L.check(_L.load().cobevt_voxelize_scratch(dims, ctypes.byref(need)), "cobevt_voxelize_scratch")
+    return need.value
+
+
+_VOXEL_WS = {}        # (device, dims) -> the int32 workspace: one buffer per shape, so a captured graph replays on the buffers it saw
+
+
+def voxelize_points(points, point_offsets, lidar_range, voxel_size, max_points=32, max_voxels=None, range_mask=False, ego_mask=False,
+                    out=None, workspace=None):
+    """spconv's points_to_voxel with OpenCOOD's collate (csrc/voxelize.hip), without a host synchronisation.
+    points (M, 4) contiguous fp32 [x, y, z, intensity]: the agents' points concatenated, in the ego frame; point_offsets (N + 1,)
+    int32 on the device (int64: converted on the device): agent a owns rows offsets[a] .. offsets[a + 1], rows at or past offsets[N]
+    are ignored.  Per agent, in input order: points with a non-finite coordinate, outside the optional masks (range_mask:
+    pcd_utils.mask_points_by_range's strict inequalities; ego_mask: pcd_utils.mask_ego_points' box) or with floor((p - lo) / voxel)
+    (fp32, rounded subtract and divide) outside the grid are dropped; the first kept point of a cell opens a voxel, voxels are numbered
+    in order of their first point, at most max_voxels per agent (cells past the cap are dropped with all their points); a voxel keeps the
+    first max_points (<= 32) points of its cell.
+    -> voxel_features (N max_voxels, T, 4) fp32, voxel_coords (N max_voxels, 4) int32 [a, 0, y, x], voxel_num_points (N max_voxels)
+    int32, num_voxels (N,) int32.  Agent a's voxels start at row a * max_voxels.  Rows without a voxel hold voxel_coords [-1, 0, 0, 0]
+    and voxel_num_points 0 - the padding rows pillar_vfe_scatter skips - and their voxel_features are NOT written (they keep what
+    `out=` held, or are uninitialised): clearing them would cost more than the operator.  out = the four tensors to write into;
+    workspace = an int32 tensor of at least voxelize_workspace_ints(...) elements (default: one cached per shape and device).
+    Bitwise reproducible: nothing depends on scheduling."""
+    _need_cuda(points, point_offsets, workspace)
+    if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 4 or not points.is_contiguous():
+        raise CobevtHipError("voxelize_points: points must be contiguous fp32 (M, 4) as [x, y, z, intensity], got %s %s"
+                             % (points.dtype, tuple(points.shape)))
+    offs = _index_i32(point_offsets, "voxelize_points: point_offsets")
+    if offs.dim() != 1 or offs.shape[0] < 2:
+        raise CobevtHipError("voxelize_points: point_offsets must be (N + 1,) with N >= 1 agents, got %s" % (tuple(offs.shape),))
+    if max_voxels is None or int(max_voxels) < 1:
+        raise CobevtHipError("voxelize_points: max_voxels (per agent, >= 1) is required")
+    nx, ny, nz = voxel_grid_size(lidar_range, voxel_size)
+    if nz != 1:
+        raise CobevtHipError("voxelize_points: the pillar front end implements nz = 1 (one voxel over the height), got grid (%d, %d, %d)"
+                             % (nx, ny, nz))
+    t, n, m, mv = int(max_points), offs.shape[0] - 1, points.shape[0], int(max_voxels)
+    if t < 1 or t > PILLAR_MAX_POINTS:
+        raise CobevtHipError("voxelize_points: 1 <= max_points <= T = %d points per voxel are supported, got %d" % (PILLAR_MAX_POINTS, t))
+    if nx < 1 or ny < 1:
+        raise CobevtHipError("voxelize_points: empty grid (%d, %d, %d)" % (nx, ny, nz))
+    dev, pcap = points.device, n * mv
+    dims = (ctypes.c_long * 9)(m, n, t, mv, nx, ny, nz, int(bool(range_mask)), int(bool(ego_mask)))
+    geom = (ctypes.c_float * 9)(*[float(v) for v in list(lidar_range) + list(voxel_size)])
+    lib = _L.load()
+    if workspace is None:
+        key = (dev, m, n, t, mv, nx, ny)
+        workspace = _VOXEL_WS.get(key)
+        if workspace is None:
+            workspace = _VOXEL_WS[key] = torch.empty(voxelize_workspace_ints(m, n, (nx, ny, nz), t, mv), device=dev, dtype=torch.int32)
+    else:
+        need = voxelize_workspace_ints(m, n, (nx, ny, nz), t, mv)
+        if workspace.dtype != torch.int32 or not workspace.is_contiguous() or workspace.numel() < need or workspace.device != dev:
+            raise CobevtHipError("voxelize_points: workspace= must be a contiguous int32 tensor of at least %d elements on %s" % (need, dev))
+    shapes = [((pcap, t, 4), torch.float32), ((pcap, 4), torch.int32), ((pcap,), torch.int32), ((n,), torch.int32)]
+    if out is None:
+        out = [None] * 4
+    elif len(out) != 4:
+        raise CobevtHipError("voxelize_points: out= is (voxel_features, voxel_coords, voxel_num_points, num_voxels)")
+    vf, coords, npts, nvox = [_canvas(o, s, d, dev, "voxelize_points") for o, (s, d) in zip(out, shapes)]
+    cost = lambda: (0.0, 32.0 * m + 16.0 * m + 16.0 * (n * ny * nx) + 24.0 * pcap)         # noqa: E731
+    with _timed("voxelize|M%d N%d T%d %dx%d" % (m, n, t, ny, nx), cost):
+        rc = lib.cobevt_voxelize_points(_p(points), _p(offs), _p(vf), _p(coords), _p(npts), _p(nvox), _p(workspace), dims, geom, _stream())
+    _L.check(rc, "cobevt_voxelize_points")
+    return vf, coords, npts, nvox
 
 
 def sttf_warp(x, tmat, cav_mask, discrete_ratio, downsample_rate, want_mask=True, record_len=None, max_cav=None):

@@ -800,6 +800,30 @@ int cobevt_pillar_train_bwd(const float* voxel_features, const int* voxel_num_po
 int cobevt_gather_rows(const void* canvas, const int* voxel_coords, void* rows, int dtype, long P, int C, int N, int ny, int nx,
                        hipStream_t stream);
 
+/*
+ * Voxelisation of raw LiDAR points (csrc/voxelize.hip): spconv's points_to_voxel with OpenCOOD's collate, producing the voxel dict
+ * cobevt_pillar_vfe reads.  fp32 / int32 only, identical in every library.
+ *   points (M, 4) fp32 [x, y, z, intensity], the agents' points concatenated; point_offsets (N + 1) int32 ON THE DEVICE: agent a
+ *   owns rows offsets[a] .. offsets[a + 1], rows at or past offsets[N] are ignored (M can stay fixed under graph replay);
+ *   dims  = [M, N, T, max_voxels, nx, ny, nz, range_mask, ego_mask] (host), T in 1 .. 32, nz = 1, max_voxels per agent;
+ *   geom  = [x0, y0, z0, x1, y1, z1, voxel x, y, z] (host).
+ * Per agent, in input order: a point is dropped when a coordinate is not finite, when range_mask is set and the strict inequalities
+ * of pcd_utils.mask_points_by_range fail, when ego_mask is set and it lies in the box of pcd_utils.mask_ego_points, or when
+ * floor((p - lo) / voxel) (fp32, correctly rounded subtract and divide) is outside the grid on any axis.  The first kept point of a
+ * cell opens a voxel; voxels are numbered in order of their first point; once an agent has max_voxels, cells that would open
+ * another are dropped with all their points while open cells keep accepting points.  A voxel keeps the first T points of its cell.
+ * Outputs, Pcap = N * max_voxels rows, agent a's voxels from row a * max_voxels: voxel_features (Pcap, T, 4) - slots past the
+ * point count zero; voxel_coords (Pcap, 4) = [a, 0, y, x]; voxel_num_points (Pcap); num_voxels (N).  Rows without a voxel get
+ * voxel_coords [-1, 0, 0, 0] and voxel_num_points 0 (the padding rows cobevt_pillar_vfe skips); their voxel_features are NOT
+ * written.  Seven launches, integer atomics only, no workgroup waits on another, no host read, no allocation; the result does not
+ * depend on scheduling (bitwise reproducible).  workspace: cobevt_voxelize_scratch(dims) ints, contents irrelevant on entry.
+ * points, voxel_features and voxel_coords must be 16-byte aligned.
+ */
+int cobevt_voxelize_scratch(const long* dims, long* workspace_ints);
+int cobevt_voxelize_points(const float* points, const int* point_offsets, float* voxel_features, int* voxel_coords,
+                           int* voxel_num_points, int* num_voxels, int* workspace, const long* dims, const float* geom,
+                           hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
