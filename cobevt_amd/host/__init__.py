@@ -27,6 +27,9 @@ from .point_pillar_fusebevt import PointPillarFuseBEVT  # noqa: F401
 from .pipeline import CapturedCall, CapturedCorpBEVT, HostFrameFeeder, PipelinedCorpBEVT  # noqa: F401
 # the data formats either side of the path
 from .camera_bev_postprocessor import CameraBevPostprocessor  # noqa: F401
+from .voxel_postprocessor import VoxelPostprocessor  # noqa: F401
+from . import eval_utils  # noqa: F401
+from .eval_utils import calculate_ap, caluclate_tp_fp, eval_final_results, voc_ap  # noqa: F401
 from .rgb_preprocessor import RgbPreProcessor  # noqa: F401
 from .intermediate_fusion_dataset import collate_batch  # noqa: F401
 from .train_utils import load_saved_model  # noqa: F401

@@ -14,8 +14,14 @@ forward(batch_dict): batch_dict['processed_lidar'] = {voxel_features (P, T <= 32
 voxel_num_points (P,)} and batch_dict['record_len'] (B,) -> {'fused_feature': (B, 64, ny, nx)} fp32.  The front end is ONE operator
 call (two launches) from the voxels straight into the (B, max_cav, ny, nx, 64) canvas FuseBEVT reads; rows whose batch index is
 negative are skipped, which is how a caller pads P to a fixed size for graph replay.  In train() mode the forward is the differentiable
-graph of host/training.point_pillar_fusebevt (batch statistics over the pillars the operator writes; parameter gradients)."""
+graph of host/training.point_pillar_fusebevt (batch statistics over the pillars the operator writes; parameter gradients).
+
+Optional args['anchor_number'] = A adds the detection head OpenCOOD's PointPillar models carry: cls_head (64 -> A, 1 x 1, bias) and
+reg_head (64 -> 7A), and the forward adds 'psm' (B, A, ny, nx) and 'rm' (B, 7A, ny, nx) in fp32 - both from ONE dense product of the
+concatenated weights over the fused rows (ops.linear) - for host.VoxelPostprocessor.post_process.  Inference only: the reference has
+no detection loss, so train() with the argument set raises.  Without the argument the state_dict and the outputs are unchanged."""
 import torch
+import torch.nn as nn
 
 from .. import ops
 from ..lib import CobevtHipError
@@ -48,6 +54,13 @@ class PointPillarFuseBEVT(HipModule):
                                  "PFN layer's %d channels" % c)
         if self.max_cav < 1:
             raise CobevtHipError("PointPillarFuseBEVT: max_cav must be at least 1")
+        self.anchor_number = args.get("anchor_number")
+        if self.anchor_number is not None:
+            if int(self.anchor_number) < 1:
+                raise CobevtHipError("PointPillarFuseBEVT: anchor_number must be at least 1, got %r" % (self.anchor_number,))
+            self.anchor_number = int(self.anchor_number)
+            self.cls_head = nn.Conv2d(c, self.anchor_number, kernel_size=1)
+            self.reg_head = nn.Conv2d(c, 7 * self.anchor_number, kernel_size=1)
         # plain objects without parameters: the state_dict is the same with and without `preprocess`
         self.preprocessors = None
         if pre is not None:
@@ -83,7 +96,19 @@ class PointPillarFuseBEVT(HipModule):
                                       rt.get_compute_dtype(), use_absolute_xyz=self.pillar_vfe.use_absolute_xyz,
                                       with_distance=self.pillar_vfe.with_distance, record_len=rl, max_cav=self.max_cav, out=out)
 
+    def _head_plan(self):
+        """cls_head and reg_head as one (8A, 64) dense layer"""
+        tensors = [self.cls_head.weight, self.cls_head.bias, self.reg_head.weight, self.reg_head.bias]
+
+        def build(dt, dev):
+            w = torch.cat([self.cls_head.weight.detach().flatten(1), self.reg_head.weight.detach().flatten(1)])
+            return ops.ConvPlan(w, torch.cat([self.cls_head.bias.detach(), self.reg_head.bias.detach()]), dtype=dt, device=dev)
+        return self._plan("det_head", tensors, build)
+
     def forward(self, batch_dict):
+        if self.training and self.anchor_number is not None:
+            raise CobevtHipError("PointPillarFuseBEVT: the detection head (args['anchor_number']) is inference only - the reference has no "
+                                 "detection loss to train it with; call .eval(), or build the model without anchor_number to train")
         batch_dict = self.with_voxels(batch_dict)
         if self.training and training.lidar_trains(self.pillar_vfe.pfn_layers[0], batch_dict["processed_lidar"]["voxel_features"]):
             return training.point_pillar_fusebevt(self, batch_dict)
@@ -93,4 +118,10 @@ class PointPillarFuseBEVT(HipModule):
         # the agent mask as CorpBEVT.fuse_and_decode builds it without an ROI mask (corpbevt.py:125-128)
         com_mask = cav_mask[:, None, None, None, :].expand(b, h, w, 1, l).contiguous()
         fused = self.fusion_net.forward_blhwc(x, com_mask)                      # (B, ny, nx, 64)
-        return {"fused_feature": rt.nchw_view(fused).float()}
+        out = {"fused_feature": rt.nchw_view(fused).float()}
+        if self.anchor_number is not None:
+            a = self.anchor_number
+            maps = rt.nchw_view(ops.linear(fused, self._head_plan())).float()   # (B, 8A, ny, nx): A class maps, then 7A deltas
+            out["psm"] = maps[:, :a].contiguous()
+            out["rm"] = maps[:, a:].contiguous()
+        return out

@@ -1279,6 +1279,167 @@ def voxelize_points(points, point_offsets, lidar_range, voxel_size, max_points=3
     return vf, coords, npts, nvox
 
 
+DETECT_TOP = 1000          # box_utils.nms_rotated's `top`: the fixed capacity of the detection outputs
+DETECT_MAX_CAV = 16
+_DETECT_WS = {}            # (device, total anchors) -> the workspace: one buffer per size, so a captured graph replays on the buffer it saw
+
+
+def detect_workspace_bytes(total_anchors):
+    """bytes of detect_post_process' / nms_rotated's workspace for `total_anchors` candidates (cobevt_detect_scratch)"""
+    need = ctypes.c_long(0)
+    _L.check(_L.load().cobevt_detect_scratch(int(total_anchors), ctypes.byref(need)), "cobevt_detect_scratch")
+    return need.value
+
+
+def _detect_workspace(workspace, total, dev, what):
+    need = detect_workspace_bytes(total)
+    if workspace is None:
+        workspace = _DETECT_WS.get((dev, total))
+        if workspace is None:
+            workspace = _DETECT_WS[(dev, total)] = torch.empty((need + 7) // 8, device=dev, dtype=torch.int64)
+        return workspace
+    if workspace.dtype != torch.int64 or not workspace.is_contiguous() or workspace.numel() * 8 < need or workspace.device != dev:
+        raise CobevtHipError("%s: workspace= must be a contiguous int64 tensor of at least %d elements on %s" % (what, (need + 7) // 8, dev))
+    return workspace
+
+
+def _detect_out(out, dev, what):
+    shapes = [((DETECT_TOP, 8, 3), torch.float32), ((DETECT_TOP,), torch.float32), ((DETECT_TOP,), torch.int32), ((1,), torch.int32)]
+    if out is None:
+        out = [None] * 4
+    elif len(out) != 4:
+        raise CobevtHipError("%s: out= is (boxes, scores, index, count)" % what)
+    return [_canvas(o, sh, d, dev, what) for o, (sh, d) in zip(out, shapes)]
+
+
+def _f32_dev(t, dev, what, shape=None):
+    """a contiguous fp32 tensor on `dev` from a tensor or an array (an anchor box is numpy float64 in the reference)"""
+    t = torch.as_tensor(t)
+    if not t.is_floating_point():
+        raise CobevtHipError("%s must be floating point, got %s" % (what, t.dtype))
+    t = t.to(device=dev, dtype=torch.float32).contiguous()
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise CobevtHipError("%s must have shape %s, got %s" % (what, tuple(shape), tuple(t.shape)))
+    return t
+
+
+def _head_maps(psm, rm, anchors, what, batch=None):
+    """checks of one sample's head maps -> (N, H, W, A); psm may be None"""
+    if rm.dtype != torch.float32 or rm.dim() != 4 or not rm.is_contiguous():
+        raise CobevtHipError("%s: rm must be contiguous fp32 (N, 7A, H, W), got %s %s" % (what, rm.dtype, tuple(rm.shape)))
+    n, c7, h, w = rm.shape
+    if tuple(anchors.shape[:2]) != (h, w) or anchors.dim() != 4 or anchors.shape[3] != 7 or anchors.shape[2] * 7 != c7 or c7 == 0:
+        raise CobevtHipError("%s: anchors must be (H, W, A, 7) with rm (N, 7A, H, W), got %s and %s"
+                             % (what, tuple(anchors.shape), tuple(rm.shape)))
+    a = anchors.shape[2]
+    if n < 1 or h < 1 or w < 1 or (batch is not None and n != batch):
+        raise CobevtHipError("%s: batch size %s expected, got rm %s" % (what, ">= 1" if batch is None else batch, tuple(rm.shape)))
+    if psm is not None and (psm.dtype != torch.float32 or tuple(psm.shape) != (n, a, h, w) or not psm.is_contiguous()):
+        raise CobevtHipError("%s: psm must be contiguous fp32 %s, got %s %s" % (what, (n, a, h, w), psm.dtype, tuple(psm.shape)))
+    return n, h, w, a
+
+
+def delta_to_boxes3d(deltas, anchors):
+    """VoxelPostprocessor.delta_to_boxes3d (csrc/detect_post.hip): deltas = the regression map (N, 7A, H, W) contiguous fp32 on the
+    device, channel a * 7 + k = delta k of anchor a; anchors (H, W, A, 7) (tensor or array, any float type) -> boxes3d (N, H W A, 7)
+    fp32 in (h, w, a) order: x, y = delta * sqrt(a4^2 + a5^2) + anchor, z = delta * a3 + anchor, sizes exp(delta) * anchor, yaw added."""
+    _need_cuda(deltas)
+    anc = _f32_dev(anchors, deltas.device, "delta_to_boxes3d: anchors")
+    n, h, w, a = _head_maps(None, deltas, anc, "delta_to_boxes3d")
+    out = torch.empty((n, h * w * a, 7), device=deltas.device, dtype=torch.float32)
+    _L.check(_L.load().cobevt_delta_to_boxes3d(_p(deltas), _p(anc), _p(out), n, h, w, a, _stream()), "cobevt_delta_to_boxes3d")
+    return out
+
+
+def _quads(boxes, dev, what):
+    """(N, 8, 3) or (N, 4, 2) -> contiguous fp32 (N, 4, 2): corners 0 .. 3 in xy, the polygon common_utils.convert_format builds"""
+    b = torch.as_tensor(boxes)
+    if b.dim() != 3 or tuple(b.shape[1:]) not in ((8, 3), (4, 2)) or not b.is_floating_point():
+        raise CobevtHipError("%s must be floating point (N, 8, 3) or (N, 4, 2), got %s %s" % (what, b.dtype, tuple(b.shape)))
+    return b[:, :4, :2].to(device=dev, dtype=torch.float32).contiguous()
+
+
+def rotated_iou(a, b):
+    """Pairwise IoU of convex quads: a (N, 4, 2) / (N, 8, 3), b (M, 4, 2) / (M, 8, 3) on the device (corners 0 .. 3 in xy, either
+    winding) -> (N, M) fp64.  The fp32 corners are clipped in fp64 by the device function the NMS mask uses; a pair whose union has no
+    area gives 0."""
+    _need_cuda(a, b)
+    qa = _quads(a, a.device, "rotated_iou: a")
+    qb = _quads(b, a.device, "rotated_iou: b")
+    out = torch.empty((qa.shape[0], qb.shape[0]), device=a.device, dtype=torch.float64)
+    _L.check(_L.load().cobevt_rotated_iou(_p(qa), _p(qb), _p(out), qa.shape[0], qb.shape[0], _stream()), "cobevt_rotated_iou")
+    return out
+
+
+def nms_rotated_device(boxes, scores, threshold, out=None, workspace=None):
+    """box_utils.nms_rotated without a host read: boxes (N, 8, 3) or (N, 4, 2) and scores (N) on the device -> the fixed-capacity
+    (boxes (1000, 8, 3), scores (1000), index (1000) int32 = kept input rows in pick order, count (1) int32); rows past count zero."""
+    _need_cuda(boxes, scores, workspace)
+    if boxes.dim() != 3 or tuple(boxes.shape[1:]) not in ((8, 3), (4, 2)) or not boxes.is_floating_point():
+        raise CobevtHipError("nms_rotated: boxes must be floating point (N, 8, 3) or (N, 4, 2), got %s %s" % (boxes.dtype, tuple(boxes.shape)))
+    dev, n = boxes.device, boxes.shape[0]
+    b = boxes.to(torch.float32).contiguous()
+    sc = _f32_dev(scores, dev, "nms_rotated: scores", (n,))
+    ws = _detect_workspace(workspace, n, dev, "nms_rotated")
+    ob, osc, oi, oc = _detect_out(out, dev, "nms_rotated")
+    rc = _L.load().cobevt_nms_rotated(_p(b) if n else None, _p(sc) if n else None, n, b.shape[1] * b.shape[2], float(threshold), _p(ob),
+                                      _p(osc), _p(oi), _p(oc), _p(ws), _stream())
+    _L.check(rc, "cobevt_nms_rotated")
+    return ob, osc, oi, oc
+
+
+def nms_rotated(boxes, scores, threshold):
+    """box_utils.nms_rotated: rotated NMS over the 1000 best-scored of N boxes (N, 8, 3) or (N, 4, 2) on the device -> int32 indices
+    of the kept boxes, best score first (equal scores: lower index first).  Reads the count back once (one synchronisation);
+    nms_rotated_device does not."""
+    _, _, index, count = nms_rotated_device(boxes, scores, threshold)
+    return index[:int(count.item())].clone()
+
+
+def detect_post_process(cavs, score_threshold, nms_thresh, order, out=None, workspace=None):
+    """VoxelPostprocessor.post_process on the device, without a synchronisation (csrc/detect_post.hip).
+    cavs: a sequence of 1 .. 16 (psm, rm, anchors, transformation_matrix): psm (1, A, H, W) and rm (1, 7A, H, W) contiguous fp32 on
+    the device, anchors (H, W, A, 7) and the 4 x 4 matrix tensors or arrays (converted to fp32 on the device; give device tensors to
+    capture the call in a graph).  order: the box order ('hwl' reads the size columns as [5, 4, 3], any other as they stand).
+    -> boxes (1000, 8, 3) fp32, scores (1000) fp32, index (1000) int32 (global anchor index: cav 0's anchors in (h, w, a) order, then
+    cav 1's, ...), count (1) int32, in pick order; rows at and past count are zero.  Survivors of score > score_threshold and the
+    reference's box filters, the 1000 best of all cavs, rotated NMS (iou > nms_thresh), then the GT_RANGE mask - see cobevt_hip.h.
+    out = the four tensors to write into; workspace = an int64 tensor of detect_workspace_bytes(total anchors) bytes."""
+    cavs = list(cavs)
+    if not 1 <= len(cavs) <= DETECT_MAX_CAV:
+        raise CobevtHipError("detect_post_process: 1 .. %d cavs are supported, got %d" % (DETECT_MAX_CAV, len(cavs)))
+    if not isinstance(order, str):
+        raise CobevtHipError("detect_post_process: order must be a string such as 'hwl' or 'lhw', got %r" % (order,))
+    keep, dims, mats, total = [], [], [], 0
+    dev = None
+    for c, cav in enumerate(cavs):
+        if len(cav) != 4:
+            raise CobevtHipError("detect_post_process: cav %d must be (psm, rm, anchors, transformation_matrix)" % c)
+        psm, rm, anchors, mat = cav
+        _need_cuda(psm, rm)
+        dev = psm.device if dev is None else dev
+        if psm.device != dev or rm.device != dev:
+            raise CobevtHipError("detect_post_process: cav %d is on another device" % c)
+        anc = _f32_dev(anchors, dev, "detect_post_process: anchors of cav %d" % c)
+        _, h, w, a = _head_maps(psm, rm, anc, "detect_post_process: cav %d" % c, batch=1)
+        mats.append(_f32_dev(mat, dev, "detect_post_process: transformation_matrix of cav %d" % c, (4, 4)))
+        keep.append((psm, rm, anc))
+        dims += [h, w, a]
+        total += h * w * a
+    if total > 0x7fffffff // 8:
+        raise CobevtHipError("detect_post_process: %d anchors are more than the operator indexes" % total)
+    matrices = mats[0].reshape(1, 4, 4) if len(mats) == 1 else torch.stack(mats)
+    ws = _detect_workspace(workspace, total, dev, "detect_post_process")
+    ob, osc, oi, oc = _detect_out(out, dev, "detect_post_process")
+    ptrs = [(ctypes.c_void_p * len(cavs))(*[k[j].data_ptr() for k in keep]) for j in range(3)]
+    cost = lambda: (0.0, 36.0 * total + 8.0 * DETECT_TOP * 16 + 200.0 * DETECT_TOP)         # noqa: E731
+    with _timed("detect_post|cavs%d N%d" % (len(cavs), total), cost):
+        rc = _L.load().cobevt_detect_post(ptrs[0], ptrs[1], ptrs[2], _p(matrices), _ints(dims), len(cavs), int(order == "hwl"),
+                                          float(score_threshold), float(nms_thresh), _p(ob), _p(osc), _p(oi), _p(oc), _p(ws), _stream())
+    _L.check(rc, "cobevt_detect_post")
+    return ob, osc, oi, oc
+
+
 def sttf_warp(x, tmat, cav_mask, discrete_ratio, downsample_rate, want_mask=True, record_len=None, max_cav=None):
     """x: (B, L, H, W, C) contiguous ; tmat (B, L, 4, 4) fp32 -> warped (B,L,H,W,C), com_mask (B,H,W,1,L)|None.
     With record_len (int32 device (B,)) x is the un-grouped agent batch (N, H, W, C): regroup + warp in one launch,

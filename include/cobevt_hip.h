@@ -824,6 +824,44 @@ int cobevt_voxelize_points(const float* points, const int* point_offsets, float*
                            int* voxel_num_points, int* num_voxels, int* workspace, const long* dims, const float* geom,
                            hipStream_t stream);
 
+/*
+ * LiDAR detection output (csrc/detect_post.hip): OpenCOOD's VoxelPostprocessor.post_process - box decode, box filters, the cut at
+ * the 1000 best-scored candidates, rotated NMS, range mask - and its pieces.  fp32 / int32 data, fp64 only inside the quad clip;
+ * identical in every library.
+ *
+ * cobevt_detect_post: ncav in 1 .. 16 agents ("cavs").  psm, rm, anchors: HOST arrays of ncav DEVICE pointers - cav c's psm
+ *   (1, A, H, W) and rm (1, 7A, H, W) in NCHW fp32 (channel a * 7 + k of rm = delta k of anchor a) and anchors (H, W, A, 7) fp32;
+ *   matrices (ncav, 4, 4) fp32 ON THE DEVICE; cav_dims = [H, W, A] per cav (host); hwl != 0: the box order 'hwl' (size columns read
+ *   as [5, 4, 3]), otherwise as they stand.  The global anchor index counts cav 0's anchors in (h, w, a) order, then cav 1's, ...
+ *   score = sigmoid(psm); box = delta_to_boxes3d (x, y scaled by the anchor diagonal sqrt(a4^2 + a5^2), z by a3, exp on the sizes,
+ *   yaw added); corners as boxes_to_corners_3d, projected by the cav's matrix.  A candidate survives when score > score_threshold,
+ *   x extent <= 6, y extent <= 6, y extent != 0 (the reference's z_len is computed from the y column and used as a truth value),
+ *   min z >= -3, max z <= 1 and every coordinate is finite.  The 1000 best-scored survivors of all cavs (no cap before that cut;
+ *   equal scores: lower global index first) go through greedy NMS on the IoU of corners 0 .. 3 in xy (fp64 clip of the fp32 corners,
+ *   suppressed when (float)iou > nms_thresh); picked boxes with all 8 corners in x [-140, 140], y [-40, 40] are written in pick
+ *   order: boxes (1000, 8, 3), scores (1000), index (1000) = global anchor index, count (1).  Rows at and past count are zero.
+ *   One 8-byte memset node and four launches (decode, select + sort, mask, greedy), integer atomics only, no workgroup waits on
+ *   another, no host read, no allocation, bitwise reproducible.  workspace: cobevt_detect_scratch(total anchors) BYTES, 8-byte
+ *   aligned, contents irrelevant on entry.  Skip rules: none - every anchor of every cav is decoded.
+ *
+ * cobevt_nms_rotated: the same selection, mask and greedy pass on N given boxes - box_corners (N, 8, 3) (corner_floats = 24) or
+ *   (N, 4, 2) (corner_floats = 8, written back as corners 0 .. 3 with z = 0) and box_scores (N), any sign - without filters and
+ *   without the range mask: box_utils.nms_rotated.  index = the kept boxes' input rows in pick order.  workspace:
+ *   cobevt_detect_scratch(N).  N = 0 gives count 0.
+ *
+ * cobevt_delta_to_boxes3d: rm (N, 7A, H, W), anchors (H, W, A, 7) -> boxes3d (N, H W A, 7), N >= 1.  One launch.
+ * cobevt_rotated_iou: a (N, 4, 2), b (M, 4, 2) fp32 -> iou (N, M) fp64 by the same device function (either winding; a pair whose
+ *   union has no area gives 0).  One launch; N = 0 or M = 0 launches nothing.
+ */
+int cobevt_detect_scratch(long total_anchors, long* workspace_bytes);
+int cobevt_detect_post(const float* const* psm, const float* const* rm, const float* const* anchors, const float* matrices,
+                       const int* cav_dims, int ncav, int hwl, float score_threshold, float nms_thresh, float* boxes, float* scores,
+                       int* index, int* count, void* workspace, hipStream_t stream);
+int cobevt_nms_rotated(const float* box_corners, const float* box_scores, long N, int corner_floats, float nms_thresh, float* boxes,
+                       float* scores, int* index, int* count, void* workspace, hipStream_t stream);
+int cobevt_delta_to_boxes3d(const float* rm, const float* anchors, float* boxes3d, int N, int H, int W, int A, hipStream_t stream);
+int cobevt_rotated_iou(const float* a, const float* b, double* iou, long N, long M, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
