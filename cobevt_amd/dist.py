@@ -199,10 +199,9 @@ class DirectExchange(object):
             raise ValueError("DirectExchange: a block must be a multiple of 16 bytes")
         self.window_bytes = self.block_bytes * self.blocks
         self.spin_limit = int(spin_limit)
-        lib = _L.load()
         ptr, handle = ctypes.c_void_p(), ctypes.create_string_buffer(64)
         with torch.cuda.device(self.device):
-            _L.check(lib.cobevt_peer_window_alloc(self.window_bytes, ctypes.byref(ptr), handle), "cobevt_peer_window_alloc")
+            _L.call("cobevt_peer_window_alloc", self.window_bytes, ctypes.byref(ptr), handle)
         self._own = ptr.value
         handles = [None] * self.world
         if self.world > 1:
@@ -217,8 +216,10 @@ class DirectExchange(object):
                 continue
             q = ctypes.c_void_p()
             with torch.cuda.device(self.device):
-                _L.check(lib.cobevt_peer_window_open(ctypes.create_string_buffer(raw, 64), ctypes.byref(q)),
-                         "cobevt_peer_window_open (rank %d's window)" % r)
+                try:
+                    _L.call("cobevt_peer_window_open", ctypes.create_string_buffer(raw, 64), ctypes.byref(q))
+                except _L.CobevtHipError as e:
+                    raise _L.CobevtHipError("%s (rank %d's window)" % (e, r)) from None
             ptrs[r] = q.value
             self._mapped.append(q.value)
         self._ptrs = ptrs
@@ -243,20 +244,17 @@ class DirectExchange(object):
         if n:
             if not local.is_cuda or not local.is_contiguous() or local.dtype != self.dtype or local.shape[0] < n:
                 raise ValueError("DirectExchange: local blocks must be a contiguous device tensor of the window's dtype")
-        lib = self._L.load()
         stream = self._ct.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        self._L.check(lib.cobevt_peer_exchange(self._ct.c_void_p(local.data_ptr()) if n else None, self._ptrs, self.world,
-                                               self.rank, n, self.block_bytes, self._dest_rank, self._dest_block,
-                                               self.window_bytes, self.spin_limit, stream), "cobevt_peer_exchange")
+        self._L.call("cobevt_peer_exchange", self._ct.c_void_p(local.data_ptr()) if n else None, self._ptrs, self.world, self.rank, n,
+                     self.block_bytes, self._dest_rank, self._dest_block, self.window_bytes, self.spin_limit, stream)
         return self.window
 
     def status(self):
         """(status, completed exchanges) after synchronising the current stream; status != 0: a bounded wait gave up"""
         st, ep = self._ct.c_int(), self._ct.c_int()
         stream = self._ct.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        self._L.check(self._L.load().cobevt_peer_window_status(self._ct.c_void_p(self._own), self.window_bytes,
-                                                               self._ct.byref(st), self._ct.byref(ep), stream),
-                      "cobevt_peer_window_status")
+        self._L.call("cobevt_peer_window_status", self._ct.c_void_p(self._own), self.window_bytes, self._ct.byref(st), self._ct.byref(ep),
+                     stream)
         return st.value, ep.value
 
     _st_host = None
@@ -271,9 +269,8 @@ class DirectExchange(object):
         if self._st_ev[j] is not None and not self._st_ev[j].query():
             return                                     # four reads already in flight: the oldest will report
         stream = self._ct.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        self._L.check(self._L.load().cobevt_peer_window_status_async(self._ct.c_void_p(self._own), self.window_bytes,
-                                                                     self._ct.c_void_p(self._st_host[j].data_ptr()), stream),
-                      "cobevt_peer_window_status_async")
+        self._L.call("cobevt_peer_window_status_async", self._ct.c_void_p(self._own), self.window_bytes,
+                     self._ct.c_void_p(self._st_host[j].data_ptr()), stream)
         ev = torch.cuda.Event()
         ev.record()
         self._st_ev[j] = ev

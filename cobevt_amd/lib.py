@@ -162,6 +162,7 @@ _libs = {}
 # switches to for the launches issued inside it (host/resnet_ms.py).
 _variant = ""
 _encoder_variant = None
+_encoder_depth = 0      # nesting depth of encoder_scope()
 VARIANTS = ("", "f32s", "f32h")
 LIB_PATH_F32S = os.environ.get("COBEVT_HIP_LIB_F32S") or os.path.join(_HERE, "csrc", "libcobevt_hip_f32s.so")
 LIB_PATH_F32H = os.environ.get("COBEVT_HIP_LIB_F32H") or os.path.join(_HERE, "csrc", "libcobevt_hip_f32h.so")
@@ -179,7 +180,8 @@ def set_variant(variant):
 
 
 def get_variant():
-    return _variant
+    """The active library: the encoder's variant inside an encoder_scope() when one is set, else the selected one."""
+    return _encoder_variant if (_encoder_depth > 0 and _encoder_variant is not None) else _variant
 
 
 def set_encoder_variant(variant):
@@ -195,24 +197,23 @@ def get_encoder_variant():
 
 
 class encoder_scope(object):
-    """with lib.encoder_scope(): ...  - launches issued inside go to the encoder's library variant, when one is set."""
+    """with lib.encoder_scope(): ...  - launches issued inside go to the encoder's library variant, when one is set.
+    The scope only counts its depth, so a set_variant / set_encoder_variant made inside it takes effect and outlives it."""
 
     def __enter__(self):
-        global _variant
-        self.prev = _variant
-        if _encoder_variant is not None:
-            _variant = _encoder_variant
+        global _encoder_depth
+        _encoder_depth += 1
         return self
 
     def __exit__(self, *exc):
-        global _variant
-        _variant = self.prev
+        global _encoder_depth
+        _encoder_depth -= 1
         return False
 
 
 def load(variant=None):
     """Load (once per variant) and return the ctypes handle of the active library; raises if the HIP extension has not been built."""
-    v = _variant if variant is None else variant
+    v = get_variant() if variant is None else variant
     lib = _libs.get(v)
     if lib is not None:
         return lib
@@ -236,3 +237,8 @@ def check(rc, what):
     if rc != 0:
         msg = load().cobevt_strerror(rc).decode()
         raise CobevtHipError("%s failed: %s (code %d)" % (what, msg, rc))
+
+
+def call(name, *args, variant=None):
+    """Launch the C-ABI entry point `name` of the active library (or of `variant`); a non-zero status raises CobevtHipError."""
+    check(getattr(load(variant), name)(*args), name)

@@ -66,6 +66,10 @@ ATTN_KSPLIT = 2     # streaming attention on a small grid with >= 1024 keys (FAX
                     # 2.037 ms (profiles/r05_ab_same_job.txt); parity-tested (tests/test_kernels_gpu.py::test_attention_key_split_matches_single_pass)
 ATTN_QSPLIT = 0     # 0 = automatic query split of the resident attention kernel; > 0 pins it (tools/attn_probe.py)
 
+# the integer knobs above (everything else COBEVT_FLAGS accepts is a USE_* boolean)
+INT_KNOBS = ("CONV3_VARIANT", "BASICBLOCK_TILE_ROWS", "ROW_CHAIN_ROWS", "GEMM_ROWS3_MIN_M", "GEMM_ROWS3_MAX_K", "GEMM_ROWS3_STRIDED",
+             "GEMM_ROWS3_ROWS64_MIN_M", "BASICBLOCK_MAX_C", "ATTN_VARIANT", "ATTN_QSPLIT", "ATTN_KSPLIT")
+
 
 def dcode(dtype):
     if dtype == torch.bfloat16:
@@ -81,7 +85,7 @@ def _apply_env_flags():
         if "=" in item:
             k, v = item.split("=", 1)
             k = k.strip()
-            if k not in globals() or not (k.startswith("USE_") or k in ("CONV3_VARIANT", "BASICBLOCK_TILE_ROWS", "ROW_CHAIN_ROWS", "GEMM_ROWS3_MIN_M", "GEMM_ROWS3_MAX_K", "GEMM_ROWS3_STRIDED", "GEMM_ROWS3_ROWS64_MIN_M", "BASICBLOCK_MAX_C", "ATTN_VARIANT", "ATTN_QSPLIT", "ATTN_KSPLIT")):
+            if k not in globals() or not (k.startswith("USE_") or k in INT_KNOBS):
                 raise CobevtHipError("COBEVT_FLAGS: unknown switch %r" % k)
             globals()[k] = int(v) if not k.startswith("USE_") else bool(int(v))
 
@@ -424,15 +428,13 @@ def conv2d(x, plan, residual=None, out=None):
 
     if plan.wgt_head is not None and USE_HEAD_CONV and residual is None and (out_h, out_w) == (ho, wo):
         with _timed("head3x3|%d->%d %dx%dx%d" % (cin, plan.cout, n, ho, wo), cost):
-            rc = _L.load().cobevt_conv3x3_head_nchw(_p(x), _p(plan.wgt_head), _p(plan.bias), _p(out), plan.code, n, h, w, cin, plan.cout,
-                                                    _stream())
-        _L.check(rc, "cobevt_conv3x3_head_nchw")
+            _L.call("cobevt_conv3x3_head_nchw", _p(x), _p(plan.wgt_head), _p(plan.bias), _p(out), plan.code, n, h, w, cin, plan.cout,
+                    _stream())
         return out
     if plan.wgt_stem is not None and USE_STEM and h % 2 == 0 and w % 2 == 0 and residual is None and (out_h, out_w) == (ho, wo):
         sdims = _ints([plan.code, n, h, w, plan.cout, plan.act])
         with _timed("stem7x7|%dx%dx%d" % (n, h, w), cost):
-            rc = _L.load().cobevt_stem_conv7x7s2(_p(x), _p(plan.wgt_stem), _p(plan.bias), _p(out), sdims, _stream())
-        _L.check(rc, "cobevt_stem_conv7x7s2")
+            _L.call("cobevt_stem_conv7x7s2", _p(x), _p(plan.wgt_stem), _p(plan.bias), _p(out), sdims, _stream())
         return out
     if plan.wgt_rows is not None and USE_GEMM_ROWS and not (residual is not None and (out_h, out_w) != (ho, wo)):
         ldims = (ctypes.c_long * 16)(plan.code, n * ho * wo, plan.cout, plan.K, plan.kp_rows, cin, plan.pre_relu, plan.act,
@@ -454,21 +456,17 @@ def conv2d(x, plan, residual=None, out=None):
                                       64 if (GEMM_ROWS3_ROWS64_MIN_M and n * ho * wo >= GEMM_ROWS3_ROWS64_MIN_M) else 32)
             with _timed("gemm_rows|%d->%d M=%d%s%s r32" % (cin, plan.cout, n * ho * wo, " ln" if ln else "",
                                                         " s%d" % plan.stride if plan.stride > 1 else ""), cost):
-                rc = _L.load().cobevt_linear_rows_small_k(_p(x), _p(plan.wfrag_rows), _p(plan.bias), _p(residual), _p(plan.pre_scale),
-                                                          _p(plan.pre_shift), _p(out), d3, ctypes.c_float(plan.ln_eps), _stream())
-            _L.check(rc, "cobevt_linear_rows_small_k")
+                _L.call("cobevt_linear_rows_small_k", _p(x), _p(plan.wfrag_rows), _p(plan.bias), _p(residual), _p(plan.pre_scale),
+                        _p(plan.pre_shift), _p(out), d3, ctypes.c_float(plan.ln_eps), _stream())
             return out
         with _timed("gemm_rows|%d->%d M=%d%s%s" % (cin, plan.cout, n * ho * wo, " ln" if ln else "",
                                                    " s%d" % plan.stride if plan.stride > 1 else ""), cost):
             if v2:      # persistent workgroups, fragment-ordered weights
-                rc = _L.load().cobevt_linear_rows_wfrag(_p(x), _p(plan.wfrag_rows), _p(plan.bias), _p(residual),
-                                                        _p(plan.pre_scale), _p(plan.pre_shift), _p(out), ldims,
-                                                        ctypes.c_float(plan.ln_eps), _stream())
+                _L.call("cobevt_linear_rows_wfrag", _p(x), _p(plan.wfrag_rows), _p(plan.bias), _p(residual), _p(plan.pre_scale),
+                        _p(plan.pre_shift), _p(out), ldims, ctypes.c_float(plan.ln_eps), _stream())
             else:
-                rc = _L.load().cobevt_linear_rows(_p(x), _p(plan.wgt_rows), _p(plan.bias), _p(residual), None, None,
-                                                  _p(plan.pre_scale), _p(plan.pre_shift), _p(out), ldims,
-                                                  ctypes.c_float(plan.ln_eps), _stream())
-        _L.check(rc, "cobevt_linear_rows_wfrag" if v2 else "cobevt_linear_rows")
+                _L.call("cobevt_linear_rows", _p(x), _p(plan.wgt_rows), _p(plan.bias), _p(residual), None, None, _p(plan.pre_scale),
+                        _p(plan.pre_shift), _p(out), ldims, ctypes.c_float(plan.ln_eps), _stream())
         return out
     variant = 0
     # (the stride-2 strip variants sit at the 256-VGPR limit in fp32: with the operand split of the f32s library they spill
@@ -483,21 +481,18 @@ def conv2d(x, plan, residual=None, out=None):
         dims = _ints([plan.code, n, h, w, cin, plan.cout, plan.upsample, plan.act, sm, plan.cc3, plan.coutp3, variant,
                       plan.stride])
         with _timed("conv3x3|%d->%d %dx%dx%d" % (cin, plan.cout, n, ho, wo), cost):
-            rc = _L.load().cobevt_conv3x3_wfrag_nhwc(_p(x), _p(plan.wfrag), _p(plan.bias), _p(residual), _p(out), dims, _stream())
-        _L.check(rc, "cobevt_conv3x3_wfrag_nhwc")
+            _L.call("cobevt_conv3x3_wfrag_nhwc", _p(x), _p(plan.wfrag), _p(plan.bias), _p(residual), _p(out), dims, _stream())
         return out
     if plan.wgt3 is not None and (out_h, out_w) == (ho, wo) and USE_CONV3X3:
         dims = _ints([plan.code, n, h, w, cin, plan.cout, plan.upsample, plan.act, sm, plan.cc3])
         with _timed("conv3x3|%d->%d %dx%dx%d" % (cin, plan.cout, n, ho, wo), cost):
-            rc = _L.load().cobevt_conv3x3_nhwc(_p(x), _p(plan.wgt3), _p(plan.bias), _p(residual), _p(out), dims, _stream())
-        _L.check(rc, "cobevt_conv3x3_nhwc")
+            _L.call("cobevt_conv3x3_nhwc", _p(x), _p(plan.wgt3), _p(plan.bias), _p(residual), _p(out), dims, _stream())
         return out
     dims = _ints([plan.code, n, h, w, cin, ho, wo, plan.cout, plan.kh, plan.kw, plan.stride, plan.pad, plan.K,
                   plan.kpad, plan.upsample, plan.pre_relu, plan.act, sm, out_h, out_w, plan.smallc])
     with _timed("igemm|k%ds%d %d->%d M=%d%s" % (plan.kh, plan.stride, cin, plan.cout, n * ho * wo, " stem" if plan.smallc else ""), cost):
-        rc = _L.load().cobevt_conv2d_nhwc(_p(x), _p(plan.wgt), _p(plan.bias), _p(residual), _p(plan.pre_scale),
-                                          _p(plan.pre_shift), _p(plan.klut), _p(out), dims, _stream())
-    _L.check(rc, "cobevt_conv2d_nhwc")
+        _L.call("cobevt_conv2d_nhwc", _p(x), _p(plan.wgt), _p(plan.bias), _p(residual), _p(plan.pre_scale), _p(plan.pre_shift),
+                _p(plan.klut), _p(out), dims, _stream())
     return out
 
 
@@ -521,9 +516,7 @@ def basicblock(x, plan1, plan2):
         return 2.0 * 2 * n * h * w * c * 9 * c, float(2 * x.numel() * esz + 2 * c * 9 * c * esz)
 
     with _timed("basicblock|%d %dx%dx%d" % (c, n, h, w), cost):
-        rc = _L.load().cobevt_basicblock_nhwc(_p(x), _p(plan1.wfrag), _p(plan1.bias), _p(plan2.wfrag), _p(plan2.bias),
-                                              _p(out), dims, _stream())
-    _L.check(rc, "cobevt_basicblock_nhwc")
+        _L.call("cobevt_basicblock_nhwc", _p(x), _p(plan1.wfrag), _p(plan1.bias), _p(plan2.wfrag), _p(plan2.bias), _p(out), dims, _stream())
     return out
 
 
@@ -550,9 +543,8 @@ def dsblock(x, plan1, plan2, plan_ds):
         return 2.0 * px * 128 * (9 * 64 + 9 * 128 + 64), float(2 * (x.numel() + out.numel()) + 2 * 128 * (9 * 64 + 9 * 128 + 64))
 
     with _timed("basicblock|%d->128/s2 %dx%dx%d" % (c, n, h // 2, w // 2), cost):
-        rc = _L.load().cobevt_dsblock_nhwc(_p(x), _p(plan1.wfrag), _p(plan1.bias), _p(plan2.wfrag), _p(plan2.bias),
-                                           _p(plan_ds.wfrag_rows), _p(plan_ds.bias), _p(out), dims, _stream())
-    _L.check(rc, "cobevt_dsblock_nhwc")
+        _L.call("cobevt_dsblock_nhwc", _p(x), _p(plan1.wfrag), _p(plan1.bias), _p(plan2.wfrag), _p(plan2.bias), _p(plan_ds.wfrag_rows),
+                _p(plan_ds.bias), _p(out), dims, _stream())
     return out
 
 
@@ -604,8 +596,7 @@ def conv3_ds(y, x, plan2, plan_ds, variant):
         return 2.0 * px * plan2.cout * (9 * c + cin2), float(2 * (y.numel() + px * cin2 + out.numel()) + 2 * plan2.cout * (9 * c + cin2))
 
     with _timed("conv3x3|%d->%d +ds%d %dx%dx%d" % (c, plan2.cout, cin2, n, ho, wo), cost):
-        rc = _L.load().cobevt_conv3x3_ds_wfrag_nhwc(_p(y), _p(x), _p(table), _p(plan2.bias), _p(plan_ds.bias), _p(out), dims, _stream())
-    _L.check(rc, "cobevt_conv3x3_ds_wfrag_nhwc")
+        _L.call("cobevt_conv3x3_ds_wfrag_nhwc", _p(y), _p(x), _p(table), _p(plan2.bias), _p(plan_ds.bias), _p(out), dims, _stream())
     return out
 
 
@@ -666,9 +657,8 @@ def bottleneck(x, plan, tile_rows=0):
         return 2.0 * m * (128 * 32 + 32 * 32 * 9 + 32 * 128), float(2 * x.numel() * 2 + (128 * 32 * 2 + 32 * 32 * 9) * 2)
 
     with _timed("bottleneck|%dx%dx%d" % (n, h, w), cost):
-        rc = _L.load().cobevt_bottleneck_nhwc(_p(x), _p(plan.w1), _p(plan.w2), _p(plan.w3), _p(plan.b1), _p(plan.b2), _p(plan.b3),
-                                              _p(out), dims, _stream())
-    _L.check(rc, "cobevt_bottleneck_nhwc")
+        _L.call("cobevt_bottleneck_nhwc", _p(x), _p(plan.w1), _p(plan.w2), _p(plan.w3), _p(plan.b1), _p(plan.b2), _p(plan.b3), _p(out),
+                dims, _stream())
     return out
 
 
@@ -696,9 +686,8 @@ def bottleneck_f32(x, p1, p2, p3, y1=None):
         return 2.0 * m * ((0 if y1 is not None else 128 * 32) + 32 * 32 * 9 + 32 * 128), float((2 * x.numel() + (y1.numel() if y1 is not None else 0)) * 4)
 
     with _timed("bottleneck|%dx%dx%d%s" % (n, h, w, " y1" if y1 is not None else ""), cost):
-        rc = _L.load().cobevt_bottleneck_f32_nhwc(_p(x), _p(y1), _p(p1.wfrag_rows), _p(p1.bias), _p(p2.wfrag), _p(p2.bias),
-                                                  _p(p3.wfrag_rows), _p(p3.bias), _p(out), dims, _stream())
-    _L.check(rc, "cobevt_bottleneck_f32_nhwc")
+        _L.call("cobevt_bottleneck_f32_nhwc", _p(x), _p(y1), _p(p1.wfrag_rows), _p(p1.bias), _p(p2.wfrag), _p(p2.bias), _p(p3.wfrag_rows),
+                _p(p3.bias), _p(out), dims, _stream())
     return out
 
 
@@ -729,9 +718,7 @@ def layernorm(x, gamma, beta, eps=1e-5, out=None):
     rows = x.numel() // c
     if out is None:
         out = torch.empty_like(x)
-    rc = _L.load().cobevt_layernorm(_p(x), _p(gamma), _p(beta), _p(out), dcode(x.dtype), rows, c, float(eps), 1, 0, 0, 0,
-                                    _stream())
-    _L.check(rc, "cobevt_layernorm")
+    _L.call("cobevt_layernorm", _p(x), _p(gamma), _p(beta), _p(out), dcode(x.dtype), rows, c, float(eps), 1, 0, 0, 0, _stream())
     return out
 
 
@@ -742,9 +729,8 @@ def mean_layernorm(x, gamma, beta, eps=1e-5):
     if not x.is_contiguous():
         raise CobevtHipError("mean_layernorm: input must be contiguous")
     out = torch.empty((b, r, c), device=x.device, dtype=x.dtype)
-    rc = _L.load().cobevt_layernorm(_p(x), _p(gamma), _p(beta), _p(out), dcode(x.dtype), b * r, c, float(eps), l,
-                                    r * c, l * r * c, r, _stream())
-    _L.check(rc, "cobevt_layernorm")
+    _L.call("cobevt_layernorm", _p(x), _p(gamma), _p(beta), _p(out), dcode(x.dtype), b * r, c, float(eps), l, r * c, l * r * c, r,
+            _stream())
     return out
 
 
@@ -764,9 +750,8 @@ def mean_ln_linear(x, plan):
         return 2.0 * b * r * c * plan.cout, float((b * l * r * c + b * r * plan.cout + c * plan.cout) * 2)
 
     with _timed("gemm_rows|mean%d %d->%d M=%d ln" % (l, c, plan.cout, b * r), cost):
-        rc = _L.load().cobevt_mean_linear_rows_small_k(_p(x), _p(plan.wfrag_rows), _p(plan.bias), _p(out), dims,
-                                                       ctypes.c_float(plan.ln_eps), _stream())
-    _L.check(rc, "cobevt_mean_linear_rows_small_k")
+        _L.call("cobevt_mean_linear_rows_small_k", _p(x), _p(plan.wfrag_rows), _p(plan.bias), _p(out), dims, ctypes.c_float(plan.ln_eps),
+                _stream())
     return out
 
 
@@ -817,12 +802,11 @@ def window_attention(q, k, v, out, qmap, kmap, omap, batch, heads, scale, ldq, l
             rows = out.numel() // out.shape[-1]
             part_out = torch.empty((ks, rows, heads * 32), device=out.device, dtype=out.dtype)
             part_lse = torch.empty((ks, rows, heads), device=out.device, dtype=torch.float32)
-            rc = _L.load().cobevt_window_attention_ksplit(_p(q), _p(k), _p(v), _p(out), _p(bias_table), _p(mask), _p(part_out),
-                                                          _p(part_lse), dims, ctypes.c_float(scale), ks, rows, _stream())
+            _L.call("cobevt_window_attention_ksplit", _p(q), _p(k), _p(v), _p(out), _p(bias_table), _p(mask), _p(part_out), _p(part_lse),
+                    dims, ctypes.c_float(scale), ks, rows, _stream())
         else:
-            rc = _L.load().cobevt_window_attention(_p(q), _p(k), _p(v), _p(out), _p(bias_table), _p(mask), dims,
-                                                   ctypes.c_float(scale), _stream())
-    _L.check(rc, "cobevt_window_attention")
+            _L.call("cobevt_window_attention", _p(q), _p(k), _p(v), _p(out), _p(bias_table), _p(mask), dims, ctypes.c_float(scale),
+                    _stream())
     return out
 
 
@@ -846,8 +830,7 @@ def attention_index_map(tmap, batch, device):
     L, ntok = tmap[6] * tmap[7], tmap[1] * tmap[4] * tmap[5]
     rows = torch.empty((batch, L, ntok), device=device, dtype=torch.int32)
     _need_cuda(rows)
-    rc = _L.load().cobevt_attention_index_map(_ints(tmap), batch, _p(rows), _stream())
-    _L.check(rc, "cobevt_attention_index_map")
+    _L.call("cobevt_attention_index_map", _ints(tmap), batch, _p(rows), _stream())
     return rows
 
 
@@ -856,8 +839,7 @@ def attention_bias_index(qmap, kmap, bias_L, device):
     nq, nk = qmap[1] * qmap[4] * qmap[5], kmap[1] * kmap[4] * kmap[5]
     idx = torch.empty((nq, nk), device=device, dtype=torch.int32)
     _need_cuda(idx)
-    rc = _L.load().cobevt_attention_bias_index(_ints(qmap), _ints(kmap), int(bias_L), _p(idx), _stream())
-    _L.check(rc, "cobevt_attention_bias_index")
+    _L.call("cobevt_attention_bias_index", _ints(qmap), _ints(kmap), int(bias_L), _p(idx), _stream())
     return idx
 
 
@@ -869,8 +851,7 @@ def agent_max(x):
     b, l = x.shape[:2]
     out = torch.empty((b,) + tuple(x.shape[2:]), device=x.device, dtype=x.dtype)
     per = out[0].numel()
-    rc = _L.load().cobevt_agent_max(_p(x), _p(out), dcode(x.dtype), b, l, per, _stream())
-    _L.check(rc, "cobevt_agent_max")
+    _L.call("cobevt_agent_max", _p(x), _p(out), dcode(x.dtype), b, l, per, _stream())
     return out
 
 
@@ -878,9 +859,8 @@ def ray_embed(i_inv, e_inv, image_plane, w_img, w_cam, hw, dim, dtype):
     _need_cuda(i_inv, e_inv, image_plane, w_img, w_cam)
     bn = i_inv.shape[0]
     out = torch.empty((bn, hw, dim), device=i_inv.device, dtype=dtype)
-    rc = _L.load().cobevt_fax_ray_embed(_p(i_inv), _p(e_inv), _p(image_plane), _p(w_img), _p(w_cam), _p(out),
-                                        dcode(dtype), bn, hw, dim, _stream())
-    _L.check(rc, "cobevt_fax_ray_embed")
+    _L.call("cobevt_fax_ray_embed", _p(i_inv), _p(e_inv), _p(image_plane), _p(w_img), _p(w_cam), _p(out), dcode(dtype), bn, hw, dim,
+            _stream())
     return out
 
 
@@ -897,9 +877,8 @@ def bev_embed(e_inv, world, w_bev, b_bev, w_cam, x, n):
     if not bcast:
         x = x.contiguous()
     out = torch.empty((b, n, hw, d), device=x.device, dtype=x.dtype)
-    rc = _L.load().cobevt_fax_bev_embed(_p(e_inv), _p(world), _p(w_bev), _p(b_bev), _p(w_cam), _p(x), _p(out),
-                                        dcode(x.dtype), b, n, hw, d, int(bcast), _stream())
-    _L.check(rc, "cobevt_fax_bev_embed")
+    _L.call("cobevt_fax_bev_embed", _p(e_inv), _p(world), _p(w_bev), _p(b_bev), _p(w_cam), _p(x), _p(out), dcode(x.dtype), b, n, hw, d,
+            int(bcast), _stream())
     return out
 
 
@@ -924,10 +903,8 @@ def bev_embed_linear(e_inv, world, w_bev, b_bev, w_cam, x, n, plan):
             return 2.0 * m * plan.cout * d, float((hw if bcast else x.numel() // d) * d * 2 + plan.cout * d * 2 + out.numel() * 2)
 
         with _timed("gemm_rows|embed %d->%d M=%d ln r32" % (d, plan.cout, b * n * hw), cost3):
-            rc = _L.load().cobevt_bev_embed_linear_rows_small_k(_p(e_inv), _p(world), _p(w_bev), _p(b_bev), _p(w_cam), _p(x),
-                                                                _p(plan.wfrag_rows), _p(plan.bias), _p(out), dims,
-                                                                ctypes.c_float(plan.ln_eps), _stream())
-        _L.check(rc, "cobevt_bev_embed_linear_rows_small_k")
+            _L.call("cobevt_bev_embed_linear_rows_small_k", _p(e_inv), _p(world), _p(w_bev), _p(b_bev), _p(w_cam), _p(x),
+                    _p(plan.wfrag_rows), _p(plan.bias), _p(out), dims, ctypes.c_float(plan.ln_eps), _stream())
         return out
     fused = (USE_EMBED_GEMM and USE_GEMM_ROWS and plan.has_ln and ln_fusable(plan) and plan.K == d and hw % 128 == 0
              and plan.stride == 1 and plan.pre_scale is None and plan.act == 0 and x.is_contiguous())
@@ -943,10 +920,8 @@ def bev_embed_linear(e_inv, world, w_bev, b_bev, w_cam, x, n, plan):
         return 2.0 * m * plan.cout * d, float(x.numel() * esz + plan.cout * d * esz + out.numel() * esz)
 
     with _timed("gemm_rows|embed %d->%d M=%d ln" % (d, plan.cout, b * n * hw), cost):
-        rc = _L.load().cobevt_bev_embed_linear_rows(_p(e_inv), _p(world), _p(w_bev), _p(b_bev), _p(w_cam), _p(x),
-                                                    _p(plan.wgt_rows), _p(plan.bias), _p(out), dims,
-                                                    ctypes.c_float(plan.ln_eps), _stream())
-    _L.check(rc, "cobevt_bev_embed_linear_rows")
+        _L.call("cobevt_bev_embed_linear_rows", _p(e_inv), _p(world), _p(w_bev), _p(b_bev), _p(w_cam), _p(x), _p(plan.wgt_rows),
+                _p(plan.bias), _p(out), dims, ctypes.c_float(plan.ln_eps), _stream())
     return out
 
 
@@ -967,8 +942,7 @@ def stem_pool(x, plan):
         return 2.0 * n * (h // 2) * (w // 2) * 64 * 147, float(x.numel() * 4 + out.numel() * esz)
 
     with _timed("stem7x7|pool %dx%dx%d" % (n, h, w), cost):
-        rc = _L.load().cobevt_stem_conv7x7s2_pool(_p(x), _p(plan.wgt_stem), _p(plan.bias), _p(out), dims, _stream())
-    _L.check(rc, "cobevt_stem_conv7x7s2_pool")
+        _L.call("cobevt_stem_conv7x7s2_pool", _p(x), _p(plan.wgt_stem), _p(plan.bias), _p(out), dims, _stream())
     return out
 
 
@@ -991,8 +965,7 @@ def stem_pool_u8(x, lut, plan):
         return 2.0 * n * (h // 2) * (w // 2) * 64 * 147, float(x.numel() + out.numel() * esz)
 
     with _timed("stem7x7|pool u8 %dx%dx%d" % (n, h, w), cost):
-        rc = _L.load().cobevt_stem_conv7x7s2_pool_u8(_p(x), _p(lut), _p(plan.wgt_stem), _p(plan.bias), _p(out), dims, _stream())
-    _L.check(rc, "cobevt_stem_conv7x7s2_pool_u8")
+        _L.call("cobevt_stem_conv7x7s2_pool_u8", _p(x), _p(lut), _p(plan.wgt_stem), _p(plan.bias), _p(out), dims, _stream())
     return out
 
 
@@ -1006,8 +979,7 @@ def host_fetch(src_pinned, dst, blocks=0):
     if (tuple(src_pinned.shape) != tuple(dst.shape) or src_pinned.dtype != dst.dtype or not src_pinned.is_contiguous() or not dst.is_contiguous()
             or nbytes % 16):
         raise CobevtHipError("host_fetch: contiguous tensors of one shape / dtype, a multiple of 16 bytes")
-    rc = _L.load().cobevt_host_fetch(ctypes.c_void_p(src_pinned.data_ptr()), _p(dst), nbytes, int(blocks), _stream())
-    _L.check(rc, "cobevt_host_fetch")
+    _L.call("cobevt_host_fetch", ctypes.c_void_p(src_pinned.data_ptr()), _p(dst), nbytes, int(blocks), _stream())
     return dst
 
 
@@ -1016,8 +988,7 @@ def maxpool3x3s2(x):
     n, h, w, c = x.shape
     ho, wo = (h + 2 - 3) // 2 + 1, (w + 2 - 3) // 2 + 1
     out = torch.empty((n, ho, wo, c), device=x.device, dtype=x.dtype)
-    rc = _L.load().cobevt_maxpool3x3s2(_p(x), _p(out), dcode(x.dtype), n, h, w, c, _stream())
-    _L.check(rc, "cobevt_maxpool3x3s2")
+    _L.call("cobevt_maxpool3x3s2", _p(x), _p(out), dcode(x.dtype), n, h, w, c, _stream())
     return out
 
 
@@ -1031,8 +1002,7 @@ def to_nhwc(x, dtype):
         return v
     out = torch.empty((n, h, w, c), device=x.device, dtype=dtype)
     strides = (ctypes.c_long * 4)(*x.stride())
-    rc = _L.load().cobevt_to_nhwc(_p(x), dcode(x.dtype), _p(out), dcode(dtype), n, c, h, w, strides, _stream())
-    _L.check(rc, "cobevt_to_nhwc")
+    _L.call("cobevt_to_nhwc", _p(x), dcode(x.dtype), _p(out), dcode(dtype), n, c, h, w, strides, _stream())
     return out
 
 
@@ -1042,8 +1012,7 @@ def from_nhwc(x, dtype):
     n, h, w, c = x.shape
     out = torch.empty((n, c, h, w), device=x.device, dtype=dtype)
     strides = (ctypes.c_long * 4)(*out.stride())
-    rc = _L.load().cobevt_from_nhwc(_p(x), dcode(x.dtype), _p(out), dcode(dtype), n, c, h, w, strides, _stream())
-    _L.check(rc, "cobevt_from_nhwc")
+    _L.call("cobevt_from_nhwc", _p(x), dcode(x.dtype), _p(out), dcode(dtype), n, c, h, w, strides, _stream())
     return out
 
 
@@ -1058,8 +1027,7 @@ def copy_into_interior(x, dst):
         raise CobevtHipError("copy_into_interior: dst must be a contiguous (N, >= h, >= w, C) map of x's dtype")
     sN, sH, sW, sC = dst.stride()
     strides = (ctypes.c_long * 4)(sN, sC, sH, sW)                     # (N, C, H, W) order of the C entry point
-    rc = _L.load().cobevt_from_nhwc(_p(x), dcode(x.dtype), _p(dst), dcode(dst.dtype), n, c, h, w, strides, _stream())
-    _L.check(rc, "cobevt_from_nhwc")
+    _L.call("cobevt_from_nhwc", _p(x), dcode(x.dtype), _p(dst), dcode(dst.dtype), n, c, h, w, strides, _stream())
     return dst
 
 
@@ -1072,8 +1040,7 @@ def regroup(x, record_len, max_cav):
     per = x[0].numel()
     out = torch.empty((b, max_cav) + tuple(x.shape[1:]), device=x.device, dtype=x.dtype)
     mask = torch.empty((b, max_cav), device=x.device, dtype=torch.float32)
-    rc = _L.load().cobevt_regroup(_p(x), _p(record_len), _p(out), _p(mask), dcode(x.dtype), b, max_cav, per, _stream())
-    _L.check(rc, "cobevt_regroup")
+    _L.call("cobevt_regroup", _p(x), _p(record_len), _p(out), _p(mask), dcode(x.dtype), b, max_cav, per, _stream())
     return out, mask
 
 
@@ -1113,9 +1080,8 @@ def _pillar_call(voxel_features, voxel_num_points, voxel_coords, w, shift, geom,
         raise CobevtHipError("pillar_vfe: geom = (voxel x, y, z, offset x, y, z)")
     dims = _ints([p, t, f, k, int(bool(use_absolute_xyz)), int(bool(with_distance)), dcode(dtype), rows, n, b, max_cav, ny, nx])
     g = (ctypes.c_float * 6)(*[float(v) for v in geom])
-    rc = _L.load().cobevt_pillar_vfe(_p(voxel_features), _p(npts), _p(coords), _p(w), _p(shift), _p(record_len), _p(out), _p(cav), dims, g,
-                                     _stream())
-    _L.check(rc, "cobevt_pillar_vfe")
+    _L.call("cobevt_pillar_vfe", _p(voxel_features), _p(npts), _p(coords), _p(w), _p(shift), _p(record_len), _p(out), _p(cav), dims, g,
+            _stream())
 
 
 def _canvas(out, shape, dtype, device, what):
@@ -1193,8 +1159,7 @@ def scatter_rows(rows, voxel_coords, num_agents, grid, out=None):
     if n < 1 or ny < 1 or nx < 1:
         raise CobevtHipError("scatter_rows: empty canvas (%d, %d, %d, %d)" % (n, ny, nx, c))
     out = _canvas(out, (n, ny, nx, c), rows.dtype, rows.device, "scatter_rows")
-    rc = _L.load().cobevt_scatter_rows(_p(rows), _p(coords), _p(out), dcode(rows.dtype), p, c, n, ny, nx, _stream())
-    _L.check(rc, "cobevt_scatter_rows")
+    _L.call("cobevt_scatter_rows", _p(rows), _p(coords), _p(out), dcode(rows.dtype), p, c, n, ny, nx, _stream())
     return out
 
 
@@ -1212,7 +1177,7 @@ def voxelize_workspace_ints(num_points, num_agents, grid, max_points, max_voxels
     """int32 elements of voxelize_points' workspace for M points of N agents on an (nx, ny, nz) grid (cobevt_voxelize_scratch)"""
     dims = (ctypes.c_long * 9)(int(num_points), int(num_agents), int(max_points), int(max_voxels), int(grid[0]), int(grid[1]), int(grid[2]), 0, 0)
     need = ctypes.c_long(0)
-    _L.check(_L.load().cobevt_voxelize_scratch(dims, ctypes.byref(need)), "cobevt_voxelize_scratch")
+    _L.call("cobevt_voxelize_scratch", dims, ctypes.byref(need))
     return need.value
 
 
@@ -1256,7 +1221,6 @@ def voxelize_points(points, point_offsets, lidar_range, voxel_size, max_points=3
     dev, pcap = points.device, n * mv
     dims = (ctypes.c_long * 9)(m, n, t, mv, nx, ny, nz, int(bool(range_mask)), int(bool(ego_mask)))
     geom = (ctypes.c_float * 9)(*[float(v) for v in list(lidar_range) + list(voxel_size)])
-    lib = _L.load()
     if workspace is None:
         key = (dev, m, n, t, mv, nx, ny)
         workspace = _VOXEL_WS.get(key)
@@ -1274,8 +1238,7 @@ def voxelize_points(points, point_offsets, lidar_range, voxel_size, max_points=3
     vf, coords, npts, nvox = [_canvas(o, s, d, dev, "voxelize_points") for o, (s, d) in zip(out, shapes)]
     cost = lambda: (0.0, 32.0 * m + 16.0 * m + 16.0 * (n * ny * nx) + 24.0 * pcap)         # noqa: E731
     with _timed("voxelize|M%d N%d T%d %dx%d" % (m, n, t, ny, nx), cost):
-        rc = lib.cobevt_voxelize_points(_p(points), _p(offs), _p(vf), _p(coords), _p(npts), _p(nvox), _p(workspace), dims, geom, _stream())
-    _L.check(rc, "cobevt_voxelize_points")
+        _L.call("cobevt_voxelize_points", _p(points), _p(offs), _p(vf), _p(coords), _p(npts), _p(nvox), _p(workspace), dims, geom, _stream())
     return vf, coords, npts, nvox
 
 
@@ -1287,7 +1250,7 @@ _DETECT_WS = {}            # (device, total anchors) -> the workspace: one buffe
 def detect_workspace_bytes(total_anchors):
     """bytes of detect_post_process' / nms_rotated's workspace for `total_anchors` candidates (cobevt_detect_scratch)"""
     need = ctypes.c_long(0)
-    _L.check(_L.load().cobevt_detect_scratch(int(total_anchors), ctypes.byref(need)), "cobevt_detect_scratch")
+    _L.call("cobevt_detect_scratch", int(total_anchors), ctypes.byref(need))
     return need.value
 
 
@@ -1347,7 +1310,7 @@ def delta_to_boxes3d(deltas, anchors):
     anc = _f32_dev(anchors, deltas.device, "delta_to_boxes3d: anchors")
     n, h, w, a = _head_maps(None, deltas, anc, "delta_to_boxes3d")
     out = torch.empty((n, h * w * a, 7), device=deltas.device, dtype=torch.float32)
-    _L.check(_L.load().cobevt_delta_to_boxes3d(_p(deltas), _p(anc), _p(out), n, h, w, a, _stream()), "cobevt_delta_to_boxes3d")
+    _L.call("cobevt_delta_to_boxes3d", _p(deltas), _p(anc), _p(out), n, h, w, a, _stream())
     return out
 
 
@@ -1367,7 +1330,7 @@ def rotated_iou(a, b):
     qa = _quads(a, a.device, "rotated_iou: a")
     qb = _quads(b, a.device, "rotated_iou: b")
     out = torch.empty((qa.shape[0], qb.shape[0]), device=a.device, dtype=torch.float64)
-    _L.check(_L.load().cobevt_rotated_iou(_p(qa), _p(qb), _p(out), qa.shape[0], qb.shape[0], _stream()), "cobevt_rotated_iou")
+    _L.call("cobevt_rotated_iou", _p(qa), _p(qb), _p(out), qa.shape[0], qb.shape[0], _stream())
     return out
 
 
@@ -1382,9 +1345,8 @@ def nms_rotated_device(boxes, scores, threshold, out=None, workspace=None):
     sc = _f32_dev(scores, dev, "nms_rotated: scores", (n,))
     ws = _detect_workspace(workspace, n, dev, "nms_rotated")
     ob, osc, oi, oc = _detect_out(out, dev, "nms_rotated")
-    rc = _L.load().cobevt_nms_rotated(_p(b) if n else None, _p(sc) if n else None, n, b.shape[1] * b.shape[2], float(threshold), _p(ob),
-                                      _p(osc), _p(oi), _p(oc), _p(ws), _stream())
-    _L.check(rc, "cobevt_nms_rotated")
+    _L.call("cobevt_nms_rotated", _p(b) if n else None, _p(sc) if n else None, n, b.shape[1] * b.shape[2], float(threshold), _p(ob),
+            _p(osc), _p(oi), _p(oc), _p(ws), _stream())
     return ob, osc, oi, oc
 
 
@@ -1434,9 +1396,8 @@ def detect_post_process(cavs, score_threshold, nms_thresh, order, out=None, work
     ptrs = [(ctypes.c_void_p * len(cavs))(*[k[j].data_ptr() for k in keep]) for j in range(3)]
     cost = lambda: (0.0, 36.0 * total + 8.0 * DETECT_TOP * 16 + 200.0 * DETECT_TOP)         # noqa: E731
     with _timed("detect_post|cavs%d N%d" % (len(cavs), total), cost):
-        rc = _L.load().cobevt_detect_post(ptrs[0], ptrs[1], ptrs[2], _p(matrices), _ints(dims), len(cavs), int(order == "hwl"),
-                                          float(score_threshold), float(nms_thresh), _p(ob), _p(osc), _p(oi), _p(oc), _p(ws), _stream())
-    _L.check(rc, "cobevt_detect_post")
+        _L.call("cobevt_detect_post", ptrs[0], ptrs[1], ptrs[2], _p(matrices), _ints(dims), len(cavs), int(order == "hwl"),
+                float(score_threshold), float(nms_thresh), _p(ob), _p(osc), _p(oi), _p(oc), _p(ws), _stream())
     return ob, osc, oi, oc
 
 
@@ -1461,10 +1422,8 @@ def sttf_warp(x, tmat, cav_mask, discrete_ratio, downsample_rate, want_mask=True
     if tuple(tmat.shape[:2]) != (b, l):
         raise CobevtHipError("sttf_warp: tmat must be (B, L, 4, 4)")
     com = torch.empty((b, h, w, 1, l), device=x.device, dtype=torch.float32) if want_mask else None
-    rc = _L.load().cobevt_sttf_warp(_p(x), _p(tmat), _p(cav_mask), _p(out), _p(com), _p(record_len), _p(cav),
-                                    dcode(x.dtype), b, l, h, w, c,
-                                    ctypes.c_float(discrete_ratio), ctypes.c_float(downsample_rate), _stream())
-    _L.check(rc, "cobevt_sttf_warp")
+    _L.call("cobevt_sttf_warp", _p(x), _p(tmat), _p(cav_mask), _p(out), _p(com), _p(record_len), _p(cav), dcode(x.dtype), b, l, h, w, c,
+            ctypes.c_float(discrete_ratio), ctypes.c_float(downsample_rate), _stream())
     return (out, com, cav) if record_len is not None else (out, com)
 
 
@@ -1480,9 +1439,8 @@ def pairwise_warp(x, pairwise, record_len, max_cav, discrete_ratio, downsample_r
         raise CobevtHipError("pairwise_warp: pairwise must be (B, max_cav, max_cav, 4, 4)")
     nb = torch.empty((b, l, l, h, w, c), device=x.device, dtype=x.dtype)
     roi = torch.empty((b, l, l, h, w), device=x.device, dtype=torch.float32)
-    rc = _L.load().cobevt_pairwise_warp(_p(x), _p(pairwise.contiguous()), _p(record_len), _p(nb), _p(roi), dcode(x.dtype), b, l, h, w, c,
-                                        ctypes.c_float(discrete_ratio), ctypes.c_float(downsample_rate), _stream())
-    _L.check(rc, "cobevt_pairwise_warp")
+    _L.call("cobevt_pairwise_warp", _p(x), _p(pairwise.contiguous()), _p(record_len), _p(nb), _p(roi), dcode(x.dtype), b, l, h, w, c,
+            ctypes.c_float(discrete_ratio), ctypes.c_float(downsample_rate), _stream())
     return nb, roi
 
 
@@ -1492,9 +1450,8 @@ def agent_message_reduce(msg, ego, roi, record_len, mode):
     _need_cuda(msg, ego, roi, record_len)
     b, l, _, h, w, c = msg.shape
     out = torch.zeros_like(ego)
-    rc = _L.load().cobevt_agent_message_reduce(_p(msg), _p(ego), _p(roi), _p(record_len), _p(out), dcode(msg.dtype), b, l, h * w, c,
-                                               {"avg": 0, "max": 1}[mode], _stream())
-    _L.check(rc, "cobevt_agent_message_reduce")
+    _L.call("cobevt_agent_message_reduce", _p(msg), _p(ego), _p(roi), _p(record_len), _p(out), dcode(msg.dtype), b, l, h * w, c,
+            {"avg": 0, "max": 1}[mode], _stream())
     return out
 
 
@@ -1503,8 +1460,7 @@ def gru_zero_state(x):
     _need_cuda(x)
     c = x.shape[-1] // 2
     out = torch.empty(x.shape[:-1] + (c,), device=x.device, dtype=x.dtype)
-    rc = _L.load().cobevt_gru_zero_state(_p(x), _p(out), dcode(x.dtype), x.numel() // (2 * c), c, _stream())
-    _L.check(rc, "cobevt_gru_zero_state")
+    _L.call("cobevt_gru_zero_state", _p(x), _p(out), dcode(x.dtype), x.numel() // (2 * c), c, _stream())
     return out
 
 
@@ -1513,9 +1469,8 @@ def agent_softmax_sum(score, nb, roi, record_len, n_agents, use_mask=True):
     _need_cuda(score, nb, roi, record_len)
     b, l, _, h, w, c = nb.shape
     out = torch.zeros((n_agents, h, w, c), device=nb.device, dtype=nb.dtype)
-    rc = _L.load().cobevt_agent_softmax_sum(_p(score), score.shape[-1], _p(nb), _p(roi), _p(record_len), _p(out), dcode(nb.dtype),
-                                            b, l, h * w, c, int(bool(use_mask)), _stream())
-    _L.check(rc, "cobevt_agent_softmax_sum")
+    _L.call("cobevt_agent_softmax_sum", _p(score), score.shape[-1], _p(nb), _p(roi), _p(record_len), _p(out), dcode(nb.dtype), b, l, h * w,
+            c, int(bool(use_mask)), _stream())
     return out
 
 
@@ -1525,8 +1480,7 @@ def invert_small(m):
     d = m.shape[-1]
     x = m.to(torch.float32).contiguous()
     out = torch.empty_like(x)
-    rc = _L.load().cobevt_invert_small(_p(x), _p(out), x.numel() // (d * d), d, _stream())
-    _L.check(rc, "cobevt_invert_small")
+    _L.call("cobevt_invert_small", _p(x), _p(out), x.numel() // (d * d), d, _stream())
     return out
 
 
@@ -1535,9 +1489,7 @@ def resize_nhwc(x, ho, wo, mode):
     _need_cuda(x)
     n, h, w, c = x.shape
     out = torch.empty((n, ho, wo, c), device=x.device, dtype=x.dtype)
-    rc = _L.load().cobevt_resize_nhwc(_p(x), _p(out), dcode(x.dtype), n, h, w, c, ho, wo, 0 if mode == "nearest" else 1,
-                                      _stream())
-    _L.check(rc, "cobevt_resize_nhwc")
+    _L.call("cobevt_resize_nhwc", _p(x), _p(out), dcode(x.dtype), n, h, w, c, ho, wo, 0 if mode == "nearest" else 1, _stream())
     return out
 
 
@@ -1548,8 +1500,7 @@ def channel_affine(x, scale, shift):
         x = x.to(torch.float32).contiguous()
     out = torch.empty_like(x)
     n, c = x.shape[0], x.shape[1]
-    rc = _L.load().cobevt_channel_affine(_p(x), _p(scale), _p(shift), _p(out), n, c, x.numel() // (n * c), _stream())
-    _L.check(rc, "cobevt_channel_affine")
+    _L.call("cobevt_channel_affine", _p(x), _p(scale), _p(shift), _p(out), n, c, x.numel() // (n * c), _stream())
     return out
 
 
@@ -1602,13 +1553,10 @@ def attn_mlp_chain(a, skip, plan_p, plan_1, plan_2, post_ln=None, next_plan=None
 
     with _timed("row_chain|C%d H%d M=%d%s%s" % (c, hd, m, " post" if post_ln is not None else "",
                                                   " +next%d" % nn_ if fuse_next else ""), cost):
-        rc = _L.load().cobevt_attn_mlp_chain(_p(a), _p(skip), _p(out), _p(plan_p.wfrag_rows), _p(plan_p.bias),
-                                             _p(plan_1.wfrag_rows), _p(plan_1.bias), _p(plan_2.wfrag_rows), _p(plan_2.bias),
-                                             _p(pg), _p(pb), _p(next_plan.wfrag_rows) if fuse_next else None,
-                                             _p(next_plan.bias) if fuse_next else None, _p(out_next), dims,
-                                             ctypes.c_float(plan_1.ln_eps), ctypes.c_float(pe),
-                                             ctypes.c_float(next_plan.ln_eps if fuse_next else 0.0), _stream())
-    _L.check(rc, "cobevt_attn_mlp_chain")
+        _L.call("cobevt_attn_mlp_chain", _p(a), _p(skip), _p(out), _p(plan_p.wfrag_rows), _p(plan_p.bias), _p(plan_1.wfrag_rows),
+                _p(plan_1.bias), _p(plan_2.wfrag_rows), _p(plan_2.bias), _p(pg), _p(pb), _p(next_plan.wfrag_rows) if fuse_next else None,
+                _p(next_plan.bias) if fuse_next else None, _p(out_next), dims, ctypes.c_float(plan_1.ln_eps), ctypes.c_float(pe),
+                ctypes.c_float(next_plan.ln_eps if fuse_next else 0.0), _stream())
     if next_plan is None:
         return out
     return out, (out_next if fuse_next else linear(out, next_plan))
@@ -1638,10 +1586,9 @@ def proj_chain(x, plan_p, next_plan, residual=None, out_next=None):
         return 2.0 * m * (c * c + c * nn_), float(m * (c * (2 if residual is not None else 1) + nn_) * 2 + (c * c + c * nn_) * 2)
 
     with _timed("row_chain|proj C%d M=%d +next%d" % (c, m, nn_), cost):
-        rc = _L.load().cobevt_proj_chain(_p(x), _p(plan_p.pre_scale), _p(plan_p.pre_shift), _p(residual), _p(plan_p.wfrag_rows),
-                                         _p(plan_p.bias), None, _p(next_plan.wfrag_rows), _p(next_plan.bias), _p(out_next), dims,
-                                         ctypes.c_float(next_plan.ln_eps), _stream())
-    _L.check(rc, "cobevt_proj_chain")
+        _L.call("cobevt_proj_chain", _p(x), _p(plan_p.pre_scale), _p(plan_p.pre_shift), _p(residual), _p(plan_p.wfrag_rows),
+                _p(plan_p.bias), None, _p(next_plan.wfrag_rows), _p(next_plan.bias), _p(out_next), dims, ctypes.c_float(next_plan.ln_eps),
+                _stream())
     return out_next
 
 
@@ -1688,8 +1635,7 @@ def proj_chain_kv(x, plan_key, plan_val, next_key, next_val, residual=None, out_
         return 2.0 * 2 * m * (k * 128 + 128 * nn_), float(m * (k + (128 if residual is not None else 0) + 2 * nn_) * 2 + 2 * (k * 128 + 128 * nn_) * 2)
 
     with _timed("row_chain|proj kv K%d M=%d +next%d" % (k, m, nn_), cost):
-        rc = _L.load().cobevt_proj_chain_kv(_p(x), ptrs, dims, ctypes.c_float(next_key.ln_eps), _stream())
-    _L.check(rc, "cobevt_proj_chain_kv")
+        _L.call("cobevt_proj_chain_kv", _p(x), ptrs, dims, ctypes.c_float(next_key.ln_eps), _stream())
     return outs[0], outs[1]
 
 
@@ -1733,13 +1679,11 @@ def swap_stage(qkv, x, tmap, batch, heads, scale, bias_table, bias_L, mask, plan
         return flops, float(m * (3 * c + 2 * c + nn_) * 2 + (c * c + 2 * c * hd + c * nn_) * 2)
 
     with _timed("swap_stage|mode%d M=%d Nk%d H%d%s" % (tmap[0], m, nk, hd, " +next%d" % nn_ if nn_ else ""), cost):
-        rc = _L.load().cobevt_swap_fusion_stage(
-            _p(qkv), _p(x), _p(out), _p(qkv_next), _ints(tmap), _p(bias_table), _p(mask), _p(plan_p.wfrag_rows), _p(plan_p.bias),
-            _p(plan_1.wfrag_rows), _p(plan_1.bias), _p(plan_2.wfrag_rows), _p(plan_2.bias),
-            _p(next_plan.wfrag_rows) if next_plan is not None else None, _p(next_plan.bias) if next_plan is not None else None,
-            dims, ctypes.c_float(scale), ctypes.c_float(plan_1.ln_eps), ctypes.c_float(next_plan.ln_eps if next_plan is not None else 0.0),
-            _stream())
-    _L.check(rc, "cobevt_swap_fusion_stage")
+        _L.call("cobevt_swap_fusion_stage", _p(qkv), _p(x), _p(out), _p(qkv_next), _ints(tmap), _p(bias_table), _p(mask),
+                _p(plan_p.wfrag_rows), _p(plan_p.bias), _p(plan_1.wfrag_rows), _p(plan_1.bias), _p(plan_2.wfrag_rows), _p(plan_2.bias),
+                _p(next_plan.wfrag_rows) if next_plan is not None else None, _p(next_plan.bias) if next_plan is not None else None, dims,
+                ctypes.c_float(scale), ctypes.c_float(plan_1.ln_eps), ctypes.c_float(next_plan.ln_eps if next_plan is not None else 0.0),
+                _stream())
     return out, qkv_next
 
 
@@ -1756,8 +1700,7 @@ def softmax_argmax(seg_logits):
     n, c, h, w = x.shape
     prob = torch.empty((n, c, h, w), device=x.device, dtype=torch.float32)
     seg_map = torch.empty((n, h, w), device=x.device, dtype=torch.int64)
-    rc = _L.load().cobevt_softmax_argmax(_p(x), _p(prob), _p(seg_map), dcode(x.dtype), n, c, h * w, _stream())
-    _L.check(rc, "cobevt_softmax_argmax")
+    _L.call("cobevt_softmax_argmax", _p(x), _p(prob), _p(seg_map), dcode(x.dtype), n, c, h * w, _stream())
     return prob, seg_map
 
 
@@ -1771,8 +1714,7 @@ def seg_class_counts(pred, gt, num_classes):
     p64, g64 = pred.to(torch.int64).contiguous(), gt.to(torch.int64).contiguous()
     n, h, w = p64.shape
     counts = torch.empty((n, num_classes + 1, 3), device=pred.device, dtype=torch.int64)
-    rc = _L.load().cobevt_seg_class_counts(_p(p64), _p(g64), _p(counts), n, h * w, num_classes, _stream())
-    _L.check(rc, "cobevt_seg_class_counts")
+    _L.call("cobevt_seg_class_counts", _p(p64), _p(g64), _p(counts), n, h * w, num_classes, _stream())
     host = counts.cpu()
     if int(host[:, num_classes, 0].sum()) or int(host[:, num_classes, 1].sum()):
         raise CobevtHipError("seg_class_counts: labels outside [0, %d)" % num_classes)
@@ -1823,8 +1765,7 @@ def depthwise_conv(x, plan):
         return 2.0 * n * ho * wo * c * plan.k * plan.k, float((x.numel() + out.numel()) * esz)
 
     with _timed("depthwise|%dx%d s%d C%d %dx%d" % (plan.k, plan.k, plan.stride, c, h, w), cost):
-        rc = _L.load().cobevt_depthwise_conv_nhwc(_p(x), _p(plan.wgt), _p(plan.bias), _p(out), dims, _stream())
-    _L.check(rc, "cobevt_depthwise_conv_nhwc")
+        _L.call("cobevt_depthwise_conv_nhwc", _p(x), _p(plan.wgt), _p(plan.bias), _p(out), dims, _stream())
     return out
 
 
@@ -1835,8 +1776,7 @@ def spatial_mean(x):
     if not x.is_contiguous():
         raise CobevtHipError("spatial_mean: input must be contiguous channels-last")
     out = torch.empty((n, c), device=x.device, dtype=torch.float32)
-    rc = _L.load().cobevt_spatial_mean_nhwc(_p(x), _p(out), dcode(x.dtype), n, h * w, c, _stream())
-    _L.check(rc, "cobevt_spatial_mean_nhwc")
+    _L.call("cobevt_spatial_mean_nhwc", _p(x), _p(out), dcode(x.dtype), n, h * w, c, _stream())
     return out
 
 
@@ -1849,8 +1789,7 @@ def se_gate(mean, w_reduce, b_reduce, w_expand, b_expand):
     if tuple(w_reduce.shape) != (cs, c) or tuple(w_expand.shape) != (c, cs) or b_reduce.numel() != cs or b_expand.numel() != c:
         raise CobevtHipError("se_gate: inconsistent shapes")
     gate = torch.empty((n, c), device=mean.device, dtype=torch.float32)
-    rc = _L.load().cobevt_se_gate(_p(mean), _p(w_reduce), _p(b_reduce), _p(w_expand), _p(b_expand), _p(gate), n, c, cs, _stream())
-    _L.check(rc, "cobevt_se_gate")
+    _L.call("cobevt_se_gate", _p(mean), _p(w_reduce), _p(b_reduce), _p(w_expand), _p(b_expand), _p(gate), n, c, cs, _stream())
     return gate
 
 
@@ -1861,8 +1800,7 @@ def channel_gate(x, gate):
     if tuple(gate.shape) != (n, c) or gate.dtype != torch.float32 or not x.is_contiguous() or not gate.is_contiguous():
         raise CobevtHipError("channel_gate: gate must be (N, C) fp32 for a contiguous (N, H, W, C) map")
     out = torch.empty_like(x)
-    rc = _L.load().cobevt_channel_gate_nhwc(_p(x), _p(gate), _p(out), dcode(x.dtype), n, h * w, c, _stream())
-    _L.check(rc, "cobevt_channel_gate_nhwc")
+    _L.call("cobevt_channel_gate_nhwc", _p(x), _p(gate), _p(out), dcode(x.dtype), n, h * w, c, _stream())
     return out
 
 
@@ -1921,8 +1859,7 @@ def weighted_cross_entropy(logits, target, weight, want_stats=False):
         raise CobevtHipError("weighted_cross_entropy: %d class weights for %d classes" % (wt.numel(), c))
     scratch = torch.empty(3 * n * ((h * w + 4095) // 4096), device=x.device, dtype=torch.float32)
     out = torch.empty(4, device=x.device, dtype=torch.float32)
-    rc = _L.load().cobevt_weighted_cross_entropy(_p(x), _p(y), _p(wt), _p(scratch), _p(out), dcode(x.dtype), n, c, h * w, _stream())
-    _L.check(rc, "cobevt_weighted_cross_entropy")
+    _L.call("cobevt_weighted_cross_entropy", _p(x), _p(y), _p(wt), _p(scratch), _p(out), dcode(x.dtype), n, c, h * w, _stream())
     # nn.CrossEntropyLoss raises for targets outside [0, C) other than ignore_index = -100.  Here the count of such labels leaves the
     # device WITHOUT a host sync (a blocking read would drain the launch queue twice per training step): it is copied into a pinned
     # host word behind the kernel and inspected by the following calls (and by check_deferred_label_errors()), so a bad label
@@ -1952,9 +1889,8 @@ def iou_counts(pred, label, visibility, label_indices, thresholds, min_visibilit
     if min_visibility is not None:
         vis = visibility.to(device=dev, dtype=torch.uint8).contiguous()
         mv = int(min_visibility)
-    rc = _L.load().cobevt_iou_counts(_p(pred.contiguous()), _p(label), _p(vis), _p(masks), _p(thr), _p(counts), n, c, nl, hw,
-                                     thr.numel(), mv, _stream())
-    _L.check(rc, "cobevt_iou_counts")
+    _L.call("cobevt_iou_counts", _p(pred.contiguous()), _p(label), _p(vis), _p(masks), _p(thr), _p(counts), n, c, nl, hw, thr.numel(), mv,
+            _stream())
     return counts.cpu()
 
 
@@ -1977,7 +1913,6 @@ def sigmoid_focal_loss_mean(pred, label, visibility, label_indices, min_visibili
         vis, mv = visibility.to(device=dev, dtype=torch.uint8).contiguous(), int(min_visibility)
     scratch = torch.empty(2 * n * ((hw + 2047) // 2048), device=dev, dtype=torch.float32)
     out = torch.empty(3, device=dev, dtype=torch.float32)
-    rc = _L.load().cobevt_sigmoid_focal_loss(_p(pred.float().contiguous()), _p(label), _p(vis), _p(masks), _p(scratch), _p(out), n, c, nl,
-                                             hw, mv, ctypes.c_float(alpha), ctypes.c_float(gamma), int(soft), _stream())
-    _L.check(rc, "cobevt_sigmoid_focal_loss")
+    _L.call("cobevt_sigmoid_focal_loss", _p(pred.float().contiguous()), _p(label), _p(vis), _p(masks), _p(scratch), _p(out), n, c, nl, hw,
+            mv, ctypes.c_float(alpha), ctypes.c_float(gamma), int(soft), _stream())
     return out[0]

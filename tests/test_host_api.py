@@ -67,6 +67,10 @@ def test_c_abi_exports_every_declared_symbol():
     # argument validation happens before any launch: null pointers are rejected without touching a device
     dims = (ctypes.c_int * 21)(*([0] * 21))
     assert l.cobevt_conv2d_nhwc(None, None, None, None, None, None, None, None, dims, None) == 1
+    # ... and through the checked call path that status raises, under the symbol's own name with the library's text for it
+    with pytest.raises(CobevtHipError) as e:
+        lib.call("cobevt_conv2d_nhwc", None, None, None, None, None, None, None, None, dims, None)
+    assert str(e.value) == "cobevt_conv2d_nhwc failed: %s (code 1)" % l.cobevt_strerror(1).decode()
 
 
 def test_second_library_and_compute_modes():
