@@ -11,10 +11,7 @@ the convolution family follows a bf16 autocast region (bf16 storage, fp32 master
 
 No CPU path: every Function raises on CPU tensors (lib.CobevtHipError) like the inference ops do.
 
-Library variant: every launch below is `_L.call(..., variant="")`, the native library, whatever host.set_compute_dtype selected for INFERENCE
-(under "fp32_split" / "fp32_fast" the process-global variant would otherwise route train_rows.hip and attention_bwd.hip
-through split products while wgrad3 and the rest stayed exact - a mixed, untested training arithmetic).  The split matrix paths are
-inference modes; training is exact fp32 or bf16 autocast.
+Library variant: every launch below goes through `_call`, i.e. to the native library.
 """
 import ctypes
 
@@ -25,6 +22,14 @@ from . import ops
 from .lib import CobevtHipError
 
 _p, _stream, _ints, _need_cuda = ops._p, ops._stream, ops._ints, ops._need_cuda
+
+
+def _call(name, *args):
+    """Every launch of this module: the entry point `name` of the NATIVE library, whatever host.set_compute_dtype selected for INFERENCE
+    (under "fp32_split" / "fp32_fast" the process-global variant would otherwise route train_rows.hip and attention_bwd.hip
+    through split products while wgrad3 and the rest stayed exact - a mixed, untested training arithmetic).  The split matrix paths are
+    inference modes; training is exact fp32 or bf16 autocast."""
+    _L.call(name, *args, variant="")
 
 # Mixed precision (train_camera.py:123-124,157-160,174-177: `--half` = torch.cuda.amp.autocast + GradScaler): inside an autocast
 # region every Function below receives its floating-point inputs cast to fp32 and runs with autocast off - the HIP kernels of
@@ -134,8 +139,8 @@ class WindowAttentionFn(torch.autograd.Function):
         out = torch.empty((out_rows, d), device=q.device, dtype=torch.float32)
         lse = torch.empty((batch, L, heads, nq), device=q.device, dtype=torch.float32)
         dims = _attn_dims(batch, heads, ldq, ldk, ldv, d, table, bias_L, qmap, kmap, omap)
-        _L.call("cobevt_window_attention_lse", _p(q), _p(k), _p(v), _p(out), _p(lse), _p(table), _p(mk), dims, ctypes.c_float(scale),
-                ctypes.c_float(drop_p), ctypes.c_uint(drop_seed), _p(seed_dev), _stream(), variant="")
+        _call("cobevt_window_attention_lse", _p(q), _p(k), _p(v), _p(out), _p(lse), _p(table), _p(mk), dims, ctypes.c_float(scale),
+              ctypes.c_float(drop_p), ctypes.c_uint(drop_seed), _p(seed_dev), _stream())
         ctx.save_for_backward(q, k, v, out, lse, table, mk)
         ctx.cfg = cfg
         return (out, lse * _LN2) if want_lse else out
@@ -161,9 +166,9 @@ class WindowAttentionFn(torch.autograd.Function):
             dims = _attn_dims(batch, heads, d, d, d, d, table, bias_L, qmap, kmap, omap)
         if bf16_mm:
             dims[0] |= 0x100 if USE_ATTN_KV2 else 0x300   # the five products on the bf16 matrix path (operands rounded as they are staged; softmax, sums fp32)
-        _L.call("cobevt_window_attention_bwd", _p(q), _p(k), _p(v), _p(out), _p(lse), _p(dout), _p(dl), _p(dq), _p(dk), _p(dv), _p(dbias),
-                _p(table), _p(mk), dims, ctypes.c_float(scale), ctypes.c_float(drop_p), ctypes.c_uint(drop_seed), _p(seed_dev),
-                _stream(), variant="")
+        _call("cobevt_window_attention_bwd", _p(q), _p(k), _p(v), _p(out), _p(lse), _p(dout), _p(dl), _p(dq), _p(dk), _p(dv), _p(dbias),
+              _p(table), _p(mk), dims, ctypes.c_float(scale), ctypes.c_float(drop_p), ctypes.c_uint(drop_seed), _p(seed_dev),
+              _stream())
         return dq, dk, dv, dbias, None, None
 
 
@@ -189,8 +194,8 @@ class WindowSelfAttentionFn(torch.autograd.Function):
         lse = torch.empty((batch, L, heads, nq), device=qkv.device, dtype=torch.float32)
         q, k, v = qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:]
         dims = _attn_dims(batch, heads, 3 * d, 3 * d, 3 * d, d, table, bias_L, qmap, kmap, omap)
-        _L.call("cobevt_window_attention_lse", _p(q), _p(k), _p(v), _p(out), _p(lse), _p(table), _p(mk), dims, ctypes.c_float(scale),
-                ctypes.c_float(drop_p), ctypes.c_uint(drop_seed), _p(seed_dev), _stream(), variant="")
+        _call("cobevt_window_attention_lse", _p(q), _p(k), _p(v), _p(out), _p(lse), _p(table), _p(mk), dims, ctypes.c_float(scale),
+              ctypes.c_float(drop_p), ctypes.c_uint(drop_seed), _p(seed_dev), _stream())
         ctx.save_for_backward(qkv, out, lse, table, mk)
         ctx.cfg = cfg
         return out
@@ -208,9 +213,9 @@ class WindowSelfAttentionFn(torch.autograd.Function):
             dims[0] |= 0x100 if USE_ATTN_KV2 else 0x300
         q, k, v = qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:]
         dq, dk, dv = dqkv[:, :d], dqkv[:, d:2 * d], dqkv[:, 2 * d:]
-        _L.call("cobevt_window_attention_bwd", _p(q), _p(k), _p(v), _p(out), _p(lse), _p(dout), None, _p(dq), _p(dk), _p(dv), _p(dbias),
-                _p(table), _p(mk), dims, ctypes.c_float(scale), ctypes.c_float(drop_p), ctypes.c_uint(drop_seed), _p(seed_dev),
-                _stream(), variant="")
+        _call("cobevt_window_attention_bwd", _p(q), _p(k), _p(v), _p(out), _p(lse), _p(dout), None, _p(dq), _p(dk), _p(dv), _p(dbias),
+              _p(table), _p(mk), dims, ctypes.c_float(scale), ctypes.c_float(drop_p), ctypes.c_uint(drop_seed), _p(seed_dev),
+              _stream())
         return dqkv, dbias, None, None
 
 
@@ -263,8 +268,8 @@ class WindowAttentionHalfFn(torch.autograd.Function):
         lse = torch.empty((2, batch, L, heads, nq), device=q.device, dtype=torch.float32)
         dims = _attn_dims(batch, heads, q.stride(0), k.stride(0), v.stride(0), d, table, bias_L, qmap, kmap, omap)
         dims[0] = ops.BF16
-        _L.call("cobevt_window_attention_lse", _p(q), _p(k), _p(v), _p(out), _p(lse), _p(table), _p(mk), dims, ctypes.c_float(scale),
-                ctypes.c_float(0.0), ctypes.c_uint(0), None, _stream(), variant="")
+        _call("cobevt_window_attention_lse", _p(q), _p(k), _p(v), _p(out), _p(lse), _p(table), _p(mk), dims, ctypes.c_float(scale),
+              ctypes.c_float(0.0), ctypes.c_uint(0), None, _stream())
         if fused:
             ctx.save_for_backward(qkv, out, lse, table, mk)
         else:
@@ -292,8 +297,8 @@ class WindowAttentionHalfFn(torch.autograd.Function):
         dbias = None if table is None else _zeros(table.shape, table.device, table.dtype)
         dims = _attn_dims(batch, heads, q.stride(0), k.stride(0), v.stride(0), d, table, bias_L, qmap, kmap, omap)
         dims[0] = ops.BF16 | 0x100 | (0x400 if USE_ATTN_D_SCRATCH else 0)
-        _L.call("cobevt_window_attention_bwd", _p(q), _p(k), _p(v), _p(out), _p(lse), _p(dout), None, _p(dq), _p(dk), _p(dv), _p(dbias),
-                _p(table), _p(mk), dims, ctypes.c_float(scale), ctypes.c_float(0.0), ctypes.c_uint(0), None, _stream(), variant="")
+        _call("cobevt_window_attention_bwd", _p(q), _p(k), _p(v), _p(out), _p(lse), _p(dout), None, _p(dq), _p(dk), _p(dv), _p(dbias),
+              _p(table), _p(mk), dims, ctypes.c_float(scale), ctypes.c_float(0.0), ctypes.c_uint(0), None, _stream())
         if ctx.fused:
             return dqkv, None, None, dbias, None, None, None
         return dq, dk, dv, dbias, None, None, None
@@ -348,8 +353,8 @@ def attention_dropout_mask(batch, windows, heads, nq, nk, drop_p, drop_seed, dev
     """bool (batch, windows, heads, nq, nk): the keep mask the training kernels use for (drop_p, drop_seed) (test hook)"""
     keep = torch.empty((batch, windows, heads, nq, nk), device=device, dtype=torch.uint8)
     _need_cuda(keep)
-    _L.call("cobevt_attention_dropout_mask", batch, windows, heads, nq, nk, ctypes.c_float(drop_p), ctypes.c_uint(drop_seed), _p(keep),
-            _stream(), variant="")
+    _call("cobevt_attention_dropout_mask", batch, windows, heads, nq, nk, ctypes.c_float(drop_p), ctypes.c_uint(drop_seed), _p(keep),
+          _stream())
     return keep.bool()
 
 
@@ -379,8 +384,8 @@ class LayerNormFn(torch.autograd.Function):
         else:
             C = x.shape[-1]
             y = torch.empty(x.shape, device=x.device, dtype=torch.bfloat16 if out_bf16 else torch.float32)
-            _L.call("cobevt_layernorm_fwd_t", _p(x), _p(g), _p(b), _p(y), x.numel() // C, C, ctypes.c_float(eps),
-                    _ints([ops.dcode(x.dtype), ops.dcode(y.dtype)]), _stream(), variant="")
+            _call("cobevt_layernorm_fwd_t", _p(x), _p(g), _p(b), _p(y), x.numel() // C, C, ctypes.c_float(eps),
+                  _ints([ops.dcode(x.dtype), ops.dcode(y.dtype)]), _stream())
         ctx.save_for_backward(x, g)
         ctx.eps = eps
         return y
@@ -397,10 +402,10 @@ class LayerNormFn(torch.autograd.Function):
         dg = _zeros(C, x.device, torch.float32)
         db = _zeros(C, x.device, torch.float32)
         if x.dtype == torch.float32 and dy.dtype == torch.float32:
-            _L.call("cobevt_layernorm_bwd", _p(x), _p(dy), _p(g), _p(dx), _p(dg), _p(db), rows, C, ctypes.c_float(ctx.eps), _stream(), variant="")
+            _call("cobevt_layernorm_bwd", _p(x), _p(dy), _p(g), _p(dx), _p(dg), _p(db), rows, C, ctypes.c_float(ctx.eps), _stream())
         else:
-            _L.call("cobevt_layernorm_bwd_t", _p(x), _p(dy), _p(g), _p(dx), _p(dg), _p(db), rows, C, ctypes.c_float(ctx.eps),
-                    _ints([ops.dcode(x.dtype), ops.dcode(dy.dtype), ops.dcode(dx.dtype)]), _stream(), variant="")
+            _call("cobevt_layernorm_bwd_t", _p(x), _p(dy), _p(g), _p(dx), _p(dg), _p(db), rows, C, ctypes.c_float(ctx.eps),
+                  _ints([ops.dcode(x.dtype), ops.dcode(dy.dtype), ops.dcode(dx.dtype)]), _stream())
         return dx, dg, db, None, None
 
 
@@ -426,10 +431,10 @@ class GeluFn(torch.autograd.Function):
         x = x if x.is_contiguous() else x.contiguous()
         y = torch.empty_like(x)
         if x.dtype == torch.bfloat16:
-            _L.call("cobevt_gelu_bf16", _p(x), None, _p(y), x.numel(), _stream(), variant="")
+            _call("cobevt_gelu_bf16", _p(x), None, _p(y), x.numel(), _stream())
         else:
             x = _f32c(x, "gelu input")
-            _L.call("cobevt_gelu", _p(x), None, _p(y), x.numel(), _stream(), variant="")
+            _call("cobevt_gelu", _p(x), None, _p(y), x.numel(), _stream())
         ctx.save_for_backward(x)
         return y
 
@@ -440,9 +445,9 @@ class GeluFn(torch.autograd.Function):
         dy = dy if dy.is_contiguous() else dy.contiguous()
         dx = torch.empty_like(x)
         if x.dtype == torch.bfloat16:
-            _L.call("cobevt_gelu_bf16", _p(x), _p(dy), _p(dx), x.numel(), _stream(), variant="")
+            _call("cobevt_gelu_bf16", _p(x), _p(dy), _p(dx), x.numel(), _stream())
         else:
-            _L.call("cobevt_gelu", _p(x), _p(dy), _p(dx), x.numel(), _stream(), variant="")
+            _call("cobevt_gelu", _p(x), _p(dy), _p(dx), x.numel(), _stream())
         return dx
 
 
@@ -471,12 +476,12 @@ def column_sum(rows2d):
     acc = torch.empty(c, device=rows2d.device, dtype=torch.float64)
     if c % 8:
         out = torch.empty(c, device=rows2d.device, dtype=torch.float32)
-        _L.call("cobevt_channel_sums", _p(rows2d), None, _p(acc), None, None, None, 0, ops.dcode(rows2d.dtype), m, c, _stream(), variant="")
-        _L.call("cobevt_f64_to_f32", _p(acc), _p(out), c, _stream(), variant="")
+        _call("cobevt_channel_sums", _p(rows2d), None, _p(acc), None, None, None, 0, ops.dcode(rows2d.dtype), m, c, _stream())
+        _call("cobevt_f64_to_f32", _p(acc), _p(out), c, _stream())
         return out
     out = torch.empty(c, device=rows2d.device, dtype=torch.float32)
-    _L.call("cobevt_channel_sums", _p(rows2d), None, _p(acc), None, _p(out), _p(_scratch(c, rows2d.device)), _SCRATCH_BLOCKS,
-            ops.dcode(rows2d.dtype), m, c, _stream(), variant="")
+    _call("cobevt_channel_sums", _p(rows2d), None, _p(acc), None, _p(out), _p(_scratch(c, rows2d.device)), _SCRATCH_BLOCKS,
+          ops.dcode(rows2d.dtype), m, c, _stream())
     return out
 
 
@@ -585,7 +590,7 @@ def conv_weight_rows(weight, dtype, fwd=True, dgrad=False):
     rf = torch.empty((cout, kpf), device=w.device, dtype=dtype) if fwd else None
     rd = torch.empty((cin, kpd), device=w.device, dtype=dtype) if dgrad else None
     dims = _ints([ops.dcode(dtype), cout, cin, kh, kw, kpf, kpd])
-    _L.call("cobevt_conv_weight_rows", _p(w), _p(rf), _p(rd), dims, _stream(), variant="")
+    _call("cobevt_conv_weight_rows", _p(w), _p(rf), _p(rd), dims, _stream())
     return rf, rd
 
 
@@ -604,7 +609,7 @@ def _igemm_rows(x, w2, cout, cin, kh, kw, bias, stride, pad, ho, wo):
     out = torch.empty((n, ho, wo, cout), device=x.device, dtype=w2.dtype)
     dims = _ints([ops.BF16 if bf16 else ops.FP32, n, h, w, cin, ho, wo, cout, kh, kw, stride, pad, K, kpad, 0, 0, 0, 0, ho, wo, smallc])
     b = None if bias is None else _f32c(bias.detach().float(), "bias")
-    _L.call("cobevt_conv2d_nhwc", _p(x), _p(w2), _p(b), None, None, None, _p(klut), _p(out), dims, _stream(), variant="")
+    _call("cobevt_conv2d_nhwc", _p(x), _p(w2), _p(b), None, None, None, _p(klut), _p(out), dims, _stream())
     return out
 
 
@@ -631,8 +636,8 @@ def conv3_weight_operand(weight, variant, dgrad):
         op = torch.empty(((o + 127) // 128 * 4, i // 64, 9, 4, 64, 8), device=w.device, dtype=torch.bfloat16)
     else:
         op = torch.empty((o, i // 64, 9, 64), device=w.device, dtype=torch.bfloat16)
-    _L.call("cobevt_conv3_weight_operands", _p(w), _p(op) if variant else None, None if variant else _p(op), _ints([cout, cin, int(dgrad)]),
-            _stream(), variant="")
+    _call("cobevt_conv3_weight_operands", _p(w), _p(op) if variant else None, None if variant else _p(op), _ints([cout, cin, int(dgrad)]),
+          _stream())
     return op
 
 
@@ -649,7 +654,7 @@ def conv3_weight_operand_pair(weight, var_f, var_d):
     d = buf(cin, cout, var_d) if var_d >= 0 else None
     outs = (ctypes.c_void_p * 4)(f.data_ptr() if var_f else None, None if var_f else f.data_ptr(),
                                  d.data_ptr() if (d is not None and var_d) else None, d.data_ptr() if (d is not None and not var_d) else None)
-    _L.call("cobevt_conv3_weight_operands2", _p(w), outs, _ints([cout, cin]), _stream(), variant="")
+    _call("cobevt_conv3_weight_operands2", _p(w), outs, _ints([cout, cin]), _stream())
     return f, d
 
 
@@ -662,10 +667,10 @@ def _conv3_strips(x, operand, variant, cout, bias, stride):
     b = None if bias is None else _f32c(bias.detach().float(), "bias")
     if variant:
         dims = _ints([ops.BF16, n, h, w, cin, cout, 0, 0, 0, 64, (cout + 127) // 128 * 128, variant, stride])
-        _L.call("cobevt_conv3x3_wfrag_nhwc", _p(x), _p(operand), _p(b), None, _p(out), dims, _stream(), variant="")
+        _call("cobevt_conv3x3_wfrag_nhwc", _p(x), _p(operand), _p(b), None, _p(out), dims, _stream())
     else:
         dims = _ints([ops.BF16, n, h, w, cin, cout, 0, 0, 0, 64])
-        _L.call("cobevt_conv3x3_nhwc", _p(x), _p(operand), _p(b), None, _p(out), dims, _stream(), variant="")
+        _call("cobevt_conv3x3_nhwc", _p(x), _p(operand), _p(b), None, _p(out), dims, _stream())
     return out
 
 
@@ -680,7 +685,7 @@ def linear_weight_frags(weight2d, forward=True, transposed=False):
     np_, kp = (n + 127) // 128 * 128, (k + 127) // 128 * 128
     f = torch.empty((np_ // 32, kp // 16, 64, 8), device=w.device, dtype=torch.bfloat16) if forward else None
     t = torch.empty((kp // 32, np_ // 16, 64, 8), device=w.device, dtype=torch.bfloat16) if transposed else None
-    _L.call("cobevt_linear_weight_frags", _p(w), _p(f), _p(t), _ints([n, k]), _stream(), variant="")
+    _call("cobevt_linear_weight_frags", _p(w), _p(f), _p(t), _ints([n, k]), _stream())
     return f, t
 
 
@@ -690,7 +695,7 @@ def _rows_gemm(x2d, frag, n_out, k_in, bias):
     out = torch.empty((m, n_out), device=x2d.device, dtype=torch.bfloat16)
     b = None if bias is None else _f32c(bias.detach().float(), "bias")
     d3 = (ctypes.c_long * 14)(ops.BF16, m, n_out, k_in, k_in, 0, 0, 0, 1, m, 1, m, 1, 32)
-    _L.call("cobevt_linear_rows_small_k", _p(x2d), _p(frag), _p(b), None, None, None, _p(out), d3, ctypes.c_float(0.0), _stream(), variant="")
+    _call("cobevt_linear_rows_small_k", _p(x2d), _p(frag), _p(b), None, None, None, _p(out), d3, ctypes.c_float(0.0), _stream())
     return out
 
 
@@ -761,8 +766,8 @@ def blocked_operands(xl, dyl, k, pad, stride=1, mode=0):
         return xb, db, hp, nxb, ndb
     xb = torch.empty((n, hp, nxb, planes, cin, 8), device=xl.device, dtype=xl.dtype)
     db = torch.empty((n, ho, ndb, 1, cout, 8), device=xl.device, dtype=xl.dtype)
-    _L.call("cobevt_wgrad_block_operand", _p(xl), _p(xb), _ints([n, h, w, cin, hp, nxb, pad, pad, planes, sx]), _stream(), variant="")
-    _L.call("cobevt_wgrad_block_operand", _p(dyl), _p(db), _ints([n, ho, wo, cout, ho, ndb, 0, 0, 1, 1]), _stream(), variant="")
+    _call("cobevt_wgrad_block_operand", _p(xl), _p(xb), _ints([n, h, w, cin, hp, nxb, pad, pad, planes, sx]), _stream())
+    _call("cobevt_wgrad_block_operand", _p(dyl), _p(db), _ints([n, ho, wo, cout, ho, ndb, 0, 0, 1, 1]), _stream())
     return xb, db, hp, nxb, ndb
 
 
@@ -846,12 +851,12 @@ class Conv2dFn(torch.autograd.Function):
             # a dense projection: dy^T x over the rows (csrc/wgrad3.hip), dw written, partial sums in a scratch buffer
             dw = torch.empty((cout, cin, 1, 1), device=dyl.device, dtype=torch.float32)
             scratch = torch.empty((chunks1, cout * cin), device=dyl.device, dtype=torch.float32)
-            _L.call("cobevt_linear_wgrad", _p(xl), _p(dyl), _p(dw), _p(scratch), (ctypes.c_long * 4)(n * h * w, cin, cout, chunks1), _stream(), variant="")
+            _call("cobevt_linear_wgrad", _p(xl), _p(dyl), _p(dw), _p(scratch), (ctypes.c_long * 4)(n * h * w, cin, cout, chunks1), _stream())
         elif chunks3 > 0:
             # straight from the channels-last maps (csrc/wgrad3.hip): dw is written, partial sums in a scratch buffer
             dw = torch.empty((cout, cin, kh, kw), device=dyl.device, dtype=torch.float32)
             scratch = torch.empty((chunks3, cout * cin * 9), device=dyl.device, dtype=torch.float32)
-            _L.call("cobevt_conv_wgrad3", _p(xl), _p(dyl), _p(dw), _p(scratch), _ints([n, h, w, cin, cout, chunks3]), _stream(), variant="")
+            _call("cobevt_conv_wgrad3", _p(xl), _p(dyl), _p(dw), _p(scratch), _ints([n, h, w, cin, cout, chunks3]), _stream())
         elif ctx.needs_input_grad[1]:
             dw = _zeros((cout, cin, kh, kw), dyl.device, torch.float32)
             mode = wgrad_blocked_mode(kh, stride, pad, cin) if (USE_WGRAD_BLOCKED and xl.dtype == torch.bfloat16 and kh == kw) else None
@@ -860,10 +865,10 @@ class Conv2dFn(torch.autograd.Function):
             if mode is not None:
                 x_blk, dy_blk, hp, nxb, ndb = blocked_operands(xl, dyl, kh, pad, stride, mode)
                 dims = _ints([n, hp, nxb, cin, ho, ndb, cout, kh, stride, mode])
-                _L.call("cobevt_conv_wgrad_blocked", _p(x_blk), _p(dy_blk), _p(dw), dims, _stream(), variant="")
+                _call("cobevt_conv_wgrad_blocked", _p(x_blk), _p(dy_blk), _p(dw), dims, _stream())
             else:
                 dims = _ints([n, h, w, cin, ho, wo, cout, kh, stride, pad, ops.BF16 if xl.dtype == torch.bfloat16 else ops.FP32])
-                _L.call("cobevt_conv_wgrad", _p(xl), _p(dyl), _p(dw), dims, _stream(), variant="")
+                _call("cobevt_conv_wgrad", _p(xl), _p(dyl), _p(dw), dims, _stream())
         if has_bias and ctx.needs_input_grad[2]:
             db = column_sum(dyl.reshape(-1, cout)).to(ctx.bias_dtype)
         return dx, dw, db, None, None
@@ -922,10 +927,10 @@ class BatchNormActFn(torch.autograd.Function):
         if training:
             # batch statistics: sums of x - running_mean (when there is one: no cancellation in the variance, fp32 partial sums suffice)
             # per workgroup, then one launch that reduces them and finishes every channel incl. the running-stat update
-            _L.call("cobevt_bn_batch_stats", _p(xl), _p(g), _p(b), _p(bn.running_mean) if track else None,
-                    _p(bn.running_var) if track else None, _p(scale), _p(shift), _p(mean), _p(rstd), _p(_scratch(c, dev)), _SCRATCH_BLOCKS,
-                    dt, rows, c, ctypes.c_float(bn.eps), ctypes.c_float(momentum),
-                    _p(bn.num_batches_tracked) if (track and bn.num_batches_tracked is not None) else None, _stream(), variant="")
+            _call("cobevt_bn_batch_stats", _p(xl), _p(g), _p(b), _p(bn.running_mean) if track else None,
+                  _p(bn.running_var) if track else None, _p(scale), _p(shift), _p(mean), _p(rstd), _p(_scratch(c, dev)), _SCRATCH_BLOCKS,
+                  dt, rows, c, ctypes.c_float(bn.eps), ctypes.c_float(momentum),
+                  _p(bn.num_batches_tracked) if (track and bn.num_batches_tracked is not None) else None, _stream())
             if track:
                 # the kernel wrote the running statistics through raw pointers: tell torch, so that everything keyed on a buffer's
                 # version counter - HipModule._plan's folded eval-mode weights, the captured-graph fingerprint of
@@ -935,10 +940,10 @@ class BatchNormActFn(torch.autograd.Function):
                     if t is not None:
                         torch.autograd.graph.increment_version(t)
         else:
-            _L.call("cobevt_bn_finalize", None, None, _p(g), _p(b), _p(bn.running_mean), _p(bn.running_var), _p(scale), _p(shift), _p(mean),
-                    _p(rstd), c, rows, ctypes.c_float(bn.eps), ctypes.c_float(momentum), 0, 0, None, _stream(), variant="")
+            _call("cobevt_bn_finalize", None, None, _p(g), _p(b), _p(bn.running_mean), _p(bn.running_var), _p(scale), _p(shift), _p(mean),
+                  _p(rstd), c, rows, ctypes.c_float(bn.eps), ctypes.c_float(momentum), 0, 0, None, _stream())
         y = torch.empty_like(xl)
-        _L.call("cobevt_bn_apply", _p(xl), _p(rl), _p(scale), _p(shift), _p(y), dt, rows, c, int(act), _stream(), variant="")
+        _call("cobevt_bn_apply", _p(xl), _p(rl), _p(scale), _p(shift), _p(y), dt, rows, c, int(act), _stream())
         ctx.save_for_backward(xl, y if act else None, mean, rstd, g)
         ctx.cfg = (int(act), int(training), residual is not None, gamma is not None, beta is not None,
                    None if gamma is None else gamma.dtype)
@@ -955,8 +960,8 @@ class BatchNormActFn(torch.autograd.Function):
         f = torch.empty((2, c), device=xl.device, dtype=torch.float32) if (has_g or has_b) else None
         dx = torch.empty_like(xl)
         dres = torch.empty_like(xl) if has_res else None
-        _L.call("cobevt_bn_backward", _p(xl), _p(y), _p(dyl), _p(mean), _p(rstd), _p(g), _p(acc), _p(f), _p(_scratch(c, xl.device)),
-                _SCRATCH_BLOCKS, _p(dx), _p(dres), ops.dcode(xl.dtype), rows, c, act, training, _stream(), variant="")
+        _call("cobevt_bn_backward", _p(xl), _p(y), _p(dyl), _p(mean), _p(rstd), _p(g), _p(acc), _p(f), _p(_scratch(c, xl.device)),
+              _SCRATCH_BLOCKS, _p(dx), _p(dres), ops.dcode(xl.dtype), rows, c, act, training, _stream())
         dg = f[0].to(pdt) if has_g else None
         db = f[1].to(pdt) if has_b else None
         return (dx.permute(0, 3, 1, 2), None if dres is None else dres.permute(0, 3, 1, 2), dg, db, None, None, None)
@@ -993,7 +998,7 @@ class GroupMeanFn(torch.autograd.Function):
         b, n = x.shape[:2]
         inner = x.numel() // (b * n)
         out = torch.empty((b,) + tuple(x.shape[2:]), device=x.device, dtype=x.dtype)
-        _L.call("cobevt_group_mean", _p(x), _p(out), ops.dcode(x.dtype), b, n, inner, 0, _stream(), variant="")
+        _call("cobevt_group_mean", _p(x), _p(out), ops.dcode(x.dtype), b, n, inner, 0, _stream())
         ctx.shape = tuple(x.shape)
         ctx.dtype = x.dtype
         return out
@@ -1004,7 +1009,7 @@ class GroupMeanFn(torch.autograd.Function):
         dy = dy.to(ctx.dtype)
         dy = dy if dy.is_contiguous() else dy.contiguous()
         dx = torch.empty(ctx.shape, device=dy.device, dtype=dy.dtype)
-        _L.call("cobevt_group_mean", _p(dy), _p(dx), ops.dcode(dy.dtype), b, n, dy.numel() // b, 1, _stream(), variant="")
+        _call("cobevt_group_mean", _p(dy), _p(dx), ops.dcode(dy.dtype), b, n, dy.numel() // b, 1, _stream())
         return dx
 
 
@@ -1042,7 +1047,7 @@ class FaxBevQueryFn(torch.autograd.Function):
         d = w.shape[0]
         out = torch.empty((B, n, H, W, d), device=grid.device, dtype=torch.float32)
         dims = _ints([B, n, H, W, d, int(round_bf16), kd, int(per_batch)])
-        _L.call("cobevt_fax_bev_query_train", _p(grid), _p(w), _p(bb), _p(c), _p(x), _p(out), dims, _stream(), variant="")
+        _call("cobevt_fax_bev_query_train", _p(grid), _p(w), _p(bb), _p(c), _p(x), _p(out), dims, _stream())
         ctx.save_for_backward(grid, w, bb, c)
         ctx.cfg = (B, n, H, W, d, int(round_bf16), kd, int(per_batch), tuple(weight.shape), bias is not None, x is not None)
         return out
@@ -1056,8 +1061,8 @@ class FaxBevQueryFn(torch.autograd.Function):
         dw = _zeros((d, kd), dq.device, torch.float32)
         db = _zeros(d, dq.device, torch.float32) if has_bias else None
         dc = _zeros((B * n, d), dq.device, torch.float32)
-        _L.call("cobevt_fax_bev_query_train_bwd", _p(grid), _p(w), _p(bb), _p(c), _p(dq), _p(dx), _p(dw), _p(db), _p(dc),
-                _ints([B, n, H, W, d, rb, kd, per_batch]), _stream(), variant="")
+        _call("cobevt_fax_bev_query_train_bwd", _p(grid), _p(w), _p(bb), _p(c), _p(dq), _p(dx), _p(dw), _p(db), _p(dc),
+              _ints([B, n, H, W, d, rb, kd, per_batch]), _stream())
         return dx, None, dw.reshape(wshape), db, dc, None, None
 
 
@@ -1102,7 +1107,7 @@ class MaxPool3x3s2Fn(torch.autograd.Function):
         n, h, w, c = xl.shape
         dyl = _nhwc(dy.to(xl.dtype))
         dx = torch.empty_like(xl)
-        _L.call("cobevt_maxpool3x3s2_bwd_t", _p(xl), _p(dyl), _p(dx), ops.dcode(xl.dtype), n, h, w, c, _stream(), variant="")
+        _call("cobevt_maxpool3x3s2_bwd_t", _p(xl), _p(dyl), _p(dx), ops.dcode(xl.dtype), n, h, w, c, _stream())
         return dx.permute(0, 3, 1, 2)
 
 
@@ -1120,7 +1125,7 @@ def _pixel_unshuffle(tl, inverse):
     else:
         ho, wo, cc = h // 2, w // 2, c
         out = torch.empty((n, ho, wo, 4 * c), device=tl.device, dtype=tl.dtype)
-    _L.call("cobevt_pixel_unshuffle2_nhwc", _p(tl), _p(out), ops.dcode(tl.dtype), n, ho, wo, cc, int(inverse), _stream(), variant="")
+    _call("cobevt_pixel_unshuffle2_nhwc", _p(tl), _p(out), ops.dcode(tl.dtype), n, ho, wo, cc, int(inverse), _stream())
     return out
 
 
@@ -1152,7 +1157,7 @@ def _upsample2(tl, backward):
         out = torch.empty((n, h, w, c), device=tl.device, dtype=tl.dtype)
     else:
         out = torch.empty((n, 2 * h, 2 * w, c), device=tl.device, dtype=tl.dtype)
-    _L.call("cobevt_upsample_nearest2_nhwc", _p(tl), _p(out), ops.dcode(tl.dtype), n, h, w, c, int(backward), _stream(), variant="")
+    _call("cobevt_upsample_nearest2_nhwc", _p(tl), _p(out), ops.dcode(tl.dtype), n, h, w, c, int(backward), _stream())
     return out
 
 
@@ -1202,8 +1207,8 @@ class SttfWarpFn(torch.autograd.Function):
         h, w, c = shape[-3:]
         dout = _f32c(dout.float(), "dout")
         dx = torch.zeros(shape, device=dout.device, dtype=torch.float32)
-        _L.call("cobevt_sttf_warp_bwd", _p(dout), _p(tm), _p(record_len), _p(dx), b, l, h, w, c, ctypes.c_float(ratio),
-                ctypes.c_float(rate), _stream(), variant="")
+        _call("cobevt_sttf_warp_bwd", _p(dout), _p(tm), _p(record_len), _p(dx), b, l, h, w, c, ctypes.c_float(ratio),
+              ctypes.c_float(rate), _stream())
         return dx.to(dt), None, None, None, None, None
 
 
@@ -1231,7 +1236,7 @@ class WeightedCrossEntropyFn(torch.autograd.Function):
         n, c, h, w = x.shape
         dx = torch.empty_like(x)
         up = dloss.reshape(1).to(torch.float32).contiguous()
-        _L.call("cobevt_weighted_cross_entropy_bwd", _p(x), _p(y), _p(wt), _p(stats), _p(up), _p(dx), n, c, h * w, _stream(), variant="")
+        _call("cobevt_weighted_cross_entropy_bwd", _p(x), _p(y), _p(wt), _p(stats), _p(up), _p(dx), n, c, h * w, _stream())
         return dx, None, None
 
 
@@ -1255,7 +1260,7 @@ class SwishFn(torch.autograd.Function):
         if not (xc.is_contiguous() or (xc.dim() == 4 and xc.is_contiguous(memory_format=torch.channels_last))):
             xc = xc.contiguous()
         out = torch.empty_like(xc)                          # same strides
-        _L.call("cobevt_swish", _p(xc), None, _p(out), ops.dcode(xc.dtype), xc.numel(), _stream(), variant="")
+        _call("cobevt_swish", _p(xc), None, _p(out), ops.dcode(xc.dtype), xc.numel(), _stream())
         ctx.save_for_backward(xc)
         return out
 
@@ -1266,7 +1271,7 @@ class SwishFn(torch.autograd.Function):
         if g.stride() != xc.stride():                       # bring the gradient into x's memory order
             g = torch.empty_like(xc).copy_(g)
         dx = torch.empty_like(xc)
-        _L.call("cobevt_swish", _p(xc), _p(g), _p(dx), ops.dcode(xc.dtype), xc.numel(), _stream(), variant="")
+        _call("cobevt_swish", _p(xc), _p(g), _p(dx), ops.dcode(xc.dtype), xc.numel(), _stream())
         return dx
 
 
@@ -1296,7 +1301,7 @@ class DepthwiseConvFn(torch.autograd.Function):
         zero = _zeros(c, xl.device, torch.float32)
         out = torch.empty((n, ho, wo, c), device=xl.device, dtype=xl.dtype)
         dims = _ints([ops.dcode(xl.dtype), n, h, w, c, k, stride, pad[0], pad[0], ho, wo, 0])
-        _L.call("cobevt_depthwise_conv_nhwc", _p(xl), _p(taps), _p(zero), _p(out), dims, _stream(), variant="")
+        _call("cobevt_depthwise_conv_nhwc", _p(xl), _p(taps), _p(zero), _p(out), dims, _stream())
         ctx.save_for_backward(xl, taps, zero)
         ctx.cfg = (int(stride), (int(pad[0]), int(pad[1])), k, weight.dtype)
         return out.permute(0, 3, 1, 2)
@@ -1320,12 +1325,12 @@ class DepthwiseConvFn(torch.autograd.Function):
             dx = torch.empty_like(xl)
             # dx[i] = sum_a dy_stuffed[i + pad0 - a] w[a]  =  correlation of the stuffed gradient with the flipped taps, top / left pad k - 1 - pad0
             dims = _ints([ops.dcode(xl.dtype), n, g.shape[1], g.shape[2], c, k, 1, k - 1 - pad[0], k - 1 - pad[0], h, w, 0])
-            _L.call("cobevt_depthwise_conv_nhwc", _p(g), _p(flipped), _p(zero), _p(dx), dims, _stream(), variant="")
+            _call("cobevt_depthwise_conv_nhwc", _p(g), _p(flipped), _p(zero), _p(dx), dims, _stream())
             dx = dx.permute(0, 3, 1, 2)
         if ctx.needs_input_grad[1]:
             dwt = _zeros((k * k, c), xl.device, torch.float32)
             dims = _ints([ops.dcode(xl.dtype), n, h, w, c, k, stride, pad[0], pad[0], ho, wo])
-            _L.call("cobevt_depthwise_wgrad", _p(xl), _p(dyl), _p(dwt), dims, _stream(), variant="")
+            _call("cobevt_depthwise_wgrad", _p(xl), _p(dyl), _p(dwt), dims, _stream())
             dw = dwt.reshape(k, k, c).permute(2, 0, 1)[:, None].contiguous().to(wdt)
         return dx, dw, None, None
 
@@ -1356,7 +1361,7 @@ class ResizeBilinearFn(torch.autograd.Function):
         n, h, w, c = ctx.shape
         dyl = _nhwc(dy.to(ctx.dt))
         dx = torch.zeros((n, h, w, c), device=dyl.device, dtype=torch.float32)
-        _L.call("cobevt_resize_bilinear_bwd", _p(dyl), _p(dx), ops.dcode(dyl.dtype), n, h, w, c, dyl.shape[1], dyl.shape[2], _stream(), variant="")
+        _call("cobevt_resize_bilinear_bwd", _p(dyl), _p(dx), ops.dcode(dyl.dtype), n, h, w, c, dyl.shape[1], dyl.shape[2], _stream())
         return dx.to(ctx.dt).permute(0, 3, 1, 2), None, None
 
 
@@ -1383,8 +1388,8 @@ class SigmoidFocalLossFn(torch.autograd.Function):
         nl = label.shape[1]
         scratch = torch.empty(2 * n * ((hw + 2047) // 2048), device=pred.device, dtype=torch.float32)
         out = torch.empty(3, device=pred.device, dtype=torch.float32)
-        _L.call("cobevt_sigmoid_focal_loss", _p(p32), _p(label), _p(vis), _p(masks), _p(scratch), _p(out), n, c, nl, hw, min_visibility,
-                ctypes.c_float(alpha), ctypes.c_float(gamma), int(soft), _stream(), variant="")
+        _call("cobevt_sigmoid_focal_loss", _p(p32), _p(label), _p(vis), _p(masks), _p(scratch), _p(out), n, c, nl, hw, min_visibility,
+              ctypes.c_float(alpha), ctypes.c_float(gamma), int(soft), _stream())
         ctx.save_for_backward(p32, label, vis, masks, out)
         ctx.cfg = cfg
         return out[0].clone()
@@ -1396,8 +1401,8 @@ class SigmoidFocalLossFn(torch.autograd.Function):
         n, c, hw = p32.shape
         dp = torch.empty_like(p32)
         gs = g.reshape(1).float().contiguous()
-        _L.call("cobevt_sigmoid_focal_loss_bwd", _p(p32), _p(label), _p(vis), _p(masks), _p(out), _p(gs), _p(dp), n, c, label.shape[1], hw,
-                min_visibility, ctypes.c_float(alpha), ctypes.c_float(gamma), int(soft), _stream(), variant="")
+        _call("cobevt_sigmoid_focal_loss_bwd", _p(p32), _p(label), _p(vis), _p(masks), _p(out), _p(gs), _p(dp), n, c, label.shape[1], hw,
+              min_visibility, ctypes.c_float(alpha), ctypes.c_float(gamma), int(soft), _stream())
         return dp, None, None, None, None
 
 
@@ -1418,8 +1423,8 @@ class PairwiseWarpFn(torch.autograd.Function):
         (n, h, w, c), l, dr, ds = ctx.cfg
         dnb = dnb.contiguous()
         dx = torch.zeros((n, h, w, c), device=dnb.device, dtype=torch.float32)
-        _L.call("cobevt_pairwise_warp_bwd", _p(dnb), _p(pairwise), _p(record_len), _p(dx), ops.dcode(dnb.dtype), record_len.shape[0], l, h,
-                w, c, ctypes.c_float(dr), ctypes.c_float(ds), _stream(), variant="")
+        _call("cobevt_pairwise_warp_bwd", _p(dnb), _p(pairwise), _p(record_len), _p(dx), ops.dcode(dnb.dtype), record_len.shape[0], l, h,
+              w, c, ctypes.c_float(dr), ctypes.c_float(ds), _stream())
         return dx.to(dnb.dtype), None, None, None, None, None
 
 
@@ -1486,7 +1491,7 @@ def pillar_train_stats(weight, gamma, beta, vf, npts, coords, record_len, norm, 
     dims = _ints([p, t, f, k, int(bool(use_abs)), int(bool(dist)), ops.FP32, int(rows), n, nb, int(max_cav or 0), ny, nx])
     gm = (ctypes.c_float * 6)(*[float(v) for v in geom])
     n_stat, n_bwd = ctypes.c_long(0), ctypes.c_long(0)
-    _L.call("cobevt_pillar_train_scratch", p, ctypes.byref(n_stat), ctypes.byref(n_bwd), variant="")
+    _call("cobevt_pillar_train_scratch", p, ctypes.byref(n_stat), ctypes.byref(n_bwd))
     order = torch.empty(max(p, 1), device=dev, dtype=torch.int32)
     dst = torch.empty(max(p, 1), device=dev, dtype=torch.int64)
     count = torch.empty(1, device=dev, dtype=torch.int32)
@@ -1500,9 +1505,9 @@ def pillar_train_stats(weight, gamma, beta, vf, npts, coords, record_len, norm, 
     nbt = norm.num_batches_tracked if track else None
     eps = 0.0 if norm is None else norm.eps
     momentum = 0.0 if (norm is None or norm.momentum is None) else norm.momentum
-    _L.call("cobevt_pillar_train_stats", _p(vf), _p(npts), _p(coords), _p(rl), _p(w), _p(g), _p(b), _p(rm), _p(rv), _p(nbt), _p(order),
-            _p(dst), _p(count), _p(partial), _p(wf), _p(sf), _p(stat), dims, gm, mode, ctypes.c_float(eps), ctypes.c_float(momentum),
-            _stream(), variant="")
+    _call("cobevt_pillar_train_stats", _p(vf), _p(npts), _p(coords), _p(rl), _p(w), _p(g), _p(b), _p(rm), _p(rv), _p(nbt), _p(order),
+          _p(dst), _p(count), _p(partial), _p(wf), _p(sf), _p(stat), dims, gm, mode, ctypes.c_float(eps), ctypes.c_float(momentum),
+          _stream())
     if track:
         # written through raw pointers: bump the version counters (plans folded from the running statistics, graph fingerprints)
         for tns in (norm.running_mean, norm.running_var, norm.num_batches_tracked):
@@ -1530,8 +1535,8 @@ def pillar_train_backward(tensors, dims, gm, mode, n_bwd, k, has_g, has_b, dout)
     dw = torch.empty((ops.PILLAR_CHANNELS, k), device=dev, dtype=torch.float32)
     dg = torch.empty(ops.PILLAR_CHANNELS, device=dev, dtype=torch.float32) if has_g else None
     db = torch.empty(ops.PILLAR_CHANNELS, device=dev, dtype=torch.float32) if has_b else None
-    _L.call("cobevt_pillar_train_bwd", _p(vf), _p(npts), _p(coords), _p(order), _p(dst), _p(count), _p(wf), _p(sf), _p(w), _p(g), _p(stat),
-            _p(dout), _p(partial), _p(dw), _p(dg), _p(db), dims, gm, mode, _stream(), variant="")
+    _call("cobevt_pillar_train_bwd", _p(vf), _p(npts), _p(coords), _p(order), _p(dst), _p(count), _p(wf), _p(sf), _p(w), _p(g), _p(stat),
+          _p(dout), _p(partial), _p(dw), _p(dg), _p(db), dims, gm, mode, _stream())
     return dw, dg, db
 
 
@@ -1609,7 +1614,7 @@ class ScatterRowsFn(torch.autograd.Function):
         (p, c), n, ny, nx = ctx.cfg
         dcanvas = _f32c(dcanvas.float(), "d canvas")
         drows = torch.empty((p, c), device=dcanvas.device, dtype=torch.float32)
-        _L.call("cobevt_gather_rows", _p(dcanvas), _p(coords), _p(drows), ops.FP32, p, c, n, ny, nx, _stream(), variant="")
+        _call("cobevt_gather_rows", _p(dcanvas), _p(coords), _p(drows), ops.FP32, p, c, n, ny, nx, _stream())
         return drows, None, None, None
 
 

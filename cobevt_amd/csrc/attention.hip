@@ -20,6 +20,7 @@
 // lane-local plus one xor-32 exchange.  O^T += V^T.P^T uses the score registers directly as the B
 // operand; the key <-> k-slot permutation this implies is applied identically when reading V^T from LDS.
 #include "attn_common.hpp"
+#include "f32_matrix.hpp"
 
 namespace cobevt {
 
@@ -83,14 +84,14 @@ __global__ __launch_bounds__(512) void attn_gather_kernel(AttnParams p) {
     const TokCoord qc = tok_coord(p.qmap, q_ok ? tq : 0);          // pair mode: tq < P -> camera 0
 
     // Split-bf16 library, fp32 storage (round 6): the K tile and the V^T tile are written to LDS already split into (hi, lo) bf16 halves
-    // (common.hpp stage_x_piece: a staged tile is read by every query tile of the workgroup) and the query fragments are split once per
+    // (f32_matrix.hpp stage_x_piece: a staged tile is read by every query tile of the workgroup) and the query fragments are split once per
     // query tile, so a score MFMA pair has no conversion in front of it and a PV pair only the split of its probabilities - the in-loop
     // form split all four operands per 16-byte piece: ~380 of the ~500 VALU instructions of a 64-key tile against 32 MFMAs.
     // Third library (round 6, "fp32_fast" routes the attention launches to it): K / V^T staged as fp16 (hi, lo) pairs, the query fragments
     // and the probabilities as ONE fp16 term - a single fp16 MFMA per piece, four conversions per probability piece.  tests/precision_emul.py
     // mode fp16_qp: rounding queries and probabilities to fp16 changes the 5-agent frame's logit error in the third digit (2.6-2.9e-4).
-    constexpr bool kStage = (COBEVT_F32_SPLIT != 0) && !Elem<T>::kIsBf16;
-    constexpr bool kStage16 = (COBEVT_F32_SPLIT == 2) && !Elem<T>::kIsBf16;
+    constexpr bool kStage = kXSplit<T>;
+    constexpr bool kStage16 = kXSplit16<T>;
     auto dup_split = [](const uint4& x, uint4& hh, uint4& ll) {           // {x0..x3} -> {hi01, hi23, hi01, hi23}, {lo01, lo23, lo01, lo23}
         if constexpr (kStage16) { hh = dup_f16_piece(x); ll = hh; return; }
         uint32_t h01, h23, l01, l23;
@@ -100,7 +101,7 @@ __global__ __launch_bounds__(512) void attn_gather_kernel(AttnParams p) {
         ll = make_uint4(l01, l23, l01, l23);
     };
     auto mfma_staged_pair = [](const uint4& a_staged, const uint4& b_hh, const uint4& b_ll, f32x16& acc) {
-        if constexpr (kStage16) {       // b_hh = the duplicated fp16 form {b, b / 2^s} (common.hpp dup_f16_piece); b_ll unused
+        if constexpr (kStage16) {       // b_hh = the duplicated fp16 form {b, b / 2^s} (f32_matrix.hpp dup_f16_piece); b_ll unused
             acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a_staged), __builtin_bit_cast(f16x8, b_hh), acc, 0, 0, 0);
         } else {
             acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a_staged), __builtin_bit_cast(bf16x8, b_hh), acc, 0, 0, 0);

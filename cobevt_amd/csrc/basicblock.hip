@@ -17,6 +17,7 @@
 // cobevt_conv3x3_wfrag_nhwc), prefetched two taps ahead; D = W . X^T so a lane owns one pixel and runs of four couts
 // (8-byte LDS writes for the intermediate, 16-byte for the staging).  8 waves = cout tiles x pixel-tile groups.
 #include "common.hpp"
+#include "f32_matrix.hpp"
 
 namespace cobevt {
 
@@ -88,7 +89,7 @@ template <typename T, int NTW>
 __device__ __forceinline__ void bb_conv_chunk(const unsigned char* patch, const int (&aoff)[NTW], const bool (&ok)[NTW],
                                               int row_pitch, int pstr, const uint4* wsrc, int step0, int nstep,
                                               uint4 (&bq)[3][4], f32x16 (&acc)[NTW], int odd_off = -1) {
-    constexpr bool PACK = kXPack<T, 4>;                         // third library: one fp16 per activation, an A operand spans two k-groups (common.hpp)
+    constexpr bool PACK = kXPack<T, 4>;                         // third library: one fp16 per activation, an A operand spans two k-groups (f32_matrix.hpp)
     constexpr bool PACK3 = kXPack3<T, 4>;                       // second library: the three-term form on k-group pairs (hi and lo operands, two ring slots)
     constexpr int KGA = (PACK || PACK3) ? 2 : 4, NG = 9 * KGA, RA = PACK3 ? 2 : 3;
     uint4 af[RA][NTW];

@@ -15,9 +15,10 @@
 //   3. conv3 per 32-cout tile out of that tile; + b3 staged through LDS 64 channels at a time, then + residual + ReLU and 16-byte
 //      coalesced stores (the residual read coalesced as well).
 // Weights arrive as MFMA fragments straight from L2 (the tables of the separate launches: cobevt_linear_rows_small_k's for the 1x1s,
-// cobevt_conv3x3_wfrag_nhwc's for the 3x3).  LDS tiles that only feed MFMA operands are written through stage_x_piece (common.hpp): the
+// cobevt_conv3x3_wfrag_nhwc's for the 3x3).  LDS tiles that only feed MFMA operands are written through stage_x_piece (f32_matrix.hpp): the
 // matrix path is the library's - exact fp32 MFMA or split-bf16.  53 KB per workgroup, three per CU.
 #include "common.hpp"
+#include "f32_matrix.hpp"
 
 namespace cobevt {
 

@@ -16,6 +16,7 @@
 #include <type_traits>
 
 #include "common.hpp"
+#include "f32_matrix.hpp"
 
 namespace cobevt {
 
@@ -254,7 +255,7 @@ __global__ __launch_bounds__(kConv3Threads) void conv3x3_kernel(Conv3Params p) {
         unsigned char* wb = wbuf + buf * C::W_BYTES;
 #pragma unroll
         for (int it = 0; it < W_IT; ++it)
-            if (wlds[it] >= 0) *(uint4*)(wb + wlds[it]) = wzero[it] ? make_uint4(0, 0, 0, 0) : stage_ws_piece<T>(wreg[it]);
+            if (wlds[it] >= 0) *(uint4*)(wb + wlds[it]) = wzero[it] ? make_uint4(0, 0, 0, 0) : stage_w_piece<T>(wreg[it]);
     };
 
     f32x16 acc[2];
@@ -282,7 +283,7 @@ __global__ __launch_bounds__(kConv3Threads) void conv3x3_kernel(Conv3Params p) {
 #pragma unroll
             for (int b = 0; b < 2; ++b) bf[b] = *(const uint4*)(pb + b * 32 * WSTR + g * 32);
 #pragma unroll
-            for (int b = 0; b < 2; ++b) mfma_kgroup_ss<T>(af, bf[b], acc[b]);    // A = pixels, B = weights (both staged: common.hpp)
+            for (int b = 0; b < 2; ++b) mfma_kgroup_ss<T>(af, bf[b], acc[b]);    // A = pixels, B = weights (both staged: f32_matrix.hpp)
         }
         if (step + 1 < nsteps) store_w(RS, buf ^ 1);
         if (tap == 8 && next_chunk) {
@@ -488,10 +489,10 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void conv3x3_strips_kerne
     constexpr int P_IT = S == 1 ? (PATCH_ITEMS + NT - 1) / NT : 1;   // S = 2 refills the patch without resident registers
     constexpr int PF = 2, R = 3;
     // third library, fp32 storage, an even number of k-groups per wave and tap: the patch holds ONE fp16 per activation and a 16-byte
-    // A operand spans two k-groups (common.hpp kXPack) - KGA operand groups per tap instead of KGW
+    // A operand spans two k-groups (f32_matrix.hpp kXPack) - KGA operand groups per tap instead of KGW
     constexpr bool PACK = kXPack<T, KGW>;
     // second library, same condition: the three-term form on k-group pairs - hi and lo operands of a pair as two 16-byte reads, an operand
-    // ring of two slots instead of three (the registers), three MFMAs per pair (common.hpp kXPack3)
+    // ring of two slots instead of three (the registers), three MFMAs per pair (f32_matrix.hpp kXPack3)
     constexpr bool PACK3 = kXPack3<T, KGW>;
     constexpr int KGA = (PACK || PACK3) ? KGW / 2 : KGW;
     constexpr int RA = PACK3 ? 2 : 3;                 // slots of the A-operand ring

@@ -15,6 +15,7 @@
 // caller runs cobevt_layernorm first).  One LDS buffer + register prefetch of the next K-tile; fp32-staged,
 // 16-byte coalesced epilogue (bias, residual, ReLU / exact GELU) as in conv3x3.hip.
 #include "common.hpp"
+#include "f32_matrix.hpp"
 
 namespace cobevt {
 
@@ -237,7 +238,7 @@ __global__ __launch_bounds__(kGrThreads, 4) void gemm_rows_kernel(GemmRowsParams
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             *(uint4*)(As + srow * kGrRow + (sub * 4 + j) * 16) = stage_x_piece<T>(areg[j]);
-            *(uint4*)(Ws + srow * kGrRow + (sub * 4 + j) * 16) = stage_ws_piece<T>(wreg[j]);
+            *(uint4*)(Ws + srow * kGrRow + (sub * 4 + j) * 16) = stage_w_piece<T>(wreg[j]);
         }
     };
 
@@ -265,7 +266,7 @@ __global__ __launch_bounds__(kGrThreads, 4) void gemm_rows_kernel(GemmRowsParams
             const uint4 af = *(const uint4*)(As + abase + g * 32);
             const uint4 b0 = *(const uint4*)(Ws + bbase + g * 32);
             const uint4 b1 = *(const uint4*)(Ws + bbase + 32 * kGrRow + g * 32);
-            mfma_kgroup_ss<T>(af, b0, acc[0]);    // A = activation rows, B = weights (both staged: common.hpp)
+            mfma_kgroup_ss<T>(af, b0, acc[0]);    // A = activation rows, B = weights (both staged: f32_matrix.hpp)
             mfma_kgroup_ss<T>(af, b1, acc[1]);
         }
     }
@@ -542,7 +543,7 @@ __global__ __launch_bounds__(kGrThreads, 2) void gemm_rows2_kernel(GemmRowsParam
 #pragma unroll
                     for (int rt = 0; rt < 2; ++rt) {
                         const uint4 af = *(const uint4*)(As + (wm * 64 + rt * 32 + ql) * kGrRow + h * 16 + g * 32);
-                        mfma_kgroup_xs<T>(bfrag[g], af, acc[rt]);     // D = W . X^T : lane <-> row, registers <-> columns (A rows staged: common.hpp)
+                        mfma_kgroup_xs<T>(bfrag[g], af, acc[rt]);     // D = W . X^T : lane <-> row, registers <-> columns (A rows staged: f32_matrix.hpp)
                     }
                     if (Elem<T>::kIsBf16) {                        // pin "read, MFMA": unpinned, LLVM hoists all 16 fragment
 #pragma unroll                                                      // reads (64 VGPRs) above the MFMAs

@@ -9,6 +9,7 @@
 // pass, weights as MFMA fragments straight from L2 in two ping-pong sets of eight k-groups with the next set in flight, D = W . X^T so
 // bias / residual / activation happen in registers, results leave through an fp32 LDS tile as 16-byte coalesced stores.
 #include "wave_ops.hpp"
+#include "f32_matrix.hpp"
 
 namespace cobevt {
 

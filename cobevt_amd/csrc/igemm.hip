@@ -18,6 +18,7 @@
 // gather for tile t+1 is issued before the MFMAs of tile t.  LDS rows are padded to 80 bytes so the
 // 16-lane ds_read_b128 groups hit distinct banks.
 #include "common.hpp"
+#include "f32_matrix.hpp"
 
 namespace cobevt {
 
@@ -198,7 +199,7 @@ __global__ __launch_bounds__(256) void igemm_kernel(IgemmParams p) {
 #pragma unroll
         for (int it = 0; it < B_IT; ++it) {
             const int br = rowp + 64 * it;
-            if (br < BN) *(uint4*)(Bs + br * kRowBytes + j * 16) = stage_ws_piece<T>(b_reg[it]);
+            if (br < BN) *(uint4*)(Bs + br * kRowBytes + j * 16) = stage_w_piece<T>(b_reg[it]);
         }
     };
 
@@ -231,7 +232,7 @@ __global__ __launch_bounds__(256) void igemm_kernel(IgemmParams p) {
 #pragma unroll
             for (int a = 0; a < TM; ++a)
 #pragma unroll
-                for (int b = 0; b < TN; ++b) mfma_kgroup_ss<T>(af[a], bfr[b], acc[a][b]);    // A = gathered pixels, B = weights (both staged: common.hpp)
+                for (int b = 0; b < TN; ++b) mfma_kgroup_ss<T>(af[a], bfr[b], acc[a][b]);    // A = gathered pixels, B = weights (both staged: f32_matrix.hpp)
         }
         if (kt + 1 < nk) store_tile(buf ^ 1);
         __syncthreads();

@@ -4,7 +4,7 @@
 //            point_pillar_scatter.py:14-47, fuse_utils.py:8-61 (regroup).
 //
 // Arithmetic: fp32 on the VALU in every compute mode and in all three libraries (absolute coordinates reach +-140 m: no bf16 / fp16
-// operand, no MFMA, nothing that depends on COBEVT_F32_SPLIT); only the final store converts to the storage dtype.
+// operand, no MFMA, nothing that differs between the three libraries); only the final store converts to the storage dtype.
 //
 // Layout: a pillar's T <= 32 points sit on the 32 lanes of one half-wave (one 16-byte load per point), so the coordinate mean and the
 // 64 channel maxima are cross-lane reductions inside the half-wave; the folded weight W (K, 64) and shift s (64) are wave-uniform

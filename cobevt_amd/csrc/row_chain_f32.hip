@@ -16,10 +16,11 @@
 // so every K = 128 product is two sets and fc2's K = 256 four), the next set always in flight under the current one's MFMAs.
 // LDS: y stays plain fp32 (the LayerNorm and the residual read it); the tiles that only feed MFMA operand reads - a, LN(y), the hidden
 // activations, the next projection's input - are written through stage_x_piece, i.e. already split into (hi, lo) halves in the
-// split-bf16 / fp16 libraries (common.hpp): the main loops are ds_read_b128 + MFMA, the weight fragment's split is shared by nothing
+// split-bf16 / fp16 libraries (f32_matrix.hpp): the main loops are ds_read_b128 + MFMA, the weight fragment's split is shared by nothing
 // (one 32-row tile per wave) but costs 12 VALU instructions per MFMA pair against 24.  73 KB per workgroup, two per CU.
 #include "row_chain.hpp"
 #include "wave_ops.hpp"
+#include "f32_matrix.hpp"
 
 namespace cobevt {
 

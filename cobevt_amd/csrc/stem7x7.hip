@@ -13,6 +13,7 @@
 // persistent: the weight tile stays in LDS, the next tile's patch is prefetched into registers (fp32 image read once,
 // converted on the fly), and the epilogue is staged through LDS for 16-byte coalesced stores.
 #include "common.hpp"
+#include "f32_matrix.hpp"
 
 namespace cobevt {
 
@@ -377,7 +378,7 @@ __global__ __launch_bounds__(StemPoolCfg<T>::NT) void stem_pool_kernel(StemParam
                 if constexpr (Elem<T>::kIsBf16) *(uint32_t*)dst = pack_bf2(preg[it].x, preg[it].y);
                 else if constexpr (kXSplit<T>) {
                     // second / third library: the 16-byte operand piece {x0..x3} lives in LDS as {hi(x0,x1), hi(x2,x3), lo(x0,x1), lo(x2,x3)}
-                    // (common.hpp stage_x_piece); this float pair is the first or the second half of its piece
+                    // (f32_matrix.hpp stage_x_piece); this float pair is the first or the second half of its piece
                     uint32_t hi, lo;
                     split_pair_staged(preg[it].x, preg[it].y, hi, lo);
                     unsigned char* pb = patch + (pdst[it] & ~15) + ((pdst[it] >> 1) & 4);

@@ -21,7 +21,7 @@ def set_compute_dtype(dtype, matrix_path=None):
     The string "fp32_split" is shorthand for (torch.float32, "split_bf16").
     "fp32_fast" = (torch.float32, "split_bf16_enc_fp16") (round 6): as "fp32_split", except that the ResNet encoder's convolutions -
     80 % of a frame's flops - run on v_mfma_f32_32x32x16_f16 with fp16 OPERANDS out of fp32 storage (libcobevt_hip_f32h.so;
-    csrc/common.hpp COBEVT_F32_SPLIT == 2): the folded weights as one fp16 term, the activations as one fp16 value where a wave owns
+    the third setting of csrc/f32_matrix.hpp): the folded weights as one fp16 term, the activations as one fp16 value where a wave owns
     two k-groups per tap (the packed form: one MFMA per two k-groups - the strip kernels' 128-cout tiles, the BasicBlocks) and as an
     fp16 (hi, lo) pair elsewhere (stem, 64-cout tiles, 1x1 shortcuts).  fp32 accumulation, fp32 storage, every residual added in
     fp32; ~3e-4 max-rel on the 5-agent frame (inside the north-star's 1e-3, not the 1e-5 of "fp32_split").  Precondition: encoder

@@ -154,9 +154,9 @@ SIGNATURES = {
 }
 
 _libs = {}
-# "" = libcobevt_hip.so; "f32s" = libcobevt_hip_f32s.so, the same sources and C ABI built with -DCOBEVT_F32_SPLIT=1: fp32-storage
-# kernels on the split-bf16 matrix path (cobevt_amd/build.py, csrc/common.hpp).  host.set_compute_dtype selects it.
-# "f32h" = libcobevt_hip_f32h.so (-DCOBEVT_F32_SPLIT=2, round 6): fp32 storage, one fp16 MFMA per 16-byte piece with the weight
+# "" = libcobevt_hip.so; "f32s" = libcobevt_hip_f32s.so, the same C ABI with the fp32-storage matrix kernels rebuilt on the split-bf16
+# matrix path and every other object shared (cobevt_amd/build.py, csrc/f32_matrix.hpp).  host.set_compute_dtype selects it.
+# "f32h" = libcobevt_hip_f32h.so (the third setting of f32_matrix.hpp, round 6): fp32 storage, one fp16 MFMA per 16-byte piece with the weight
 # operand as a single fp16 term - half the split-bf16 matrix time at 11-bit weights.  Only the ResNet encoder's convolutions are
 # routed through it, and only under host.set_compute_dtype("fp32_fast"): `set_encoder_variant` names the library `encoder_scope()`
 # switches to for the launches issued inside it (host/resnet_ms.py).

@@ -74,7 +74,7 @@ def test_c_abi_exports_every_declared_symbol():
 
 
 def test_second_library_and_compute_modes():
-    """libcobevt_hip_f32s.so (same sources, -DCOBEVT_F32_SPLIT=1: fp32 storage on the split-bf16 matrix path) loads, exports the whole
+    """libcobevt_hip_f32s.so (the fp32-matrix sources built with -DCOBEVT_F32_SPLIT=1, the other objects shared: fp32 storage on the split-bf16 matrix path) loads, exports the whole
     C ABI, and host.set_compute_dtype selects it - "fp32_split" is fp32 storage, so the lowered plans are shared with exact fp32"""
     l2 = lib.load("f32s")
     assert l2 is not lib.load("") and l2.cobevt_abi_version() == 1

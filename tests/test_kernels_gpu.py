@@ -1578,7 +1578,7 @@ def test_attention_key_split_matches_single_pass(cuda, dtype, use_bias, ncam):
 
 
 # ----------------------------------------------------------------------------------------------------------------------
-# fp32 storage on the split-bf16 matrix path (libcobevt_hip_f32s.so: csrc/common.hpp COBEVT_F32_SPLIT, cobevt_amd/build.py).
+# fp32 storage on the split-bf16 matrix path (libcobevt_hip_f32s.so: csrc/f32_matrix.hpp COBEVT_F32_SPLIT, cobevt_amd/build.py).
 # The same kernel tests as exact fp32, at the same 2e-4 tolerance, with the second library selected.
 # ----------------------------------------------------------------------------------------------------------------------
 def _split_cases():
@@ -1637,7 +1637,7 @@ def test_split_bf16_matrix_path_is_the_one_that_runs(cuda):
 
 
 # ----------------------------------------------------------------------------------------------------------------------
-# fp32 storage, ONE fp16 MFMA per piece (libcobevt_hip_f32h.so: csrc/common.hpp COBEVT_F32_SPLIT == 2; round 6): the ResNet encoder's
+# fp32 storage, ONE fp16 MFMA per piece (libcobevt_hip_f32h.so: csrc/f32_matrix.hpp COBEVT_F32_SPLIT == 2; round 6): the ResNet encoder's
 # library under host.set_compute_dtype("fp32_fast").  The arithmetic is pinned, not just bounded: a kernel must equal the fp64 convolution
 # with the folded weights ROUNDED TO fp16 and the activations either UNROUNDED (the (hi, lo) form: fp16 pairs = 22 bits - the stem, the
 # 64-cout strip tiles, the dense-row kernel) or ROUNDED TO fp16 as well (the packed form: two k-groups per MFMA - the 128-cout strip tiles
