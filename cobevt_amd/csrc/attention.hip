@@ -19,6 +19,7 @@
 // so lane (q = lane&31, half h) holds 16 of the 32 key scores of its query -> softmax reductions are
 // lane-local plus one xor-32 exchange.  O^T += V^T.P^T uses the score registers directly as the B
 // operand; the key <-> k-slot permutation this implies is applied identically when reading V^T from LDS.
+#include <stdlib.h>
 #include "attn_common.hpp"
 #include "f32_matrix.hpp"
 
@@ -543,100 +544,75 @@ __global__ void attn_bias_index_dump_kernel(TokMap qm, TokMap km, int bias_L, in
 
 using namespace cobevt;
 
-// C-ABI entry point, see include/cobevt_hip.h
+// the streaming footprints attn_select.hpp sizes its launches with
+static_assert(AttnLds<bf16_t, 64>::kFixed == kAttnStreamLdsBf16Kt64, "attn_select.hpp: streaming LDS footprint, bf16 / 64-key tiles");
+static_assert(AttnLds<bf16_t, 128>::kFixed == kAttnStreamLdsBf16Kt128, "attn_select.hpp: streaming LDS footprint, bf16 / 128-key tiles");
+static_assert(AttnLds<float, 64>::kFixed == kAttnStreamLdsF32Kt64, "attn_select.hpp: streaming LDS footprint, fp32 / 64-key tiles");
+
+// one (storage type, tile width, dropout) of the streaming kernel: the descriptor's bias / mask booleans -> the instantiation
+template <typename T, int KT, bool DROP = false>
+static void launch_stream(const AttnParams& p, const AttnLaunch& a, hipStream_t stream) {
+    const dim3 grid(a.grid[0], a.grid[1], a.grid[2]), block(a.block);
+    switch (a.BIAS << 1 | a.MASK) {
+        case 3: hipLaunchKernelGGL((attn_gather_kernel<T, true, true, KT, DROP>), grid, block, a.lds, stream, p); break;
+        case 2: hipLaunchKernelGGL((attn_gather_kernel<T, true, false, KT, DROP>), grid, block, a.lds, stream, p); break;
+        case 1: hipLaunchKernelGGL((attn_gather_kernel<T, false, true, KT, DROP>), grid, block, a.lds, stream, p); break;
+        case 0: hipLaunchKernelGGL((attn_gather_kernel<T, false, false, KT, DROP>), grid, block, a.lds, stream, p); break;
+    }
+}
+
+// The two A/B gates and the CU count, each read once per process (attn_select.hpp documents the gates)
+static AttnGates attn_gates() {
+    static const AttnGates g = [] {
+        const char* big = getenv("COBEVT_ATTN_BIG");
+        const char* persist = getenv("COBEVT_ATTN_PERSIST");
+        return AttnGates{!(big && big[0] == '0'), !(persist && persist[0] == '0')};
+    }();
+    return g;
+}
+
+static int attn_cus() {
+    static int cus = 0;
+    if (cus == 0) {
+        int dev = 0;
+        hipDeviceProp_t prop;
+        cus = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 256;
+    }
+    return cus;
+}
+
+// C-ABI entry points, see include/cobevt_hip.h: parse, select (both attn_select.hpp), launch
 static int window_attention_impl(const void* q, const void* k, const void* v, void* out, float* lse,
                                  const float* bias_table, const float* mask, const int* dims, float scale,
                                  float drop_p, unsigned drop_seed, const unsigned* drop_seed_dev, hipStream_t stream,
                                  int ksplit = 1, void* part_out = nullptr, float* part_lse = nullptr, long part_rows = 0) {
-    // dims: [dtype, B, L, heads, ldq, ldk, ldv, ldo, qoff, koff, voff, ooff, bias_mode, bias_rows, bias_L,
-    //        mean_q, qmap[8], kmap[8], omap[8]]
     if (!q || !k || !v || !out || !dims) return COBEVT_ERR_ARG;
     AttnParams p;
-    // dims[0] = dtype | variant << 8 | query split << 16: variant 0 = automatic (K/V-resident kernel where it applies), 1 = force
-    // the streaming kernel (A/B runs, parity tests of both paths); query split 0 = automatic
-    const int dtype = dims[0] & 0xff, variant = (dims[0] >> 8) & 0xff, qsplit_hint = (dims[0] >> 16) & 0xff;
+    AttnHints h;
+    const int rc = attn_parse(dims, bias_table != nullptr, mask != nullptr, lse != nullptr, drop_p, ksplit, part_out && part_lse, part_rows, p, h);
+    if (rc != COBEVT_OK) return rc;
     p.q = q; p.k = k; p.v = v; p.out = out;
-    p.B = dims[1]; p.L = dims[2]; p.heads = dims[3];
-    p.ldq = dims[4]; p.ldk = dims[5]; p.ldv = dims[6]; p.ldo = dims[7];
-    p.qoff = dims[8]; p.koff = dims[9]; p.voff = dims[10]; p.ooff = dims[11];
-    p.bias_mode = dims[12]; p.bias_rows = dims[13]; p.bias_L = dims[14];
-    p.mean_q = dims[15];
-    p.qmap = read_map(dims + 16); p.kmap = read_map(dims + 24); p.omap = read_map(dims + 32);
     p.bias_table = bias_table; p.mask = mask; p.scale = scale; p.lse = lse;
-    p.drop_p = drop_p; p.drop_seed = drop_seed; p.drop_seed_dev = drop_seed_dev;
-    p.ksplit = 1; p.part_out = nullptr; p.part_lse = nullptr; p.part_rows = 0;
-    if (drop_p < 0.f || drop_p >= 1.f || (drop_p > 0.f && (!lse || dtype != 1))) return COBEVT_ERR_ARG;   // dropout: training forward only
-    if (dtype != 0 && dtype != 1) return COBEVT_ERR_ARG;
-    if (!map_ok(p.qmap) || !map_ok(p.kmap) || !map_ok(p.omap)) return COBEVT_ERR_SHAPE;
-    if (p.B < 1 || p.heads < 1 || p.L != p.qmap.X * p.qmap.Y || p.L != p.kmap.X * p.kmap.Y) return COBEVT_ERR_SHAPE;
-    if (p.bias_mode && (!bias_table || p.bias_rows < 1 || p.bias_L < 1)) return COBEVT_ERR_ARG;
-    const int ch = dtype == 0 ? 8 : 4;
-    if ((p.ldq | p.ldk | p.ldv | p.ldo | p.qoff | p.koff | p.voff | p.ooff) % ch) return COBEVT_ERR_SHAPE;
-    p.Nq = p.qmap.ncam * p.qmap.w1 * p.qmap.w2;
-    p.Nk = p.kmap.ncam * p.kmap.w1 * p.kmap.w2;
-    if (p.mean_q < 0 || p.mean_q > 2) return COBEVT_ERR_ARG;
-    if (p.mean_q && p.qmap.ncam == 1) p.mean_q = 0;
-    if (p.mean_q == 1 && (p.qmap.ncam > 8 || p.omap.ncam != 1)) return COBEVT_ERR_UNSUPPORTED;
-    if (p.mean_q == 2) {     // camera-paired queries: cameras on both sides, whole tiles per camera, no bias / mask
-        if (p.omap.ncam != 1 || p.qmap.ncam != p.kmap.ncam || p.bias_mode || mask) return COBEVT_ERR_UNSUPPORTED;
+    p.drop_seed = drop_seed; p.drop_seed_dev = drop_seed_dev;
+    if (p.ksplit > 1) { p.part_out = part_out; p.part_lse = part_lse; }
+    const AttnLaunch a = attn_select(p, h, attn_cus(), attn_gates());
+    if (a.status != COBEVT_OK) return a.status;
+    switch (a.family) {
+        case ATTN_RESIDENT:
+        case ATTN_RESIDENT_BIG: return launch_attn_resident(p, a, stream);
+        case ATTN_STREAM_DROP: launch_stream<float, 64, true>(p, a, stream); break;
+        case ATTN_STREAM:
+            switch (a.dtype * 1000 + a.KT) {
+                case 128: launch_stream<bf16_t, 128>(p, a, stream); break;
+                case 64: launch_stream<bf16_t, 64>(p, a, stream); break;
+                case 1064: launch_stream<float, 64>(p, a, stream); break;
+                default: return COBEVT_ERR_UNSUPPORTED;        // not an instantiation: attn_select never asks for it
+            }
+            break;
     }
-    // keys of a single window that covers the whole map are rows b * Nk + tk: no table (CVT attends to 4 x 64 x 64 keys)
-    p.klinear = (p.kmap.mode != 2 && p.kmap.X == 1 && p.kmap.Y == 1 && !p.bias_mode && !mask) ? 1 : 0;
-    if (lse && p.mean_q) return COBEVT_ERR_UNSUPPORTED;     // (the training path averages cameras outside the kernel)
-    // key split: streaming kernel only, plain inference attention - every query of a window on its own, or camera-paired (mean_q = 2:
-    // partial rows and the merge follow the output map, one row per BEV position; a split may start or end inside a camera, the key
-    // loop reloads the query copy whenever a tile's camera differs from the one it holds)
-    if (ksplit > 1) {
-        if (ksplit > 16 || !part_out || !part_lse || part_rows < 1 || lse || p.mean_q == 1 || drop_p > 0.f) return COBEVT_ERR_ARG;
-        if (p.mean_q != 2 && p.omap.ncam != p.qmap.ncam) return COBEVT_ERR_UNSUPPORTED;
-        p.ksplit = ksplit; p.part_out = part_out; p.part_lse = part_lse; p.part_rows = part_rows;
-    }
-    if (dtype == 0 && variant == 0 && p.mean_q != 2 && !lse && ksplit == 1) {
-        const int rc = launch_attn_resident(p, qsplit_hint, stream);
-        if (rc >= 0) return rc;
-    }
-    const int P = p.qmap.w1 * p.qmap.w2;
-    dim3 grid, block;
-    if (p.mean_q == 1) { block = dim3(64 * (p.qmap.ncam < 4 ? 4 : p.qmap.ncam)); grid = dim3(p.L * p.heads, (P + 31) / 32, p.B); }
-    else { block = dim3(256); grid = dim3(p.L * p.heads, ((p.mean_q == 2 ? P : p.Nq) + 127) / 128 * p.ksplit, p.B); }
-    if (grid.y > 65535 || grid.z > 65535) return COBEVT_ERR_SHAPE;
-    // 128-key tiles: bf16, enough keys, not the camera-paired mode (its tiles never mix cameras)
-    // ... and a grid that does not fill the chip anyway (there the iteration count sets the time; on a full grid the wider tile's
-    // registers cost occupancy: 512-token LiDAR windows, bias + mask, 8192 workgroups: 357 us against 266 us with 64-key tiles)
-    const bool wide = dtype == 0 && p.mean_q != 2 && p.Nk >= 256 && variant != 2 &&      // variant 2: 64-key tiles (A/B)
-                      (long)grid.x * grid.y * grid.z <= 1024;
-    // >= 1 key tile per split (camera-paired: 64-key tiles that never mix cameras, as the kernel counts them)
-    const int key_tiles = p.mean_q == 2 ? p.kmap.ncam * ((p.kmap.w1 * p.kmap.w2 + 63) / 64) : (p.Nk + (wide ? 127 : 63)) / (wide ? 128 : 64);
-    if (p.ksplit > 1 && key_tiles < p.ksplit) return COBEVT_ERR_SHAPE;
-    size_t lds = dtype == 0 ? (wide ? AttnLds<bf16_t, 128>::kFixed : AttnLds<bf16_t, 64>::kFixed) : AttnLds<float, 64>::kFixed;
-    if (p.bias_mode) lds += ((size_t)p.bias_rows * 4 + 15) & ~(size_t)15;
-    if (!p.klinear) lds += (size_t)p.Nk * 8;        // per-key row / coordinate table
-    if ((long)p.B * p.kmap.ncam * (p.kmap.mode == 2 ? (long)p.L * p.kmap.w1 * p.kmap.w2 : (long)p.kmap.HH * p.kmap.WW) >= 0x7fffffffL)
-        return COBEVT_ERR_UNSUPPORTED;              // the table holds 32-bit row indices
-    if (p.mean_q == 1) { const size_t need = (size_t)p.qmap.ncam * 16 * 64 * 4; if (need > lds) lds = need; }
-    if (lds > 64 * 1024) return COBEVT_ERR_UNSUPPORTED;
-    const bool hb = p.bias_mode != 0, hm = p.mask != nullptr;
-#define COBEVT_ATTN_LAUNCH(TT, KT_)                                                                                  \
-    do {                                                                                                              \
-        if (hb && hm) hipLaunchKernelGGL((attn_gather_kernel<TT, true, true, KT_>), grid, block, lds, stream, p);     \
-        else if (hb) hipLaunchKernelGGL((attn_gather_kernel<TT, true, false, KT_>), grid, block, lds, stream, p);     \
-        else if (hm) hipLaunchKernelGGL((attn_gather_kernel<TT, false, true, KT_>), grid, block, lds, stream, p);     \
-        else hipLaunchKernelGGL((attn_gather_kernel<TT, false, false, KT_>), grid, block, lds, stream, p);            \
-    } while (0)
-    if (p.drop_p > 0.f) {                          // training forward (fp32, lse): checked by the caller
-        if (hb && hm) hipLaunchKernelGGL((attn_gather_kernel<float, true, true, 64, true>), grid, block, lds, stream, p);
-        else if (hb) hipLaunchKernelGGL((attn_gather_kernel<float, true, false, 64, true>), grid, block, lds, stream, p);
-        else if (hm) hipLaunchKernelGGL((attn_gather_kernel<float, false, true, 64, true>), grid, block, lds, stream, p);
-        else hipLaunchKernelGGL((attn_gather_kernel<float, false, false, 64, true>), grid, block, lds, stream, p);
-    } else if (dtype == 0 && wide) COBEVT_ATTN_LAUNCH(bf16_t, 128);
-    else if (dtype == 0) COBEVT_ATTN_LAUNCH(bf16_t, 64);
-    else COBEVT_ATTN_LAUNCH(float, 64);
-#undef COBEVT_ATTN_LAUNCH
-    if (p.ksplit > 1) {
-        const long items = p.part_rows * p.heads * 4;
-        const dim3 mg((unsigned)((items + 255) / 256));
-        if (dtype == 0) hipLaunchKernelGGL(attn_ksplit_merge_kernel<bf16_t>, mg, dim3(256), 0, stream, p);
-        else hipLaunchKernelGGL(attn_ksplit_merge_kernel<float>, mg, dim3(256), 0, stream, p);
+    if (a.merge_grid) {
+        if (a.dtype == 0) hipLaunchKernelGGL(attn_ksplit_merge_kernel<bf16_t>, dim3(a.merge_grid), dim3(256), 0, stream, p);
+        else hipLaunchKernelGGL(attn_ksplit_merge_kernel<float>, dim3(a.merge_grid), dim3(256), 0, stream, p);
     }
     return cobevt::launch_status();
 }

@@ -15,7 +15,6 @@
 //   * online softmax with a deferred rescale (the running maximum only moves when a tile exceeds it by more than 2^8), row
 //     maxima by v_max3 + one v_permlane32_swap.
 // MFMA mapping as in attention.hip: S^T = K.Q^T (lane = query), O^T += V^T.P^T.
-#include <stdlib.h>
 #include "attn_common.hpp"
 #include "wave_ops.hpp"
 
@@ -733,137 +732,61 @@ __global__ __launch_bounds__(NW * 64, NT > 8 ? 1 : (BIAS || MASK || PERSIST) ? 2
     } while (true);
 }
 
+// One (NT, NW, PERSIST) geometry: the descriptor's variant booleans -> the instantiation
 template <int NT, int NW, bool P = false>
-int launch_nt(const AttnParams& p, int qsplit, size_t lds, dim3 grid, hipStream_t stream) {
-    const bool hb = p.bias_mode != 0, hm = p.mask != nullptr, mean = p.mean_q != 0;
-    const bool ragged = p.Nk != NT * 64;
-#define COBEVT_RES_LAUNCH(M, B, K, R) \
-    hipLaunchKernelGGL((attn_resident_kernel<NT, NW, M, B, K, R, false, P>), grid, dim3(NW * 64), lds, stream, p, qsplit)
-#define COBEVT_RES_LAUNCH_W8(K) \
-    hipLaunchKernelGGL((attn_resident_kernel<NT, NW, false, true, K, false, true, P>), grid, dim3(NW * 64), lds, stream, p, qsplit)
-    const bool w8 = hb && p.kmap.w1 == 8 && p.kmap.w2 == 8 && p.Nk == NT * 64;
-    if (mean) {
-        if (hb || hm) return -1;                       // the camera mean only occurs in the plain cross attention
-        if (ragged) COBEVT_RES_LAUNCH(true, false, false, true);
-        else COBEVT_RES_LAUNCH(true, false, false, false);
-    } else if (w8 && hm) COBEVT_RES_LAUNCH_W8(true);
-    else if (w8) COBEVT_RES_LAUNCH_W8(false);
-    else if (hb && hm) COBEVT_RES_LAUNCH(false, true, true, false);
-    else if (hb) COBEVT_RES_LAUNCH(false, true, false, false);
-    else if (hm) COBEVT_RES_LAUNCH(false, false, true, false);
-    else if (ragged) COBEVT_RES_LAUNCH(false, false, false, true);
-    else COBEVT_RES_LAUNCH(false, false, false, false);
-#undef COBEVT_RES_LAUNCH
-#undef COBEVT_RES_LAUNCH_W8
-    return cobevt::launch_status();
+int launch_nt(const AttnParams& p, const AttnLaunch& a, hipStream_t stream) {
+    const dim3 grid(a.grid[0], a.grid[1]), block(NW * 64);
+#define COBEVT_RES_CASE(M, B, K, R, W) \
+    case (M) << 4 | (B) << 3 | (K) << 2 | (R) << 1 | (W): \
+        hipLaunchKernelGGL((attn_resident_kernel<NT, NW, M, B, K, R, W, P>), grid, block, a.lds, stream, p, a.qsplit); \
+        break
+    switch (a.MEAN << 4 | a.BIAS << 3 | a.MASK << 2 | a.RAGGED << 1 | a.W8) {
+        COBEVT_RES_CASE(true, false, false, true, false);
+        COBEVT_RES_CASE(true, false, false, false, false);
+        COBEVT_RES_CASE(false, true, true, false, true);
+        COBEVT_RES_CASE(false, true, false, false, true);
+        COBEVT_RES_CASE(false, true, true, false, false);
+        COBEVT_RES_CASE(false, true, false, false, false);
+        COBEVT_RES_CASE(false, false, true, false, false);
+        COBEVT_RES_CASE(false, false, false, true, false);
+        COBEVT_RES_CASE(false, false, false, false, false);
+        default: return COBEVT_ERR_UNSUPPORTED;        // not an instantiation: attn_select never asks for it
+    }
+#undef COBEVT_RES_CASE
+    return launch_status();
 }
 
 // windows of 513 .. 1024 keys: the plain variant only (four waves, one workgroup per CU)
 template <int NT>
-int launch_big(const AttnParams& p, int qsplit, size_t lds, dim3 grid, hipStream_t stream) {
-    if (p.Nk != NT * 64) hipLaunchKernelGGL((attn_resident_kernel<NT, 4, false, false, false, true>), grid, dim3(256), lds, stream, p, qsplit);
-    else hipLaunchKernelGGL((attn_resident_kernel<NT, 4, false, false, false, false>), grid, dim3(256), lds, stream, p, qsplit);
-    return cobevt::launch_status();
+int launch_big(const AttnParams& p, const AttnLaunch& a, hipStream_t stream) {
+    const dim3 grid(a.grid[0], a.grid[1]);
+    if (a.RAGGED) hipLaunchKernelGGL((attn_resident_kernel<NT, 4, false, false, false, true>), grid, dim3(256), a.lds, stream, p, a.qsplit);
+    else hipLaunchKernelGGL((attn_resident_kernel<NT, 4, false, false, false, false>), grid, dim3(256), a.lds, stream, p, a.qsplit);
+    return launch_status();
 }
 
 }  // namespace
 
-// A/B switch: COBEVT_ATTN_BIG=0 in the environment keeps windows of more than 512 keys on the streaming kernel
-static bool attn_big_enabled() {
-    static const bool on = [] { const char* e = getenv("COBEVT_ATTN_BIG"); return !(e && e[0] == '0'); }();
-    return on;
-}
-
-// A/B switch: COBEVT_ATTN_PERSIST=0 in the environment keeps one (window, head) item per workgroup on every shape
-static bool attn_persist_enabled() {
-    static const bool on = [] { const char* e = getenv("COBEVT_ATTN_PERSIST"); return !(e && e[0] == '0'); }();
-    return on;
-}
-
-int launch_attn_resident(const AttnParams& p, int qsplit_hint, hipStream_t stream) {
-    // <= 64 keys: one streaming tile is already optimal; > 512: LDS - except the plain variant (no bias / mask / camera mean), whose K / V
-    // of up to 1024 keys (the FAX level-2 and global attentions: one whole-map window per agent) fit as 128 KB + tables: four-wave
-    // workgroups, one per CU, one 32-query tile per wave instead of the streaming kernel's key split + merge launch (round 6)
-    const bool big = p.Nk > 512;
-    if (p.Nk < 65 || p.Nk > 1024 || (big && (p.bias_mode != 0 || p.mask != nullptr || p.mean_q != 0 || !attn_big_enabled()))) return -1;
-    const int nt = ((p.Nk + 127) / 128) * 2;           // 64-key tiles, even
-    const int P = p.qmap.w1 * p.qmap.w2;
-    const bool mean = p.mean_q != 0;
-    if (!mean && p.omap.ncam != p.qmap.ncam) return -1;
-    if (mean && p.omap.ncam != 1) return -1;
-    const int NQ = mean ? P : p.Nq;
-    const bool info = p.bias_mode != 0 || p.mask != nullptr;
-    size_t lds = (size_t)nt * 64 * 128 + (size_t)nt * 64 * 4 * (1 + (info ? 2 : 0) + (p.bias_mode ? 1 : 0)) +
-                 (size_t)NQ * 4 * (p.bias_mode ? 3 : 2);
-    if (p.bias_mode) {
-        // four shifted copies of the reversed, row-padded table column (see the kernel): key quads must share (agent, window row)
-        if (p.kmap.w2 % 4 != 0 || p.bias_rows != (2 * p.bias_L - 1) * (2 * p.kmap.w1 - 1) * (2 * p.kmap.w2 - 1)) return -1;
-        const size_t rp = (size_t)(2 * p.bias_L - 1) * (2 * p.kmap.w1 - 1) * (2 * p.kmap.w2);
-        lds = ((lds + 15) & ~(size_t)15) + 4 * (rp + 4) * 4;
+int launch_attn_resident(const AttnParams& p, const AttnLaunch& a, hipStream_t stream) {
+    switch (a.NT * 100 + a.NW * 10 + a.PERSIST) {
+        case 240: return launch_nt<2, 4>(p, a, stream);
+        case 440: return launch_nt<4, 4>(p, a, stream);
+        case 640: return launch_nt<6, 4>(p, a, stream);
+        case 840: return launch_nt<8, 4>(p, a, stream);
+        case 281: return launch_nt<2, 8, true>(p, a, stream);
+        case 280: return launch_nt<2, 8>(p, a, stream);
+        case 481: return launch_nt<4, 8, true>(p, a, stream);
+        case 480: return launch_nt<4, 8>(p, a, stream);
+        case 681: return launch_nt<6, 8, true>(p, a, stream);
+        case 680: return launch_nt<6, 8>(p, a, stream);
+        case 881: return launch_nt<8, 8, true>(p, a, stream);
+        case 880: return launch_nt<8, 8>(p, a, stream);
+        case 1040: return launch_big<10>(p, a, stream);       // ATTN_RESIDENT_BIG
+        case 1240: return launch_big<12>(p, a, stream);
+        case 1440: return launch_big<14>(p, a, stream);
+        case 1640: return launch_big<16>(p, a, stream);
     }
-    lds = (lds + 15) & ~(size_t)15;
-    if (lds > 160 * 1024) return -1;
-    if ((long)p.B * p.qmap.ncam * (p.qmap.mode == 2 ? (long)p.L * P : (long)p.qmap.HH * p.qmap.WW) >= 0x7fffffffL) return -1;
-    const int ntiles = (NQ + 31) / 32;
-    // waves per workgroup: 8 when the LDS footprint leaves room for one or two workgroups per CU only and the window has the
-    // query tiles to feed them (LiDAR FuseBEVT: 512 tokens per window)
-    // (16 waves = 4 per SIMD at one workgroup per CU was measured 2x slower for the 512-key bias + mask windows: 128 VGPRs spill)
-    const int nw = big ? 4 : (lds > 40 * 1024 && ntiles >= 16) ? 8 : 4;
-    // query split: enough workgroups to fill 256 CUs x (4 | 2 | 1 resident workgroups), every wave keeping >= 1 tile
-    int qsplit = qsplit_hint;
-    if (qsplit <= 0) {
-        const long base = (long)p.B * p.L * p.heads;
-        const int resident = lds > 80 * 1024 ? 1 : (lds > 40 * 1024 ? 2 : 4);
-        qsplit = 1;
-        while (base * qsplit < 256L * resident && ntiles >= 2 * qsplit * nw) qsplit *= 2;
-        if (base * qsplit < 256L && ntiles >= 2 * qsplit * nw - nw) qsplit *= 2;     // fewer workgroups than CUs: one tile per wave
-        // bias / mask windows on a grid that still does not reach the CU count (the 5-agent fusion: 64 (window, head) pairs of 10 query
-        // tiles): keep splitting while a workgroup keeps two tiles - 13.2 us against the streaming kernel's 14.9 us in-graph
-        if (info) while (base * qsplit < 256L && ntiles >= 4 * qsplit) qsplit *= 2;
-    }
-    if (big && qsplit_hint <= 0) {                      // one query tile per wave where the window has them
-        qsplit = 1;
-        while (qsplit * 2 * nw <= ntiles) qsplit *= 2;
-    }
-    if (qsplit > ntiles) qsplit = ntiles;
-    if (qsplit < 1) qsplit = 1;
-    // fewer workgroups than CUs (nuScenes: 100 windows x 1 head; the 5-agent fusion: 16 windows x 4 heads): the streaming kernel's
-    // finer query split fills the chip better than one staging per (window, head) can (measured: 31 vs 52 us, 25 vs 29 us)
-    if (qsplit_hint <= 0 && !big && (long)p.B * p.L * p.heads * qsplit < 256) return -1;
-    dim3 grid(p.L * p.heads * qsplit, p.B);
-    if (grid.y > 65535) return -1;
-    // one workgroup per CU (> 80 KB of LDS) and several items per CU: persistent workgroups, a whole number of (8 windows x heads)
-    // groups of them so that a workgroup keeps its head (and its bias copies) across its items
-    bool persist = false;
-    if (attn_persist_enabled() && nw == 8 && lds > 80 * 1024 && !mean) {
-        static int cus = 0;
-        if (cus == 0) {
-            int dev = 0;
-            hipDeviceProp_t prop;
-            cus = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 256;
-        }
-        const int per = 8 * p.heads;
-        int gx = cus >= per && (p.L & 7) == 0 ? (cus / per) * per : cus;
-        if ((long)gx * 2 <= (long)grid.x) {             // at least two items per workgroup, else the plain form
-            grid.x = gx;
-            persist = true;
-        }
-    }
-    switch (nt * 10 + nw) {
-        case 24: return launch_nt<2, 4>(p, qsplit, lds, grid, stream);
-        case 44: return launch_nt<4, 4>(p, qsplit, lds, grid, stream);
-        case 64: return launch_nt<6, 4>(p, qsplit, lds, grid, stream);
-        case 84: return launch_nt<8, 4>(p, qsplit, lds, grid, stream);
-        case 28: return persist ? launch_nt<2, 8, true>(p, qsplit, lds, grid, stream) : launch_nt<2, 8>(p, qsplit, lds, grid, stream);
-        case 48: return persist ? launch_nt<4, 8, true>(p, qsplit, lds, grid, stream) : launch_nt<4, 8>(p, qsplit, lds, grid, stream);
-        case 68: return persist ? launch_nt<6, 8, true>(p, qsplit, lds, grid, stream) : launch_nt<6, 8>(p, qsplit, lds, grid, stream);
-        case 88: return persist ? launch_nt<8, 8, true>(p, qsplit, lds, grid, stream) : launch_nt<8, 8>(p, qsplit, lds, grid, stream);
-        case 104: return launch_big<10>(p, qsplit, lds, grid, stream);
-        case 124: return launch_big<12>(p, qsplit, lds, grid, stream);
-        case 144: return launch_big<14>(p, qsplit, lds, grid, stream);
-        case 164: return launch_big<16>(p, qsplit, lds, grid, stream);
-        default: return -1;
-    }
+    return COBEVT_ERR_UNSUPPORTED;                     // not a geometry that is compiled: attn_select never asks for it
 }
 
 }  // namespace cobevt

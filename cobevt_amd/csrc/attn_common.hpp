@@ -1,18 +1,12 @@
 // Shared declarations of the gathered-attention kernels (attention.hip: streaming K/V tiles; attention_resident.hip: the
 // K / V of a window held in LDS for all of its query tiles): token maps = the einops window / grid partitions as index
-// arithmetic, the relative-position index split, the kernel parameter block.
+// arithmetic, the relative-position index split.  The token map, the kernel parameter block and the host-side routing are plain
+// C++ in attn_select.hpp; everything __device__ is here.
 #pragma once
 #include "common.hpp"
+#include "attn_select.hpp"
 
 namespace cobevt {
-
-struct TokMap {
-    int mode;  // 0 window partition, 1 grid partition, 2 rows already stored window-partitioned
-    int ncam;  // cameras / agents concatenated inside a window
-    int HH, WW;
-    int w1, w2;
-    int X, Y;  // windows along H and W (HH == X*w1, WW == Y*w2)
-};
 
 struct TokCoord { int cam, i, j; };
 
@@ -75,42 +69,6 @@ __device__ __forceinline__ int rel_bias_key_term(const TokMap& km, const TokCoor
     return (kc.cam * (2 * km.w1 - 1) + kc.i) * (2 * km.w2 - 1) + kc.j;
 }
 
-struct AttnParams {
-    const void* q; const void* k; const void* v; void* out;
-    int ldq, ldk, ldv, ldo;
-    int qoff, koff, voff, ooff;
-    TokMap qmap, kmap, omap;
-    int B, L, heads, Nq, Nk;
-    float scale;
-    int bias_mode;            // 0 none, 1 relative-position table lookup
-    const float* bias_table;  // [rows][heads]
-    int bias_rows;
-    int bias_L;               // agent extent of the 3-D table (1 => 2-D table)
-    const float* mask;        // key mask fp32, 0 => key masked out; (B,HH,WW,ncam), or (B,L,w1,w2,ncam) for mode 2; may be null
-    int mean_q;               // 0: every query token on its own; 1: per-camera query copies, outputs averaged over the cameras
-                              // (fax_modules.py:243); 2: per-camera query copies, camera c's query scores camera c's keys only,
-                              // ONE softmax over all cameras' keys (CVT CrossAttention, cvt_modules.py:142-153)
-    float* lse;               // training forward: base-2 log-sum-exp of every query's logits, [B][L][heads][Nq] (nullable)
-    int klinear;              // streaming kernel: key token tk of the (single) window is row b * Nk + tk - no key table in LDS
-    // training only: nn.Dropout on the attention probabilities (FAX global attention, fax_modules.py:114,161): element (query,
-    // key) of a (batch, window, head) is kept with probability 1 - drop_p and scaled by 1 / (1 - drop_p); the keep decision is a
-    // counter-based hash of (drop_seed, element index), so the backward kernels regenerate the forward's mask
-    float drop_p;
-    unsigned drop_seed;
-    // nullable device word ADDED to drop_seed: a captured training step (tools/train_graph_probe.py) bumps it inside the graph, so every
-    // replay draws a new mask although the kernel arguments are frozen in the graph's nodes
-    const unsigned* drop_seed_dev;
-    // key split (streaming kernel, inference): the keys of a window are shared out over `ksplit` workgroups per query tile; each
-    // writes its normalised partial output rows to part_out[split] (same row indexing as `out`, row stride heads * 32) and the
-    // base-2 log-sum-exp of its keys to part_lse[split][row][head]; attn_ksplit_merge_kernel combines them into `out`.
-    // For the launches whose grid leaves the chip idle AND whose per-query key walk is long (level-2 / global FAX attention:
-    // 1024 keys, 160 workgroups) - the tile loop is one dependent round trip per iteration.
-    int ksplit;
-    void* part_out;
-    float* part_lse;
-    long part_rows;           // rows of `out` (stride between the splits' partial buffers)
-};
-
 __host__ __device__ __forceinline__ unsigned attn_mix32(unsigned x) {       // murmur3 finaliser
     x ^= x >> 16; x *= 0x85ebca6bu; x ^= x >> 13; x *= 0xc2b2ae35u; x ^= x >> 16;
     return x;
@@ -124,21 +82,9 @@ __device__ __forceinline__ bool attn_keep(const AttnParams& p, int b, int l, int
     return (float)u * 2.3283064365386963e-10f >= p.drop_p;
 }
 
-static inline bool map_ok(const TokMap& m) {
-    if (m.mode < 0 || m.mode > 2 || m.ncam < 1 || m.w1 < 1 || m.w2 < 1 || m.X < 1 || m.Y < 1) return false;
-    if (m.mode != 2 && (m.HH != m.X * m.w1 || m.WW != m.Y * m.w2)) return false;
-    return m.w1 < 256 && m.w2 < 256 && m.ncam < 32768;
-}
-
-static inline TokMap read_map(const int* d) {
-    TokMap m;
-    m.mode = d[0]; m.ncam = d[1]; m.HH = d[2]; m.WW = d[3]; m.w1 = d[4]; m.w2 = d[5]; m.X = d[6]; m.Y = d[7];
-    return m;
-}
-
-// attention_resident.hip: launches the K/V-resident kernel when the problem qualifies; returns COBEVT_OK, an error code, or
-// -1 when it does not apply (the caller then uses the streaming kernel).  hint: 0 auto, >0 = query split to use
-int launch_attn_resident(const AttnParams& p, int qsplit_hint, hipStream_t stream);
+// attention_resident.hip: launches the resident kernel instantiation that attn_select (attn_select.hpp) chose - no decision of its own;
+// returns the launch status
+int launch_attn_resident(const AttnParams& p, const AttnLaunch& a, hipStream_t stream);
 
 // The A operand V^T (rows = dh, k = 16 keys) of a PV MFMA out of a ROW-MAJOR V image [key][32 dh] (64 B per key, staged with the same
 // coalesced 16-byte copies as K): gfx950's transpose read.  ds_read_b64_tr_b16: every lane reads 8 bytes at its own address, then inside
@@ -154,6 +100,5 @@ __device__ __forceinline__ uint4 read_vt16(const unsigned char* p) {
     const uint2 x = __builtin_bit_cast(uint2, a), y = __builtin_bit_cast(uint2, b);
     return make_uint4(x.x, x.y, y.x, y.y);
 }
-
 
 }  // namespace cobevt

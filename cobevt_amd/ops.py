@@ -56,9 +56,11 @@ USE_PROJ_CHAIN_WAVE = True   # ... on maps of >= 32768 rows as independent waves
 USE_SWAP_STAGE = True   # a SwapFusionBlock half (attention + row chain + next to_qkv) as one launch (swap_stage.hip)
 USE_BOTTLENECK = True   # FAX ResNetBottleNeck (128 -> 32 -> 32 -> 128) as one launch (bottleneck.hip) instead of three
 ATTN_VARIANT = 0    # 0 = automatic (K/V-resident attention kernel where it applies), 1 = always the streaming kernel, 2 = ... with 64-key tiles (A/B runs)
-USE_ATTN_BIG_RESIDENT = False  # plain bf16 windows of 513 .. 1024 keys on the K/V-resident kernel (one launch) instead of key split + merge:
-                               # built and measured neutral (659.0 / 659.7 / 668.2 vs 659.2 / 660.3 / 660.5 frames/s, one frame 1.900 vs 1.904 ms,
-                               # profiles/r06_attn_big_resident_ab.txt) - kept as an opt-in switch, the key split stays the default
+USE_ATTN_BIG_RESIDENT = False  # True only SUPPRESSES the key split for plain bf16 windows of 513 .. 1024 keys, nothing more.  Which kernel such a window
+                               # takes is decided in C (csrc/attn_select.hpp), whose gate COBEVT_ATTN_BIG is ON by default: unsplit, it runs on the
+                               # K/V-resident kernel in one launch with or without this flag.  Split vs. unsplit measured neutral (659.0 / 659.7 /
+                               # 668.2 vs 659.2 / 660.3 / 660.5 frames/s, one frame 1.900 vs 1.904 ms, profiles/r06_attn_big_resident_ab.txt):
+                               # the key split stays the default
 ATTN_KSPLIT = 2     # streaming attention on a small grid with >= 1024 keys (FAX level 2 / global attention): share the keys of a window out
                     # over this many workgroups per query tile + a merge pass (0 / 1 = off).  Round 3 measured it neutral (0 / 2 / 4 =
                     # 582 / 578 / 569 frames/s, profiles/r03_ab_key_split.txt) and left it off; with the round-5 pipeline 2 is a small

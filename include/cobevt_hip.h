@@ -2,7 +2,7 @@
  * cobevt_hip.h — C ABI of libcobevt_hip.so: the MI355X (gfx950) kernels behind the CoBEVT FAX hot path.
  *
  * The reference (DerrickXuNu/CoBEVT) has no FFI: its hot path is Python nn.Modules calling ATen.  The
- * drop-in boundary is therefore the nn.Module API (cobevt_amd/host/*, same class names / constructor
+ * drop-in boundary is therefore the nn.Module API (cobevt_amd/host/, same class names / constructor
  * arguments / state_dict keys / forward contracts); those modules bind the entry points below through
  * ctypes (cobevt_amd/lib.py).  Every entry point cites the reference code whose arithmetic it replaces
  * (paths relative to the reference repository root).
