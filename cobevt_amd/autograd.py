@@ -11,7 +11,7 @@ the convolution family follows a bf16 autocast region (bf16 storage, fp32 master
 
 No CPU path: every Function raises on CPU tensors (lib.CobevtHipError) like the inference ops do.
 
-Library variant: every launch below goes through `_call`, i.e. to the native library.
+Library variant: every launch below goes through `_call` or an `ops._launch_*(..., variant="")`, i.e. to the native library.
 """
 import ctypes
 
@@ -599,30 +599,17 @@ def _igemm_rows(x, w2, cout, cin, kh, kw, bias, stride, pad, ho, wo):
     (N, ho, wo, Cout) in that dtype: cobevt_conv2d_nhwc (csrc/igemm.hip), top / left padding `pad`; taps past the bottom / right edge
     read zeros (the kernel bounds-checks every tap).  Channel counts that are not a multiple of a 16-byte chunk take the kernel's
     gather path, which reads its input as fp32.  bias: fp32 (Cout,) | None."""
-    n, h, w, _ = x.shape
-    bf16 = x.dtype == torch.bfloat16
-    K, kpad = kh * kw * cin, w2.shape[1]
-    smallc = int(cin % (8 if bf16 else 4) != 0)
-    klut = _klut(kh, kw, cin, kpad, x.device) if smallc else None
-    if smallc and bf16:
+    klut = _klut(kh, kw, cin, w2.shape[1], x.device) if cin % (8 if x.dtype == torch.bfloat16 else 4) else None
+    if klut is not None:
         x = x.float()
-    out = torch.empty((n, ho, wo, cout), device=x.device, dtype=w2.dtype)
-    dims = _ints([ops.BF16 if bf16 else ops.FP32, n, h, w, cin, ho, wo, cout, kh, kw, stride, pad, K, kpad, 0, 0, 0, 0, ho, wo, smallc])
+    out = torch.empty((x.shape[0], ho, wo, cout), device=x.device, dtype=w2.dtype)
     b = None if bias is None else _f32c(bias.detach().float(), "bias")
-    _call("cobevt_conv2d_nhwc", _p(x), _p(w2), _p(b), None, None, None, _p(klut), _p(out), dims, _stream())
+    ops._launch_conv2d_nhwc(x, w2, b, None, None, None, klut, out, ho, wo, kh, kw, stride=stride, pad=pad, variant="")
     return out
 
 
 USE_WGRAD3 = True             # bf16 3x3 / stride-1 weight gradients straight from the channels-last maps (csrc/wgrad3.hip)
 USE_TRAIN_STRIPS = True       # bf16 3x3 / pad-1 convolutions with 64 | Cin: forward and (stride 1) input gradient on the inference kernels
-
-
-def conv3_strips_plan(n, ho, wo, cin, cout, stride):
-    """tile choice of ops.conv2d for one bf16 3x3 launch: 0 = the LDS-staged kernel (reads `rows3`), else a strip variant (`frag`)"""
-    variant = ops.CONV3_VARIANT or ops.conv3_tiling(n, ho, wo, cin, cout, 64, stride=stride, bf16=True)
-    if variant == 0 and stride == 2:
-        variant = 151 if cout <= 64 else 150
-    return variant
 
 
 def conv3_weight_operand(weight, variant, dgrad):
@@ -661,16 +648,11 @@ def conv3_weight_operand_pair(weight, var_f, var_d):
 def _conv3_strips(x, operand, variant, cout, bias, stride):
     """x (N, H, W, Cin) bf16 channels-last -> (N, Ho, Wo, Cout) bf16: cobevt_conv3x3_wfrag_nhwc / cobevt_conv3x3_nhwc (csrc/conv3x3.hip) with
     the operand conv3_weight_operand made for `variant`; bias fp32 (Cout,) | None"""
-    n, h, w, cin = x.shape
+    n, h, w, _ = x.shape
     ho, wo = (h - 1) // stride + 1, (w - 1) // stride + 1
     out = torch.empty((n, ho, wo, cout), device=x.device, dtype=torch.bfloat16)
     b = None if bias is None else _f32c(bias.detach().float(), "bias")
-    if variant:
-        dims = _ints([ops.BF16, n, h, w, cin, cout, 0, 0, 0, 64, (cout + 127) // 128 * 128, variant, stride])
-        _call("cobevt_conv3x3_wfrag_nhwc", _p(x), _p(operand), _p(b), None, _p(out), dims, _stream())
-    else:
-        dims = _ints([ops.BF16, n, h, w, cin, cout, 0, 0, 0, 64])
-        _call("cobevt_conv3x3_nhwc", _p(x), _p(operand), _p(b), None, _p(out), dims, _stream())
+    ops._launch_conv3x3(x, operand, b, None, out, cout=cout, tile=variant, stride=stride, variant="")
     return out
 
 
@@ -694,8 +676,7 @@ def _rows_gemm(x2d, frag, n_out, k_in, bias):
     m = x2d.shape[0]
     out = torch.empty((m, n_out), device=x2d.device, dtype=torch.bfloat16)
     b = None if bias is None else _f32c(bias.detach().float(), "bias")
-    d3 = (ctypes.c_long * 14)(ops.BF16, m, n_out, k_in, k_in, 0, 0, 0, 1, m, 1, m, 1, 32)
-    _call("cobevt_linear_rows_small_k", _p(x2d), _p(frag), _p(b), None, None, None, _p(out), d3, ctypes.c_float(0.0), _stream())
+    ops._launch_rows(x2d.reshape(1, m, 1, k_in), frag, b, None, None, None, out.view(1, m, 1, n_out), rows=32, variant="")
     return out
 
 
@@ -797,7 +778,7 @@ class Conv2dFn(torch.autograd.Function):
         strips_d = USE_TRAIN_STRIPS and xl.dtype == torch.bfloat16 and kh == 3 and kw == 3 and pad == 1 and stride == 1 and cout % 64 == 0 \
             and cin % 8 == 0 and n * h * w * cout < 2 ** 31
         need_d = ctx.needs_input_grad[0]
-        var_d = conv3_strips_plan(n, h, w, cout, cin, 1) if (strips_d and need_d) else -1
+        var_d = ops.conv3_variant(n, h, w, cout, cin, 64, 1) if (strips_d and need_d) else -1
         rows = (USE_TRAIN_ROWS_GEMM and xl.dtype == torch.bfloat16 and kh == 1 and kw == 1 and stride == 1 and pad == 0 and cin % 8 == 0
                 and cout % 8 == 0 and cin <= 512 and cout <= 512)
         if rows:
@@ -806,7 +787,7 @@ class Conv2dFn(torch.autograd.Function):
             out = _rows_gemm(xl.reshape(-1, cin), frag_f, cout, cin, bias).reshape(n, ho, wo, cout)
             var_d = -2 if need_d else -1
         elif strips:
-            var_f = conv3_strips_plan(n, ho, wo, cin, cout, stride)
+            var_f = ops.conv3_variant(n, ho, wo, cin, cout, 64, stride)      # 0: the LDS-staged kernel (reads `rows3`), else `frag`
             op_f, op_d = conv3_weight_operand_pair(weight, var_f, var_d)      # both directions' operands from one launch
             out = _conv3_strips(xl, op_f, var_f, cout, bias, stride)
             rows_d = op_d if var_d >= 0 else conv_weight_rows(weight, xl.dtype, False, need_d)[1]

@@ -7,6 +7,7 @@ otherwise — there is no CPU path here (the CPU restatement lives in oracle/ an
 import ctypes
 import os
 import math
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -385,116 +386,133 @@ def conv3_tiling(n, ho, wo, cin, cout, cc, cus=256, stride=1, bf16=True, packed=
     return best[1]
 
 
+def conv3_packed(code, lib_variant):
+    """conv3_tiling's `packed`: the cost of an MFMA step of a 128-cout strip tile in an fp32-storage library (0: the native one)"""
+    return {"f32h": 0.5, "f32s": 0.75}.get(lib_variant, 0) if code == FP32 else 0
+
+
+def conv3_variant(n, ho, wo, cin, cout, cc, stride, bf16=True, packed=0):
+    """The 3x3 kernel of one launch: CONV3_VARIANT when pinned, else conv3_tiling's choice (0, the LDS-staged kernel, is stride 1 only)"""
+    variant = CONV3_VARIANT or conv3_tiling(n, ho, wo, cin, cout, cc, stride=stride, bf16=bf16, packed=packed)
+    return (151 if cout <= 64 else 150) if (variant == 0 and stride == 2) else variant
+
+
+ConvRoute = namedtuple("ConvRoute", "kernel ln_fused variant rows", defaults=(0, 0))
+CONV_SYMBOLS = {"head": "cobevt_conv3x3_head_nchw", "stem": "cobevt_stem_conv7x7s2", "rows_small_k": "cobevt_linear_rows_small_k",
+                "rows_wfrag": "cobevt_linear_rows_wfrag", "rows": "cobevt_linear_rows", "strips": "cobevt_conv3x3_wfrag_nhwc",
+                "conv3": "cobevt_conv3x3_nhwc", "igemm": "cobevt_conv2d_nhwc"}
+
+
+def conv_route(plan, n, h, w, out_hw=None, has_residual=False, lib_variant=""):
+    """The kernel (a key of CONV_SYMBOLS) conv2d launches for `plan` on an (n, h, w) input, from the plan, the switches above and the
+    arguments alone (out_hw: a preallocated result's size).  ln_fused: the LayerNorm runs inside the GEMM, not as a launch before it."""
+    p, (ho, wo) = plan, plan.out_hw(h, w)
+    ln, bf16, m, exact = bool(p.has_ln and ln_fusable(p)), p.code == BF16, n * ho * wo, out_hw is None or tuple(out_hw) == (ho, wo)
+    if p.wgt_head is not None and USE_HEAD_CONV and exact and not has_residual:
+        return ConvRoute("head", ln)
+    if p.wgt_stem is not None and USE_STEM and h % 2 == 0 and w % 2 == 0 and exact and not has_residual:
+        return ConvRoute("stem", ln)
+    if p.wgt_rows is not None and USE_GEMM_ROWS and (exact or not has_residual):
+        ch, use3, max_k = (8, USE_GEMM_ROWS3, GEMM_ROWS3_MAX_K) if bf16 else (4, USE_GEMM_ROWS3_F32, 512)
+        ln_ok = not ln or (p.kp_rows <= 128 if bf16 else (p.K == 128 and p.pre_scale is None))
+        s2_ok = p.stride == 1 or (not has_residual and bool(GEMM_ROWS3_STRIDED or not bf16))
+        if (use3 and p.wfrag_rows is not None and exact and p.kp_rows <= max_k and p.K % ch == 0 and p.cout % ch == 0 and p.cout <= 4096
+                and p.store_mode == 0 and ln_ok and s2_ok and m >= GEMM_ROWS3_MIN_M):
+            return ConvRoute("rows_small_k", ln, 0, 64 if (GEMM_ROWS3_ROWS64_MIN_M and m >= GEMM_ROWS3_ROWS64_MIN_M) else 32)
+        return ConvRoute("rows_wfrag" if (USE_GEMM_ROWS2 and p.wfrag_rows is not None and p.cout % ch == 0) else "rows", ln)
+    # (the stride-2 strip variants sit at the 256-VGPR limit in fp32: with the operand split of the f32s library they spill
+    # hundreds of registers, so that library's three stride-2 3x3 convs of a ResNet take the generic implicit GEMM)
+    if p.wfrag is not None and exact and USE_CONV3X3 and USE_CONV3_WFRAG \
+            and (p.stride == 1 or (USE_CONV3_S2 and not (p.code == FP32 and lib_variant == "f32s"))):
+        variant = conv3_variant(n, ho, wo, p.cin, p.cout, p.cc3, p.stride, bf16, conv3_packed(p.code, lib_variant))
+        if variant > 0:
+            return ConvRoute("strips", ln, variant)
+    return ConvRoute("conv3" if (p.wgt3 is not None and exact and USE_CONV3X3) else "igemm", ln)
+
+
+def _launch_conv2d_nhwc(x, wgt, bias, residual, pre_scale, pre_shift, klut, out, ho, wo, kh, kw, stride=1, pad=0, upsample=0, pre_relu=0,
+                        act=0, store_mode=0, out_hw=None, variant=None):
+    (n, h, w, cin), (cout, kpad), (out_h, out_w) = x.shape, wgt.shape, out_hw or (ho, wo)
+    dims = _ints([dcode(wgt.dtype), n, h, w, cin, ho, wo, cout, kh, kw, stride, pad, kh * kw * cin, kpad, upsample, pre_relu, act,
+                  store_mode, out_h, out_w, klut is not None])
+    _L.call("cobevt_conv2d_nhwc", _p(x), _p(wgt), _p(bias), _p(residual), _p(pre_scale), _p(pre_shift), _p(klut), _p(out), dims, _stream(),
+            variant=variant)
+
+
+def _launch_conv3x3(x, wgt, bias, residual, out, cout=None, tile=0, stride=1, upsample=0, act=0, store_mode=0, variant=None):
+    """tile 0: cobevt_conv3x3_nhwc on plan.wgt3, else cobevt_conv3x3_wfrag_nhwc on plan.wfrag (cc, padded Cout: the table's sizes)"""
+    dims = [dcode(x.dtype), *x.shape, cout if tile else wgt.shape[0], upsample, act, store_mode]
+    dims += [x.shape[3] // wgt.shape[1], wgt.shape[0] * 32, tile, stride] if tile else [wgt.shape[3]]
+    _L.call("cobevt_conv3x3_wfrag_nhwc" if tile else "cobevt_conv3x3_nhwc", _p(x), _p(wgt), _p(bias), _p(residual), _p(out), _ints(dims),
+            _stream(), variant=variant)
+
+
+def _launch_rows(x, wgt, bias, residual, pre_scale, pre_shift, out, kp=0, rows=0, wfrag=False, pre_relu=0, act=0, ln=0, ln_eps=0.0,
+                 stride=1, variant=None):
+    """rows > 0: cobevt_linear_rows_small_k (plan.wfrag_rows), else cobevt_linear_rows_wfrag (wfrag) or cobevt_linear_rows (plan.wgt_rows)"""
+    (n, h, w, K), (out_h, out_w, cout), code = x.shape, out.shape[1:], dcode(x.dtype)
+    ho, wo = (h - 1) // stride + 1, (w - 1) // stride + 1
+    if rows:
+        dims = (ctypes.c_long * 14)(code, n * ho * wo, cout, K, K, pre_relu, act, int(ln), stride, ho, wo, h, w, rows)
+    else:
+        dims = (ctypes.c_long * 16)(code, n * ho * wo, cout, K, kp, K, pre_relu, act, ho, wo, out_h, out_w, int(ln), stride, h, w)
+    symbol = "cobevt_linear_rows_small_k" if rows else "cobevt_linear_rows_wfrag" if wfrag else "cobevt_linear_rows"
+    _L.call(symbol, _p(x), _p(wgt), _p(bias), _p(residual), *(() if rows or wfrag else (None, None)), _p(pre_scale), _p(pre_shift), _p(out),
+            dims, ctypes.c_float(ln_eps), _stream(), variant=variant)
+
+
 def conv2d(x, plan, residual=None, out=None):
     """x: (N,H,W,Cin) channels-last contiguous in plan.dtype (fp32 image for smallc plans).  Returns the output
     in the layout selected by plan.store_mode.  `out` may be a pre-zeroed, spatially larger (N,Hp,Wp,Cout) map.
     Plans built with ln=... normalise the rows of x first (LayerNorm affine already folded into the weights)."""
     _need_cuda(x, residual, out)
-    ln = plan.has_ln
-    if ln and not ln_fusable(plan):
-        x = layernorm(x, None, None, plan.ln_eps)
-        ln = False
     n, h, w, cin = x.shape
     if cin != plan.cin or not x.is_contiguous():
         raise CobevtHipError("conv2d: bad input %s (contiguous=%s) for Cin=%d" % (tuple(x.shape), x.is_contiguous(), plan.cin))
     if x.dtype != (torch.float32 if plan.smallc else plan.dtype):
         raise CobevtHipError("conv2d: input dtype %s does not match plan (%s, smallc=%d)" % (x.dtype, plan.dtype, plan.smallc))
-    ho, wo = plan.out_hw(h, w)
-    sm = plan.store_mode
-    out_h, out_w = ho, wo
+    p, sm, (ho, wo), out_hw = plan, plan.store_mode, plan.out_hw(h, w), None
     if out is None:
-        if sm == 0:
-            out = torch.empty((n, ho, wo, plan.cout), device=x.device, dtype=plan.dtype)
-        elif sm == 1:
-            out = torch.empty((n, ho // 2, wo // 2, plan.cout * 4), device=x.device, dtype=plan.dtype)
-        elif sm == 2:
-            out = torch.empty((n, plan.cout, ho, wo), device=x.device, dtype=torch.float32)
-        else:
-            out = torch.empty((n, ho, wo, plan.cout), device=x.device, dtype=torch.float32)
+        shape = (n, ho // 2, wo // 2, p.cout * 4) if sm == 1 else (n, p.cout, ho, wo) if sm == 2 else (n, ho, wo, p.cout)
+        out = torch.empty(shape, device=x.device, dtype=p.dtype if sm in (0, 1) else torch.float32)
     else:
-        if sm not in (0, 3) or out.dim() != 4 or out.shape[0] != n or out.shape[3] != plan.cout or not out.is_contiguous():
+        if sm not in (0, 3) or out.dim() != 4 or out.shape[0] != n or out.shape[3] != p.cout or not out.is_contiguous():
             raise CobevtHipError("conv2d: incompatible `out`")
-        out_h, out_w = out.shape[1], out.shape[2]
-        if out_h < ho or out_w < wo:
+        out_hw = (out.shape[1], out.shape[2])
+        if out_hw[0] < ho or out_hw[1] < wo:
             raise CobevtHipError("conv2d: `out` smaller than the convolution result")
-    if residual is not None:
-        if tuple(residual.shape) != (n, ho, wo, plan.cout) or residual.dtype != plan.dtype or not residual.is_contiguous():
-            raise CobevtHipError("conv2d: residual must be (N,Ho,Wo,Cout) contiguous in the compute dtype")
+    if residual is not None and (tuple(residual.shape) != (n, ho, wo, p.cout) or residual.dtype != p.dtype
+                                 or not residual.is_contiguous()):
+        raise CobevtHipError("conv2d: residual must be (N,Ho,Wo,Cout) contiguous in the compute dtype")
     def cost():
-        m = n * ho * wo
-        esz = 2 if plan.code == BF16 else 4
-        nbytes = x.numel() * x.element_size() + plan.cout * plan.K * esz + out.numel() * out.element_size()
-        if residual is not None:
-            nbytes += residual.numel() * esz
-        return 2.0 * m * plan.cout * plan.K, float(nbytes)
+        esz = 2 if p.code == BF16 else 4
+        nbytes = x.numel() * x.element_size() + p.cout * p.K * esz + out.numel() * out.element_size()
+        return 2.0 * m * p.cout * p.K, float(nbytes + (0 if residual is None else residual.numel() * esz))
 
-    if plan.wgt_head is not None and USE_HEAD_CONV and residual is None and (out_h, out_w) == (ho, wo):
-        with _timed("head3x3|%d->%d %dx%dx%d" % (cin, plan.cout, n, ho, wo), cost):
-            _L.call("cobevt_conv3x3_head_nchw", _p(x), _p(plan.wgt_head), _p(plan.bias), _p(out), plan.code, n, h, w, cin, plan.cout,
-                    _stream())
-        return out
-    if plan.wgt_stem is not None and USE_STEM and h % 2 == 0 and w % 2 == 0 and residual is None and (out_h, out_w) == (ho, wo):
-        sdims = _ints([plan.code, n, h, w, plan.cout, plan.act])
+    r = conv_route(p, n, h, w, out_hw, residual is not None, _L.get_variant())
+    k, ln, m = r.kernel, r.ln_fused, n * ho * wo
+    if p.has_ln and not ln:
+        x = layernorm(x, None, None, p.ln_eps)
+    if k == "head":
+        with _timed("head3x3|%d->%d %dx%dx%d" % (cin, p.cout, n, ho, wo), cost):
+            _L.call("cobevt_conv3x3_head_nchw", _p(x), _p(p.wgt_head), _p(p.bias), _p(out), p.code, n, h, w, cin, p.cout, _stream())
+    elif k == "stem":
+        sdims = _ints([p.code, n, h, w, p.cout, p.act])
         with _timed("stem7x7|%dx%dx%d" % (n, h, w), cost):
-            _L.call("cobevt_stem_conv7x7s2", _p(x), _p(plan.wgt_stem), _p(plan.bias), _p(out), sdims, _stream())
-        return out
-    if plan.wgt_rows is not None and USE_GEMM_ROWS and not (residual is not None and (out_h, out_w) != (ho, wo)):
-        ldims = (ctypes.c_long * 16)(plan.code, n * ho * wo, plan.cout, plan.K, plan.kp_rows, cin, plan.pre_relu, plan.act,
-                                     ho, wo, out_h, out_w, int(ln), plan.stride, h, w)
-        v2 = USE_GEMM_ROWS2 and plan.wfrag_rows is not None and plan.cout % (8 if plan.code == BF16 else 4) == 0
-        # K <= 128 bf16 rows: the row-chain-style kernel (32-row workgroups, fragment-ordered weights from L2)
-        v3 = (USE_GEMM_ROWS3 and plan.code == BF16 and plan.wfrag_rows is not None and plan.kp_rows <= GEMM_ROWS3_MAX_K
-              and plan.K % 8 == 0 and (out_h, out_w) == (ho, wo) and plan.cout % 8 == 0 and plan.cout <= 4096 and sm == 0
-              and not (plan.stride > 1 and (residual is not None or not GEMM_ROWS3_STRIDED))
-              and not (ln and plan.kp_rows > 128) and n * ho * wo >= GEMM_ROWS3_MIN_M)
-        # ... and its fp32-storage form (round 6, csrc/gemm_rows3_f32.hip): K <= 512, the fused LayerNorm for K = 128
-        v3 = v3 or (USE_GEMM_ROWS3_F32 and plan.code == FP32 and plan.wfrag_rows is not None and plan.kp_rows <= 512 and plan.K % 4 == 0
-                    and (out_h, out_w) == (ho, wo) and plan.cout % 4 == 0 and plan.cout <= 4096 and sm == 0
-                    and not (plan.stride > 1 and residual is not None) and not (ln and plan.K != 128)
-                    and not (ln and plan.pre_scale is not None) and n * ho * wo >= GEMM_ROWS3_MIN_M)
-        if v3:
-            d3 = (ctypes.c_long * 14)(plan.code, n * ho * wo, plan.cout, plan.K, cin, plan.pre_relu, plan.act, int(ln),
-                                      plan.stride, ho, wo, h, w,
-                                      64 if (GEMM_ROWS3_ROWS64_MIN_M and n * ho * wo >= GEMM_ROWS3_ROWS64_MIN_M) else 32)
-            with _timed("gemm_rows|%d->%d M=%d%s%s r32" % (cin, plan.cout, n * ho * wo, " ln" if ln else "",
-                                                        " s%d" % plan.stride if plan.stride > 1 else ""), cost):
-                _L.call("cobevt_linear_rows_small_k", _p(x), _p(plan.wfrag_rows), _p(plan.bias), _p(residual), _p(plan.pre_scale),
-                        _p(plan.pre_shift), _p(out), d3, ctypes.c_float(plan.ln_eps), _stream())
-            return out
-        with _timed("gemm_rows|%d->%d M=%d%s%s" % (cin, plan.cout, n * ho * wo, " ln" if ln else "",
-                                                   " s%d" % plan.stride if plan.stride > 1 else ""), cost):
-            if v2:      # persistent workgroups, fragment-ordered weights
-                _L.call("cobevt_linear_rows_wfrag", _p(x), _p(plan.wfrag_rows), _p(plan.bias), _p(residual), _p(plan.pre_scale),
-                        _p(plan.pre_shift), _p(out), ldims, ctypes.c_float(plan.ln_eps), _stream())
-            else:
-                _L.call("cobevt_linear_rows", _p(x), _p(plan.wgt_rows), _p(plan.bias), _p(residual), None, None, _p(plan.pre_scale),
-                        _p(plan.pre_shift), _p(out), ldims, ctypes.c_float(plan.ln_eps), _stream())
-        return out
-    variant = 0
-    # (the stride-2 strip variants sit at the 256-VGPR limit in fp32: with the operand split of the f32s library they spill
-    # hundreds of registers, so that library's three stride-2 3x3 convs of a ResNet take the generic implicit GEMM)
-    if plan.wfrag is not None and (out_h, out_w) == (ho, wo) and USE_CONV3X3 and USE_CONV3_WFRAG \
-            and (plan.stride == 1 or (USE_CONV3_S2 and not (plan.code == FP32 and _L.get_variant() == "f32s"))):
-        variant = CONV3_VARIANT or conv3_tiling(n, ho, wo, cin, plan.cout, plan.cc3, stride=plan.stride, bf16=plan.code == BF16,
-                                                packed=(0.5 if _L.get_variant() == "f32h" else 0.75 if _L.get_variant() == "f32s" else 0) if plan.code == FP32 else 0)
-        if variant == 0 and plan.stride == 2:
-            variant = 151 if plan.cout <= 64 else 150
-    if variant > 0:
-        dims = _ints([plan.code, n, h, w, cin, plan.cout, plan.upsample, plan.act, sm, plan.cc3, plan.coutp3, variant,
-                      plan.stride])
-        with _timed("conv3x3|%d->%d %dx%dx%d" % (cin, plan.cout, n, ho, wo), cost):
-            _L.call("cobevt_conv3x3_wfrag_nhwc", _p(x), _p(plan.wfrag), _p(plan.bias), _p(residual), _p(out), dims, _stream())
-        return out
-    if plan.wgt3 is not None and (out_h, out_w) == (ho, wo) and USE_CONV3X3:
-        dims = _ints([plan.code, n, h, w, cin, plan.cout, plan.upsample, plan.act, sm, plan.cc3])
-        with _timed("conv3x3|%d->%d %dx%dx%d" % (cin, plan.cout, n, ho, wo), cost):
-            _L.call("cobevt_conv3x3_nhwc", _p(x), _p(plan.wgt3), _p(plan.bias), _p(residual), _p(out), dims, _stream())
-        return out
-    dims = _ints([plan.code, n, h, w, cin, ho, wo, plan.cout, plan.kh, plan.kw, plan.stride, plan.pad, plan.K,
-                  plan.kpad, plan.upsample, plan.pre_relu, plan.act, sm, out_h, out_w, plan.smallc])
-    with _timed("igemm|k%ds%d %d->%d M=%d%s" % (plan.kh, plan.stride, cin, plan.cout, n * ho * wo, " stem" if plan.smallc else ""), cost):
-        _L.call("cobevt_conv2d_nhwc", _p(x), _p(plan.wgt), _p(plan.bias), _p(residual), _p(plan.pre_scale), _p(plan.pre_shift),
-                _p(plan.klut), _p(out), dims, _stream())
+            _L.call("cobevt_stem_conv7x7s2", _p(x), _p(p.wgt_stem), _p(p.bias), _p(out), sdims, _stream())
+    elif k in ("strips", "conv3"):
+        with _timed("conv3x3|%d->%d %dx%dx%d" % (cin, p.cout, n, ho, wo), cost):
+            _launch_conv3x3(x, p.wfrag if r.variant else p.wgt3, p.bias, residual, out, cout=p.cout, tile=r.variant, stride=p.stride,
+                            upsample=p.upsample, act=p.act, store_mode=sm)
+    elif k == "igemm":
+        with _timed("igemm|k%ds%d %d->%d M=%d%s" % (p.kh, p.stride, cin, p.cout, m, " stem" if p.smallc else ""), cost):
+            _launch_conv2d_nhwc(x, p.wgt, p.bias, residual, p.pre_scale, p.pre_shift, p.klut, out, ho, wo, p.kh, p.kw, stride=p.stride,
+                                pad=p.pad, upsample=p.upsample, pre_relu=p.pre_relu, act=p.act, store_mode=sm, out_hw=out_hw)
+    else:
+        fam = "gemm_rows|%d->%d M=%d%s%s" % (cin, p.cout, m, " ln" if ln else "", " s%d" % p.stride if p.stride > 1 else "")
+        with _timed(fam + " r32" if r.rows else fam, cost):
+            _launch_rows(x, p.wgt_rows if k == "rows" else p.wfrag_rows, p.bias, residual, p.pre_scale, p.pre_shift, out, kp=p.kp_rows,
+                         rows=r.rows, wfrag=k == "rows_wfrag", pre_relu=p.pre_relu, act=p.act, ln=ln, ln_eps=p.ln_eps, stride=p.stride)
     return out
 
 
@@ -563,7 +581,7 @@ def conv3_ds_fusable(x, plan1, plan2, plan_ds):
         return 0
     n, h, w, _ = x.shape
     ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1
-    variant = CONV3_VARIANT or conv3_tiling(n, ho, wo, plan2.cin, plan2.cout, 64)
+    variant = conv3_variant(n, ho, wo, plan2.cin, plan2.cout, 64, 1)
     mt, code = (variant - 100) // 10, (variant - 100) % 10
     return variant if (variant >= 100 and 3 <= mt <= 5 and code in (0, 1)) else 0
 

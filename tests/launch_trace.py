@@ -188,6 +188,74 @@ def _detect_post():
     ops.detect_post_process(dev_cavs, cd.SCORE_THRESHOLD, cd.NMS_THRESH, "hwl")
 
 
+_RECORDER = None        # the Recorder of the trace() that is running
+
+
+def _note(symbol, *vals):
+    """a pseudo-record (no launch): a row boundary or a host-side decision of the conv2d table"""
+    _RECORDER.records.append(["", symbol, list(vals)])
+
+
+def _conv2d_table():
+    """every branch of ops.conv2d's routing and the training launchers of autograd.py, one direct call per row of cases_conv on zero
+    tensors; each row sets its own switches and library variant and restores them"""
+    import cases_conv as cv
+
+    def zeros(shape, dt):
+        return torch.zeros(shape, dtype=cv.DTYPES[dt])
+
+    for r in cv.ROWS:
+        plan = cv.plan(r)
+        old = {k: getattr(ops, k) for k in r["knobs"]}
+        old_variant = lib.get_variant()
+        x = zeros(r["x"], "fp32" if plan.smallc else r["dt"])
+        _note("row", r["name"])
+        try:
+            for k, v in r["knobs"].items():
+                setattr(ops, k, v)
+            lib.set_variant(r["lib"])
+            if len(r["w"]) == 2:
+                ops.linear(x, plan, residual=zeros(r["x"][:-1] + (plan.cout,), r["dt"]) if r["res"] else None)
+            else:
+                n = r["x"][0]
+                ho, wo = plan.out_hw(*r["x"][1:3])
+                ops.conv2d(x, plan, residual=zeros((n, ho, wo, plan.cout), r["dt"]) if r["res"] else None,
+                           out=zeros((n,) + r["out"] + (plan.cout,), r["dt"]) if r["out"] else None)
+        finally:
+            lib.set_variant(old_variant)
+            for k, v in old.items():
+                setattr(ops, k, v)
+    # the training launchers, while an fp32-storage library is the active one: they must reach the native library ("") all the same
+    old_variant = lib.get_variant()
+    lib.set_variant("f32s")
+    try:
+        for shape, dt, cout, k, stride, pad, has_bias in cv.IGEMM_ROWS:
+            _note("row", "autograd._igemm_rows")
+            cin = shape[3]
+            w2 = zeros((cout, autograd._kpad(k * k * cin, cv.DTYPES[dt])), dt)
+            ho, wo = ((s + 2 * pad - k) // stride + 1 for s in shape[1:3])
+            autograd._igemm_rows(zeros(shape, dt), w2, cout, cin, k, k, torch.zeros(cout) if has_bias else None, stride, pad, ho, wo)
+        for shape, variant, cout, stride, has_bias in cv.CONV3_STRIPS:
+            _note("row", "autograd._conv3_strips")
+            operand = autograd.conv3_weight_operand(torch.zeros(cout, shape[3], 3, 3), variant, False)     # (one more launch in the trace)
+            autograd._conv3_strips(zeros(shape, "bf16"), operand, variant, cout, torch.zeros(cout) if has_bias else None, stride)
+        for m, n_out, k_in, has_bias in cv.ROWS_GEMM:
+            _note("row", "autograd._rows_gemm")
+            autograd._rows_gemm(zeros((m, k_in), "bf16"), zeros((8,), "bf16"), n_out, k_in, torch.zeros(n_out) if has_bias else None)
+    finally:
+        lib.set_variant(old_variant)
+    # Conv2dFn's 3x3 tile choice: ops.conv3_variant on 64-channel chunks (autograd.conv3_strips_plan on the commits that still have it)
+    tile_choice = getattr(autograd, "conv3_strips_plan", None) or (
+        lambda n, ho, wo, cin, cout, stride: ops.conv3_variant(n, ho, wo, cin, cout, 64, stride))
+    for args in cv.STRIPS_PLAN:
+        old = ops.CONV3_VARIANT
+        try:
+            ops.CONV3_VARIANT = args[6]
+            _note("Conv2dFn.tile_choice", *(args + (tile_choice(*args[:6]),)))
+        finally:
+            ops.CONV3_VARIANT = old
+
+
 CASES = {}
 for _mode in MODES:
     CASES["corpbevt_small.%s" % _mode] = _corpbevt(_mode)
@@ -199,10 +267,12 @@ for _mode in MODES:
 CASES["corpbevt_small_train.fp32"] = _corpbevt_train
 CASES["voxelize_points"] = _voxelize
 CASES["detect_post_process"] = _detect_post
+CASES["conv2d_table"] = _conv2d_table
 
 
 def trace(name, setattr_, status=None):
-    rec = Recorder(status)
+    global _RECORDER
+    rec = _RECORDER = Recorder(status)
     install(setattr_, rec)
     CASES[name]()
     return rec.records

@@ -1,6 +1,7 @@
 """CPU: the launch sequence of every model (tests/launch_trace.py) against the fixtures under tests/golden/launch_traces/, and the
 call path / library selection / COBEVT_FLAGS behaviour the routing code rests on.  No GPU and no built library: lib.load is a fake."""
 import json
+import math
 
 import pytest
 import torch
@@ -30,6 +31,54 @@ def test_fast_mode_trace_splits_the_libraries():
     assert sorted(by_variant) == ["f32h", "f32s"]
     assert {"cobevt_window_attention", "cobevt_stem_conv7x7s2_pool", "cobevt_basicblock_nhwc"} <= by_variant["f32h"]
     assert "cobevt_window_attention" not in by_variant["f32s"] and "cobevt_sttf_warp" in by_variant["f32s"]
+
+
+def test_conv2d_table_launches_every_conv_entry_point():
+    """the routing table reaches all eight kernels of ops.conv2d (the model traces never launch two of them)"""
+    assert len(ops.CONV_SYMBOLS) == 8
+    assert set(ops.CONV_SYMBOLS.values()) <= {name for _, name, _ in lt.read_fixture("conv2d_table")}
+
+
+def test_conv_route_agrees_with_the_recorded_table(monkeypatch):
+    """ops.conv_route names, for every conv2d / linear row of the table, the entry point the fixture (recorded before conv_route
+    existed) shows launched, with the recorded library, LayerNorm placement, strip variant and rows per workgroup - and takes the
+    library from its argument alone, whatever lib.get_variant() says meanwhile"""
+    import cases_conv as cv
+    launched = []
+    for record in lt.read_fixture("conv2d_table"):
+        if record[1] == "row":
+            launched.append([])
+        else:
+            launched[-1].append(record)
+    routes = {}
+    for r, records in zip(cv.ROWS, launched):
+        plan = cv.plan(r)
+        n, h, w = (1, 1, math.prod(r["x"][:-1])) if len(r["w"]) == 2 else r["x"][:3]
+        with monkeypatch.context() as m:
+            for knob, value in r["knobs"].items():
+                m.setattr(ops, knob, value)
+            got = set()
+            for ambient in lib.VARIANTS:
+                m.setattr(lib, "_variant", ambient)
+                got.add(ops.conv_route(plan, n, h, w, r["out"], r["res"], r["lib"]))
+        assert len(got) == 1, "%s: the route moves with lib.get_variant(): %s" % (r["name"], got)
+        route = routes[r["name"]] = got.pop()
+        separate_ln = plan.has_ln and not route.ln_fused
+        want = ["cobevt_layernorm"] * separate_ln + [ops.CONV_SYMBOLS[route.kernel]]
+        assert [name for _, name, _ in records] == want, r["name"]
+        assert {variant for variant, _, _ in records} == {r["lib"]}, r["name"]
+        dims = next((v for v in records[-1][2] if isinstance(v, list)), None)
+        if route.kernel == "strips":
+            assert route.variant == dims[11] > 0, r["name"]
+        else:
+            assert route.variant == 0, r["name"]
+        if route.kernel == "rows_small_k":
+            assert (route.rows, int(route.ln_fused)) == (dims[13], dims[7]), r["name"]
+        elif route.kernel in ("rows", "rows_wfrag"):
+            assert int(route.ln_fused) == dims[12], r["name"]
+        assert not (route.ln_fused and not plan.has_ln), r["name"]
+    # one stride-2 fp32 plan, three libraries, three routes: the library is an input of the decision like any other
+    assert [routes["c3_s2.fp32.lib" + v][::2] for v in ("native", "f32s", "f32h")] == [("strips", 131), ("igemm", 0), ("strips", 130)]
 
 
 def test_failing_key_split_launch_names_its_own_symbol(monkeypatch):
