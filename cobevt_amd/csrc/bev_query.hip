@@ -17,11 +17,12 @@ namespace cobevt {
 
 namespace {
 
-constexpr int kMaxCams = 32;                       // B * n cameras whose offsets fit the LDS table
+constexpr int kMaxCams = kBqMaxCams;               // B * n cameras whose offsets fit the LDS table
 constexpr int kWBytes = 32 * 1024;                 // 32 fragments
 // LDS: to_q fragments (accumulator k order) | embedding operand base[128] uint4 {cx_hi cx_hi | cx_lo cy_hi | cy_hi cy_lo | -}
 //      | czw[B n][128] bf16 pair {cz_hi, cz_lo} of (b_bev - w_cam . c) | bias[128]
 constexpr int kLdsBytes = kWBytes + 128 * 16 + kMaxCams * 128 * 4 + 128 * 4;
+static_assert(kLdsBytes == kBqLds, "rows_select.hpp");
 
 // x = hi + lo with both halves bf16 values (|x - hi - lo| <= 2^-17 |x|)
 __device__ __forceinline__ void split_bf(float x, float& hi, float& lo) {
@@ -196,17 +197,9 @@ __global__ __launch_bounds__(NW * 64, 3) void bev_query_kernel(BevQueryParams p,
 
 }  // namespace
 
-// gemm_rows3.hip's entry point cobevt_bev_embed_linear_rows_small_k hands the 128 -> 128 LayerNorm case to this launcher;
-// returns -1 when the shape does not qualify
-int launch_bev_query(const BevQueryParams& p, hipStream_t stream) {
-    if (p.hw % 32 != 0 || (long)p.B * p.n > kMaxCams || p.B < 1 || p.n < 1) return -1;
-    constexpr int NW = 4;
-    cobevt::allow_dynamic_lds<bev_query_kernel<NW>>(kLdsBytes);
-    const int nblk = p.B * (p.hw >> 5) * p.n;
-    int blocks = (nblk + NW - 1) / NW;
-    if (blocks > 256 * 3) blocks = 256 * 3;                // persistent: three workgroups (12 waves) per CU
-    hipLaunchKernelGGL((bev_query_kernel<NW>), dim3((unsigned)blocks), dim3(NW * 64), kLdsBytes, stream, p, nblk);
-    return cobevt::launch_status();
+// gemm_rows3.hip's entry point cobevt_bev_embed_linear_rows_small_k hands the 128 -> 128 LayerNorm case to this launcher
+int launch_bev_query(const BevQueryParams& p, const RowsLaunch& l, hipStream_t stream) {
+    return launch_rows<bev_query_kernel<4>>(l, kLdsBytes, stream, p, l.nblk);
 }
 
 }  // namespace cobevt

@@ -1,6 +1,6 @@
 // Parameter block of the fused BEV-query kernel (bev_query.hip); launched from gemm_rows3.hip's embedding entry point.
 #pragma once
-#include "common.hpp"
+#include "rows_launch.hpp"
 
 namespace cobevt {
 
@@ -18,6 +18,6 @@ struct BevQueryParams {
     float ln_eps;
 };
 
-int launch_bev_query(const BevQueryParams& p, hipStream_t stream);
+int launch_bev_query(const BevQueryParams& p, const RowsLaunch& l, hipStream_t stream);
 
 }  // namespace cobevt

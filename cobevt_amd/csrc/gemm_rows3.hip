@@ -17,33 +17,7 @@
 
 namespace cobevt {
 
-struct Gr3Params {
-    const bf16_t* in;       // [M][lda]
-    const uint4* wfrag;     // fragment-ordered [N_p/32][8][64 lanes][16 B]
-    const float* bias;      // [N] or null
-    const bf16_t* residual; // [M][N] or null
-    const float* pre_scale; // [K] or null (with pre_shift)
-    const float* pre_shift;
-    bf16_t* out;            // [M][N]
-    int M, N, K, Kp;        // Kp = K rounded up to 128 (<= 512): the fragment array has Kp / 16 k-groups per 32-column tile
-    long lda;
-    int pre_relu, act, ln;
-    float ln_eps;
-    int in_stride, src_H, src_W, in_H, in_W;   // in_stride > 1: row m = (n, oy, ox) of an (src_H, src_W) map reads input pixel
-                                               // (oy * in_stride, ox * in_stride) of an (in_H, in_W) map (1x1 / stride-2 conv)
-    // EMB: the A rows are the BEV query  x[b][pix] + L2norm_c(w_bev . world[pix] + b_bev - w_cam . E_inv[b, cam][:, 3])
-    // (fax_modules.py:370-375,387-388) of row m = ((b * n + cam) * hw + pix), produced while staging; `in` is x (B | 1, hw, K)
-    const float* emb_E; const float* emb_world; const float* emb_wbev; const float* emb_bbev; const float* emb_wcam;
-    int emb_n, emb_hw, emb_xbcast;
-    // navg > 1: A row m = (b, r) is the MEAN of the navg rows in[b * avg_batch_stride + j * avg_stride + r * lda], j < navg
-    // (SwapFusionEncoder.mlp_head: Reduce('b m d h w -> b d h w', 'mean') -> LayerNorm -> Linear, swap_fusion_modules.py:275-281)
-    int navg, avg_rows_per_batch;
-    long avg_stride, avg_batch_stride;
-};
-
-constexpr int kG3Row = 256 + 16;            // staged output row: 128 bf16 + pad
-constexpr int kG3Rows = 32;
-// LDS: A rows [32][Kp * 2 + 16] | output tile [32][272] | N_p floats of bias
+// Gr3Params: rows_launch.hpp.  LDS: A rows [32][Kp * 2 + 16] | output tile [32][272] | N_p floats of bias (rows_select.hpp: g3_lds)
 
 // ROWS = 32 (4 waves) or 64 (8 waves = 2 row halves x 4 column tiles: every weight fragment serves twice the rows)
 template <bool EMB, int ROWS = 32>
@@ -248,118 +222,70 @@ __global__ __launch_bounds__(ROWS * 8, 4) void gemm_rows3_kernel(Gr3Params p) {
     }
 }
 
+// the kernel's parameter block of a parsed call; the pointers are the caller's
+static Gr3Params gr3_params(const RowsGemmShape& s, const void* in, const void* wfrag, const float* bias, void* out, float ln_eps) {
+    Gr3Params p = {};
+    p.in = (const bf16_t*)in; p.wfrag = (const uint4*)wfrag; p.bias = bias; p.out = (bf16_t*)out;
+    p.M = s.M; p.N = s.N; p.K = s.K; p.Kp = s.Kp; p.lda = s.lda;
+    p.pre_relu = s.pre_relu; p.act = s.act; p.ln = s.ln; p.ln_eps = ln_eps;
+    p.in_stride = s.in_stride; p.src_H = s.src_H; p.src_W = s.src_W; p.in_H = s.in_H; p.in_W = s.in_W;
+    p.emb_n = s.emb_n; p.emb_hw = s.emb_hw; p.emb_xbcast = s.emb_xbcast;
+    p.navg = s.navg; p.avg_rows_per_batch = s.avg_rows_per_batch; p.avg_stride = s.avg_stride; p.avg_batch_stride = s.avg_batch_stride;
+    return p;
+}
+
+static int launch_gr3(const Gr3Params& p, const RowsLaunch& l, hipStream_t stream) {
+    switch (l.family) {
+        case ROWS_GEMM3_F32: return launch_linear_rows_f32(p, l, stream);
+        case ROWS_LN_LINEAR64: return launch_ln_linear64(p, l, stream);
+        default:
+            if (l.ROWS == 64) return launch_rows<gemm_rows3_kernel<false, 64>>(l, g3_lds(64, 512, 4096), stream, p);
+            if (!l.EMB) return launch_rows<gemm_rows3_kernel<false, 32>>(l, 0, stream, p);
+            return launch_rows<gemm_rows3_kernel<true, 32>>(l, 0, stream, p);
+    }
+}
+
 }  // namespace cobevt
 
 using namespace cobevt;
 
-// C-ABI entry point, see include/cobevt_hip.h
-namespace cobevt {
-int launch_linear_rows_f32(const void* in, const void* wfrag, const float* bias, const void* residual, const float* pre_scale,
-                           const float* pre_shift, void* out, const long* dims, float ln_eps, hipStream_t stream);   // gemm_rows3_f32.hip
-int launch_ln_linear64(const void* in, const void* wfrag, const float* bias, void* out, int M, int N, int K, long lda, int act, float eps,
-                       hipStream_t stream);                                                                          // ln_linear64.hip
-}
-
+// C-ABI entry point, see include/cobevt_hip.h.  fp32 storage: the tensor pointers travel in the same block (gemm_rows3_f32.hip casts them back)
 extern "C" int cobevt_linear_rows_small_k(const void* in, const void* wfrag, const float* bias, const void* residual,
                                           const float* pre_scale, const float* pre_shift, void* out, const long* dims, float ln_eps,
                                           hipStream_t stream) {
-    // dims: [dtype(0), M, N, K, lda, pre_relu, act, ln, in_stride, src_H, src_W, in_H, in_W, rows_per_workgroup]
-    if (!in || !wfrag || !out || !dims) return COBEVT_ERR_ARG;
-    if (dims[0] == 1) {                                  // fp32 storage: gemm_rows3_f32.hip (round 6)
-        const int rc = cobevt::launch_linear_rows_f32(in, wfrag, bias, residual, pre_scale, pre_shift, out, dims, ln_eps, stream);
-        return rc < 0 ? COBEVT_ERR_UNSUPPORTED : rc;
-    }
-    if (dims[0] != 0) return COBEVT_ERR_UNSUPPORTED;
-    Gr3Params p;
-    p.in = (const bf16_t*)in; p.wfrag = (const uint4*)wfrag; p.bias = bias; p.residual = (const bf16_t*)residual;
-    p.pre_scale = pre_scale; p.pre_shift = pre_shift; p.out = (bf16_t*)out;
-    p.M = (int)dims[1]; p.N = (int)dims[2]; p.K = (int)dims[3]; p.lda = dims[4];
-    p.pre_relu = (int)dims[5]; p.act = (int)dims[6]; p.ln = (int)dims[7]; p.ln_eps = ln_eps;
-    p.in_stride = (int)dims[8]; p.src_H = (int)dims[9]; p.src_W = (int)dims[10]; p.in_H = (int)dims[11]; p.in_W = (int)dims[12];
-    p.Kp = (p.K + 127) / 128 * 128;
-    if (p.M < 1 || p.N < 8 || p.N % 8 || p.N > 4096 || p.K < 8 || p.K > 512 || p.K % 8 || p.lda < p.K || p.lda % 8) return COBEVT_ERR_SHAPE;
-    if (p.ln && p.K > 128) return COBEVT_ERR_UNSUPPORTED;          // LayerNorm fusion needs the row in one 128-channel tile
-    if (p.in_stride < 1 || (p.in_stride > 1 && (p.src_H < 1 || p.src_W < 1 || p.in_H < 1 || p.in_W < 1 || p.M % (p.src_H * p.src_W))))
-        return COBEVT_ERR_SHAPE;
-    if (p.in_stride > 1 && residual) return COBEVT_ERR_UNSUPPORTED;
-    if ((pre_scale == nullptr) != (pre_shift == nullptr)) return COBEVT_ERR_ARG;
-    if (p.ln && pre_scale) return COBEVT_ERR_UNSUPPORTED;
-    if (p.act < 0 || p.act > 4) return COBEVT_ERR_ARG;
-    if (p.ln && !residual && !pre_scale && !p.pre_relu && p.in_stride == 1) {   // LayerNorm + Linear of a big 64-channel map: independent waves
-        const int rc = cobevt::launch_ln_linear64(in, wfrag, bias, out, p.M, p.N, p.K, p.lda, p.act, ln_eps, stream);
-        if (rc >= 0) return rc;
-    }
-    const int rows = dims[13] == 64 ? 64 : 32;                     // dims[13]: rows per workgroup (0 = 32)
-    const size_t lds = (size_t)rows * (p.Kp * 2 + 16) + (size_t)rows * kG3Row + (size_t)((p.N + 127) / 128) * 128 * 4;
-    const unsigned blocks = (unsigned)((p.M + rows - 1) / rows);
-    p.emb_E = p.emb_world = p.emb_wbev = p.emb_bbev = p.emb_wcam = nullptr;
-    p.emb_n = p.emb_hw = 1; p.emb_xbcast = 0;
-    p.navg = 1; p.avg_rows_per_batch = 1; p.avg_stride = p.avg_batch_stride = 0;
-    if (rows == 64) {
-        cobevt::allow_dynamic_lds<gemm_rows3_kernel<false, 64>>(64 * 1040 + 64 * kG3Row + 4096 * 4);
-        hipLaunchKernelGGL((gemm_rows3_kernel<false, 64>), dim3(blocks), dim3(512), lds, stream, p);
-    } else {
-        hipLaunchKernelGGL((gemm_rows3_kernel<false, 32>), dim3(blocks), dim3(256), lds, stream, p);
-    }
-    return cobevt::launch_status();
+    RowsGemmShape s;
+    const int rc = small_k_parse(dims, in && wfrag && out, residual != nullptr, pre_scale != nullptr, pre_shift != nullptr, s);
+    if (rc != COBEVT_OK) return rc;
+    Gr3Params p = gr3_params(s, in, wfrag, bias, out, ln_eps);
+    p.residual = (const bf16_t*)residual; p.pre_scale = pre_scale; p.pre_shift = pre_shift;
+    return launch_gr3(p, small_k_select(s, rows_gates()), stream);
 }
 
 // C-ABI entry point, see include/cobevt_hip.h
 extern "C" int cobevt_bev_embed_linear_rows_small_k(const float* E_inv, const float* world, const float* w_bev, const float* b_bev,
                                                     const float* w_cam, const void* x, const void* wfrag, const float* bias, void* out,
                                                     const long* dims, float ln_eps, hipStream_t stream) {
-    // dims: [dtype(0), B, n, hw, D (= K <= 128), N, ln, x_bcast]
-    if (!E_inv || !world || !w_bev || !b_bev || !w_cam || !x || !wfrag || !out || !dims) return COBEVT_ERR_ARG;
-    if (dims[0] != 0) return COBEVT_ERR_UNSUPPORTED;
-    const long B = dims[1], n = dims[2], hw = dims[3];
-    if (dims[4] == 128 && dims[5] == 128 && dims[6] && hw % 32 == 0 && B >= 1 && n >= 1 && B * n * hw <= 0x7fffffffL) {
-        // the FAX level-0 shape: the wave-level kernel (bev_query.hip) - rows never leave the registers, weights in LDS
+    RowsGemmShape s;
+    const int rc = bev_embed_parse(dims, E_inv && world && w_bev && b_bev && w_cam && x && wfrag && out, s);
+    if (rc != COBEVT_OK) return rc;
+    const RowsLaunch l = bev_embed_select(s);
+    if (l.family == ROWS_BEV_QUERY) {
         BevQueryParams q;
         q.E_inv = E_inv; q.world = world; q.w_bev = w_bev; q.b_bev = b_bev; q.w_cam = w_cam; q.x = (const bf16_t*)x;
         q.wfrag = (const uint4*)wfrag; q.bias = bias; q.out = (bf16_t*)out;
-        q.B = (int)B; q.n = (int)n; q.hw = (int)hw; q.x_bcast = (int)dims[7]; q.ln_eps = ln_eps;
-        const int rc = launch_bev_query(q, stream);
-        if (rc >= 0) return rc;
+        q.B = s.emb_B; q.n = s.emb_n; q.hw = s.emb_hw; q.x_bcast = s.emb_xbcast; q.ln_eps = ln_eps;
+        return launch_bev_query(q, l, stream);
     }
-    Gr3Params p;
-    p.in = (const bf16_t*)x; p.wfrag = (const uint4*)wfrag; p.bias = bias; p.residual = nullptr;
-    p.pre_scale = p.pre_shift = nullptr; p.out = (bf16_t*)out;
-    p.K = (int)dims[4]; p.N = (int)dims[5]; p.ln = (int)dims[6]; p.ln_eps = ln_eps;
-    p.Kp = 128; p.lda = p.K; p.pre_relu = 0; p.act = 0;
-    p.in_stride = 1; p.src_H = p.src_W = p.in_H = p.in_W = 1;
-    if (B < 1 || n < 1 || hw < 1 || hw % kG3Rows != 0 || B * n * hw > 0x7fffffffL) return COBEVT_ERR_SHAPE;   // one camera per workgroup
-    if (p.N < 8 || p.N % 8 || p.N > 4096 || p.K < 8 || p.K > 128 || p.K % 8) return COBEVT_ERR_SHAPE;
-    p.M = (int)(B * n * hw);
+    Gr3Params p = gr3_params(s, x, wfrag, bias, out, ln_eps);
     p.emb_E = E_inv; p.emb_world = world; p.emb_wbev = w_bev; p.emb_bbev = b_bev; p.emb_wcam = w_cam;
-    p.emb_n = (int)n; p.emb_hw = (int)hw; p.emb_xbcast = (int)dims[7];
-    p.navg = 1; p.avg_rows_per_batch = 1; p.avg_stride = p.avg_batch_stride = 0;
-    const size_t lds = (size_t)kG3Rows * (p.Kp * 2 + 16) + (size_t)kG3Rows * kG3Row + (size_t)((p.N + 127) / 128) * 128 * 4 + 128 * 16;
-    const unsigned blocks = (unsigned)((p.M + kG3Rows - 1) / kG3Rows);
-    hipLaunchKernelGGL((gemm_rows3_kernel<true, 32>), dim3(blocks), dim3(256), lds, stream, p);
-    return cobevt::launch_status();
+    return launch_gr3(p, l, stream);
 }
 
 // C-ABI entry point, see include/cobevt_hip.h: out (B * R, N) = act(LayerNorm?(mean_j in[b][j][r][:]) . W^T + bias), in (B, L, R, K)
 extern "C" int cobevt_mean_linear_rows_small_k(const void* in, const void* wfrag, const float* bias, void* out, const long* dims,
                                                float ln_eps, hipStream_t stream) {
-    // dims: [dtype(0), B, L, R, K, N, ln, act]
-    if (!in || !wfrag || !out || !dims) return COBEVT_ERR_ARG;
-    if (dims[0] != 0) return COBEVT_ERR_UNSUPPORTED;
-    const long B = dims[1], Lr = dims[2], R = dims[3];
-    Gr3Params p;
-    p.in = (const bf16_t*)in; p.wfrag = (const uint4*)wfrag; p.bias = bias; p.residual = nullptr;
-    p.pre_scale = p.pre_shift = nullptr; p.out = (bf16_t*)out;
-    p.K = (int)dims[4]; p.N = (int)dims[5]; p.ln = (int)dims[6]; p.act = (int)dims[7]; p.ln_eps = ln_eps;
-    p.Kp = 128; p.lda = p.K; p.pre_relu = 0;
-    p.in_stride = 1; p.src_H = p.src_W = p.in_H = p.in_W = 1;
-    if (B < 1 || Lr < 1 || Lr > 64 || R < 1 || B * R > 0x7fffffffL) return COBEVT_ERR_SHAPE;
-    if (p.N < 8 || p.N % 8 || p.N > 4096 || p.K < 8 || p.K > 128 || p.K % 8 || p.act < 0 || p.act > 4) return COBEVT_ERR_SHAPE;
-    p.M = (int)(B * R);
-    p.emb_E = p.emb_world = p.emb_wbev = p.emb_bbev = p.emb_wcam = nullptr;
-    p.emb_n = p.emb_hw = 1; p.emb_xbcast = 0;
-    p.navg = (int)Lr; p.avg_rows_per_batch = (int)R; p.avg_stride = R * p.K; p.avg_batch_stride = Lr * R * p.K;
-    const size_t lds = (size_t)kG3Rows * (p.Kp * 2 + 16) + (size_t)kG3Rows * kG3Row + (size_t)((p.N + 127) / 128) * 128 * 4;
-    const unsigned blocks = (unsigned)((p.M + kG3Rows - 1) / kG3Rows);
-    hipLaunchKernelGGL((gemm_rows3_kernel<false, 32>), dim3(blocks), dim3(256), lds, stream, p);
-    return cobevt::launch_status();
+    RowsGemmShape s;
+    const int rc = mean_parse(dims, in && wfrag && out, s);
+    if (rc != COBEVT_OK) return rc;
+    return launch_gr3(gr3_params(s, in, wfrag, bias, out, ln_eps), mean_select(s), stream);
 }

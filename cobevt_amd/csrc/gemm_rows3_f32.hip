@@ -8,6 +8,7 @@
 // through stage_x_piece (already split in the split-bf16 / fp16 libraries), wave w owns columns [32 w, 32 w + 32) of every 128-column
 // pass, weights as MFMA fragments straight from L2 in two ping-pong sets of eight k-groups with the next set in flight, D = W . X^T so
 // bias / residual / activation happen in registers, results leave through an fp32 LDS tile as 16-byte coalesced stores.
+#include "rows_launch.hpp"
 #include "wave_ops.hpp"
 #include "f32_matrix.hpp"
 
@@ -15,8 +16,8 @@ namespace cobevt {
 
 namespace {
 
-constexpr int kRows = 32, kThreads = 256;
-constexpr int kYRow = 512 + 16;             // staged output row: 128 fp32 + pad
+constexpr int kRows = kG3fRows, kThreads = 256;
+constexpr int kYRow = kG3fYRow;             // staged output row: 128 fp32 + pad
 
 struct Gr3fParams {
     const float* in;        // [M][lda]
@@ -179,28 +180,15 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_rows3_f32_kernel(Gr3fParams 
 
 }  // namespace
 
-// the fp32-storage form of cobevt_linear_rows_small_k (gemm_rows3.hip); -1 when the shape does not qualify
-int launch_linear_rows_f32(const void* in, const void* wfrag, const float* bias, const void* residual, const float* pre_scale,
-                           const float* pre_shift, void* out, const long* dims, float ln_eps, hipStream_t stream) {
-    // dims: [dtype(1), M, N, K, lda, pre_relu, act, ln, in_stride, src_H, src_W, in_H, in_W, rows_per_workgroup (ignored)]
+// the fp32-storage form of cobevt_linear_rows_small_k (gemm_rows3.hip)
+int launch_linear_rows_f32(const Gr3Params& g, const RowsLaunch& l, hipStream_t stream) {
     Gr3fParams p;
-    p.in = (const float*)in; p.wfrag = (const uint4*)wfrag; p.bias = bias; p.residual = (const float*)residual;
-    p.pre_scale = pre_scale; p.pre_shift = pre_shift; p.out = (float*)out;
-    p.M = (int)dims[1]; p.N = (int)dims[2]; p.K = (int)dims[3]; p.lda = dims[4];
-    p.pre_relu = (int)dims[5]; p.act = (int)dims[6]; p.ln = (int)dims[7]; p.ln_eps = ln_eps;
-    p.in_stride = (int)dims[8]; p.src_H = (int)dims[9]; p.src_W = (int)dims[10]; p.in_H = (int)dims[11]; p.in_W = (int)dims[12];
-    p.Kp = (p.K + 63) / 64 * 64;
-    if (p.M < 1 || p.N < 4 || p.N % 4 || p.N > 4096 || p.K < 4 || p.K > 512 || p.K % 4 || p.lda < p.K || p.lda % 4) return -1;
-    if (p.ln && p.K != 128) return -1;                    // the fused LayerNorm is the 128-channel one of the FAX / fusion blocks
-    if (p.in_stride < 1 || (p.in_stride > 1 && (p.src_H < 1 || p.src_W < 1 || p.in_H < 1 || p.in_W < 1 || p.M % (p.src_H * p.src_W)))) return -1;
-    if (p.in_stride > 1 && residual) return -1;
-    if ((pre_scale == nullptr) != (pre_shift == nullptr) || (p.ln && pre_scale)) return -1;
-    if (p.act < 0 || p.act > 4) return -1;
-    const size_t lds = (size_t)kRows * (p.Kp * 4 + 16) + (size_t)kRows * kYRow + (size_t)((p.N + 127) / 128) * 128 * 4;
-    cobevt::allow_dynamic_lds<gemm_rows3_f32_kernel>(kRows * (512 * 4 + 16) + kRows * kYRow + 4096 * 4);
-    const unsigned blocks = (unsigned)((p.M + kRows - 1) / kRows);
-    hipLaunchKernelGGL(gemm_rows3_f32_kernel, dim3(blocks), dim3(kThreads), lds, stream, p);
-    return cobevt::launch_status();
+    p.in = (const float*)g.in; p.wfrag = g.wfrag; p.bias = g.bias; p.residual = (const float*)g.residual;
+    p.pre_scale = g.pre_scale; p.pre_shift = g.pre_shift; p.out = (float*)g.out;
+    p.M = g.M; p.N = g.N; p.K = g.K; p.Kp = g.Kp; p.lda = g.lda;
+    p.pre_relu = g.pre_relu; p.act = g.act; p.ln = g.ln; p.ln_eps = g.ln_eps;
+    p.in_stride = g.in_stride; p.src_H = g.src_H; p.src_W = g.src_W; p.in_H = g.in_H; p.in_W = g.in_W;
+    return launch_rows<gemm_rows3_f32_kernel>(l, g3f_lds(512, 4096), stream, p);
 }
 
 }  // namespace cobevt

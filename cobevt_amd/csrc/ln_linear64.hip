@@ -8,7 +8,7 @@
 // addresses, the two lanes that share a row complete each other's LayerNorm sums with one cross-half exchange, D = W . X^T hands the lane
 // four-column runs that a v_permlane32_swap per register turns back into 16-byte stores - waves never synchronise, and the NEXT block's
 // rows are requested before the current block's arithmetic starts.
-#include <stdlib.h>
+#include "rows_launch.hpp"
 #include "wave_ops.hpp"
 
 namespace cobevt {
@@ -121,36 +121,20 @@ __global__ __launch_bounds__(NW * 64, 6) void ln_linear64_kernel(LnLin64Params p
     }
 }
 
-template <int NNT> int launch_nnt(const LnLin64Params& p, hipStream_t stream) {
-    constexpr int NW = 4;
-    constexpr int lds = NNT * 4 * 1024 + NNT * 32 * 4;
-    const int nblk = (p.M + 31) / 32;
-    int blocks = (nblk + NW - 1) / NW;
-    // persistent: SIX co-resident workgroups per CU (24.8 KB of LDS and 72 VGPRs each) walk the 32-row blocks.  Measured on the LiDAR
-    // shape (M = 524,288, N = 192): 512 workgroups 90.8 us, 1024 84.2, 1536 64.8 (4.1 TB/s), 2048 (not co-resident: a tail) 79.8.
-    static const int cap = [] { const char* e = getenv("COBEVT_LN64_BLOCKS"); return e && atoi(e) > 0 ? atoi(e) : 1536; }();
-    if (blocks > cap) blocks = cap;
-    hipLaunchKernelGGL((ln_linear64_kernel<NNT, NW>), dim3((unsigned)blocks), dim3(NW * 64), lds, stream, p, nblk);
-    return cobevt::launch_status();
-}
-
 }  // namespace
 
-// the big-map LayerNorm + Linear fast path of cobevt_linear_rows_small_k (gemm_rows3.hip); -1 when the shape does not qualify
-int launch_ln_linear64(const void* in, const void* wfrag, const float* bias, void* out, int M, int N, int K, long lda, int act, float eps,
-                       hipStream_t stream) {
-    static const bool on = [] { const char* e = getenv("COBEVT_LN_LINEAR64"); return !(e && e[0] == '0'); }();
-    if (!on || K != 64 || lda != 64 || N < 32 || N > 192 || N % 32 || M < 65536) return -1;
+// the big-map LayerNorm + Linear fast path of cobevt_linear_rows_small_k (gemm_rows3.hip; rows_select.hpp: small_k_select)
+int launch_ln_linear64(const Gr3Params& g, const RowsLaunch& l, hipStream_t stream) {
     LnLin64Params p;
-    p.in = (const bf16_t*)in; p.wfrag = (const uint4*)wfrag; p.bias = bias; p.out = (bf16_t*)out;
-    p.M = M; p.N = N; p.act = act; p.eps = eps;
-    switch (N / 32) {
-        case 1: return launch_nnt<1>(p, stream);
-        case 2: return launch_nnt<2>(p, stream);
-        case 3: return launch_nnt<3>(p, stream);
-        case 4: return launch_nnt<4>(p, stream);
-        case 5: return launch_nnt<5>(p, stream);
-        default: return launch_nnt<6>(p, stream);
+    p.in = g.in; p.wfrag = g.wfrag; p.bias = g.bias; p.out = g.out;
+    p.M = g.M; p.N = g.N; p.act = g.act; p.eps = g.ln_eps;
+    switch (l.NNT) {
+        case 1: return launch_rows<ln_linear64_kernel<1, 4>>(l, 0, stream, p, l.nblk);
+        case 2: return launch_rows<ln_linear64_kernel<2, 4>>(l, 0, stream, p, l.nblk);
+        case 3: return launch_rows<ln_linear64_kernel<3, 4>>(l, 0, stream, p, l.nblk);
+        case 4: return launch_rows<ln_linear64_kernel<4, 4>>(l, 0, stream, p, l.nblk);
+        case 5: return launch_rows<ln_linear64_kernel<5, 4>>(l, 0, stream, p, l.nblk);
+        default: return launch_rows<ln_linear64_kernel<6, 4>>(l, 0, stream, p, l.nblk);
     }
 }
 

@@ -16,11 +16,12 @@ namespace cobevt {
 
 namespace {
 
-constexpr int kFp = 0, kFn = 32, kMaxNnt = 8;               // fragments: Wp 4 x 8 (natural), Wn up to 8 tiles x 8 (accumulator order)
+constexpr int kFp = 0, kFn = 32, kMaxNnt = kPcMaxNnt;              // fragments: Wp 4 x 8 (natural), Wn up to 8 tiles x 8 (accumulator order)
 constexpr int kTab = (kFn + kMaxNnt * 8) * 1024;             // fp32 tables behind the 96 KB of fragments:
 constexpr int kSc = 0, kSh = 128, kBp = 256, kBn = 384;      // pre_scale[128] pre_shift[128] bp[128] bn[256]
 constexpr int kTabFloats = 640;
 constexpr int kLdsBytes = kTab + kTabFloats * 4;             // 100,864 B: one workgroup per CU
+static_assert(kLdsBytes == kPc128Lds, "rows_select.hpp");
 
 // NNT: 32-column tiles of the next projection (Nn = 32 NNT).  NW waves per workgroup.
 template <int NNT, int NW>
@@ -196,27 +197,12 @@ __global__ __launch_bounds__(NW * 64, 1) void proj_chain128_kernel(RowChainParam
     }
 }
 
-template <int NNT> int launch128(const RowChainParams& p, hipStream_t stream) {
-    constexpr int NW = 8;
-    cobevt::allow_dynamic_lds<proj_chain128_kernel<NNT, NW>>(kLdsBytes);
-    const int nblk = (p.M + 31) / 32;
-    int blocks = (nblk + NW - 1) / NW;
-    if (blocks > 256) blocks = 256;                        // persistent: one workgroup per CU
-    hipLaunchKernelGGL((proj_chain128_kernel<NNT, NW>), dim3((unsigned)blocks), dim3(NW * 64), kLdsBytes, stream, p, nblk);
-    return cobevt::launch_status();
-}
-
 }  // namespace
 
-// cobevt_proj_chain (row_chain.hip) hands the big maps to this launcher; -1 = shape does not qualify
-int launch_proj_chain128(const RowChainParams& p, hipStream_t stream) {
-    if (p.C != 128 || !p.wn || !p.out_next || p.Nn % 32 != 0 || p.Nn > 32 * kMaxNnt || p.next_act != 0) return -1;
-    if (p.M < 32768) return -1;                            // smaller maps: the 32-row workgroups of the generic kernel fill the chip better
-    switch (p.Nn / 32) {
-        case 4: return launch128<4>(p, stream);
-        case 8: return launch128<8>(p, stream);
-        default: return -1;
-    }
+// cobevt_proj_chain (row_chain.hip) hands the big maps to this launcher
+int launch_proj_chain128(const RowChainParams& p, const RowsLaunch& l, hipStream_t stream) {
+    if (l.NNT == 4) return launch_rows<proj_chain128_kernel<4, 8>>(l, kLdsBytes, stream, p, l.nblk);
+    return launch_rows<proj_chain128_kernel<8, 8>>(l, kLdsBytes, stream, p, l.nblk);
 }
 
 }  // namespace cobevt

@@ -44,7 +44,8 @@ template <int ROWS> struct RcLds {
 // Filled once per workgroup, zero where a vector is absent or shorter: the phase epilogues read it with unconditional
 // ds_read_b128 instead of starting with a (branch-guarded -> vmcnt(0)) global round trip that also waited for the next
 // phase's weight-fragment prefetch.
-constexpr int kRcBp = 0, kRcB1 = 128, kRcB2 = 384, kRcPg = 512, kRcPb = 640, kRcBn = 768, kRcBnMax = 768, kRcBiasFloats = 1536;
+constexpr int kRcBp = 0, kRcB1 = 128, kRcB2 = 384, kRcPg = 512, kRcPb = 640, kRcBn = 768, kRcBiasFloats = 1536;
+static_assert(kRcBn + kRcBnMax == kRcBiasFloats && RcLds<32>::BYTES == rc_lds(32) && RcLds<64>::BYTES == rc_lds(64), "rows_select.hpp");
 
 // normalise one row held by 8 lanes (16 channels each; channels >= C are zero on entry and on exit)
 __device__ __forceinline__ void rc_normalise(float (&v)[16], int sub, int C, float eps) {
@@ -330,92 +331,77 @@ __global__ __launch_bounds__(ROWS * 8, 4) void row_chain_kernel(RowChainParams p
     }
 }
 
-template <int NPASS, int ROWS, bool FULL, bool MLP = true>
-static void launch_chain(const RowChainParams& p, hipStream_t stream) {
-    cobevt::allow_dynamic_lds<row_chain_kernel<NPASS, ROWS, FULL, MLP>>(RcLds<ROWS>::BYTES);
-    const unsigned blocks = (unsigned)((p.M + ROWS - 1) / ROWS);
-    hipLaunchKernelGGL((row_chain_kernel<NPASS, ROWS, FULL, MLP>), dim3(blocks), dim3(ROWS * 8), RcLds<ROWS>::BYTES, stream, p);
+// the generic kernel's instantiation for a selection (the cases stand in the order the code object has always held the kernels)
+static int launch_generic(const RowChainParams& p, const RowsLaunch& l, hipStream_t stream) {
+    constexpr int lds64 = RcLds<64>::BYTES, lds32 = RcLds<32>::BYTES;
+    switch (l.MLP ? l.ROWS * 100 + l.NPASS * 10 + l.FULL : 0) {           // <ROWS><NPASS><FULL>
+        case 6421: return launch_rows<row_chain_kernel<2, 64, true>>(l, lds64, stream, p);
+        case 6420: return launch_rows<row_chain_kernel<2, 64, false>>(l, lds64, stream, p);
+        case 6411: return launch_rows<row_chain_kernel<1, 64, true>>(l, lds64, stream, p);
+        case 6410: return launch_rows<row_chain_kernel<1, 64, false>>(l, lds64, stream, p);
+        case 3221: return launch_rows<row_chain_kernel<2, 32, true>>(l, lds32, stream, p);
+        case 3220: return launch_rows<row_chain_kernel<2, 32, false>>(l, lds32, stream, p);
+        case 3211: return launch_rows<row_chain_kernel<1, 32, true>>(l, lds32, stream, p);
+        case 3210: return launch_rows<row_chain_kernel<1, 32, false>>(l, lds32, stream, p);
+        default: return launch_rows<row_chain_kernel<1, 32, true, false>>(l, lds32, stream, p);     // projection chain
+    }
+}
+
+static int launch_chain(const RowChainParams& p, const RowsLaunch& l, hipStream_t stream) {
+    switch (l.family) {
+        case ROWS_CHAIN_F32: return launch_row_chain_f32(p, l, stream);
+        case ROWS_CHAIN64: return launch_row_chain64(p, l, stream);
+        case ROWS_PROJ128: return launch_proj_chain128(p, l, stream);
+        default: return launch_generic(p, l, stream);
+    }
+}
+
+// the kernels' parameter block of a parsed call; the pointers are the caller's
+static RowChainParams chain_params(const ChainShape& s, float eps1, float eps_post, float eps_next) {
+    RowChainParams p = {};
+    p.M = s.M; p.C = s.C; p.Hd = s.Hd; p.Hdp = s.Hdp;
+    p.Nn = s.Nn; p.next_ln = s.next_ln; p.next_act = s.next_act; p.skip_rows = s.skip_rows;
+    p.eps1 = eps1; p.eps_post = eps_post; p.eps_next = eps_next;
+    p.pre_relu = s.pre_relu;
+    return p;
 }
 
 }  // namespace cobevt
 
 using namespace cobevt;
 
-// C-ABI entry point, see include/cobevt_hip.h
+// C-ABI entry point, see include/cobevt_hip.h.  fp32 storage: the tensor pointers travel in the same block (row_chain_f32.hip casts them back)
 extern "C" int cobevt_attn_mlp_chain(const void* a, const void* skip, void* out, const void* wp, const float* bp,
                                      const void* w1, const float* b1, const void* w2, const float* b2,
                                      const float* post_gamma, const float* post_beta, const void* wnext, const float* bnext,
                                      void* out_next, const int* dims, float eps1, float eps_post, float eps_next,
                                      hipStream_t stream) {
-    // dims: [dtype, M, C, Hd, Hdp, Nn, next_ln, next_act, rows_per_workgroup, skip_rows]
-    if (!a || !out || !wp || !w1 || !b1 || !w2 || !b2 || !dims) return COBEVT_ERR_ARG;
-    if (dims[0] != 0 && dims[0] != 1) return COBEVT_ERR_ARG;
-    if (dims[0] == 1) {                                        // fp32 storage: the C = 128 / hidden 256 chain (row_chain_f32.hip); other widths run the GEMMs separately
-        if ((post_gamma == nullptr) != (post_beta == nullptr) || (wnext == nullptr) != (out_next == nullptr)) return COBEVT_ERR_ARG;
-        const int M = dims[1], sr = dims[9] > 0 ? dims[9] : dims[1];
-        if (M < 1 || sr > M || M % sr || (wnext && (dims[7] < 0 || dims[7] > 2))) return COBEVT_ERR_SHAPE;
-        const int rc = launch_row_chain_f32(a, skip, out, wp, bp, w1, b1, w2, b2, post_gamma, post_beta, wnext, bnext, out_next, M, dims[2], dims[3],
-                                            dims[4], dims[5], dims[6], dims[7], sr, eps1, eps_post, eps_next, stream);
-        return rc < 0 ? COBEVT_ERR_UNSUPPORTED : rc;
-    }
-    RowChainParams p;
+    ChainShape s;
+    const int rc = chain_parse(dims, a && out && wp && w1 && b1 && w2 && b2, skip != nullptr, post_gamma != nullptr, post_beta != nullptr,
+                               wnext != nullptr, out_next != nullptr, s);
+    if (rc != COBEVT_OK) return rc;
+    const RowsLaunch l = chain_select(s, rows_gates());
+    if (l.status != COBEVT_OK) return l.status;
+    RowChainParams p = chain_params(s, eps1, eps_post, eps_next);
     p.a = (const bf16_t*)a; p.skip = (const bf16_t*)skip; p.out = (bf16_t*)out;
     p.wp = (const uint4*)wp; p.bp = bp; p.w1 = (const uint4*)w1; p.b1 = b1; p.w2 = (const uint4*)w2; p.b2 = b2;
     p.post_g = post_gamma; p.post_b = post_beta;
     p.wn = (const uint4*)wnext; p.bn = bnext; p.out_next = (bf16_t*)out_next;
-    p.M = dims[1]; p.C = dims[2]; p.Hd = dims[3]; p.Hdp = dims[4];
-    p.Nn = dims[5]; p.next_ln = dims[6]; p.next_act = dims[7];
-    p.skip_rows = dims[9] > 0 ? dims[9] : p.M;                 // dims[9]: rows of `skip` (0 = M), M % skip_rows == 0
-    p.eps1 = eps1; p.eps_post = eps_post; p.eps_next = eps_next;
-    p.pre_scale = p.pre_shift = nullptr; p.pre_relu = 0;
-    if (p.M < 1 || p.C < 8 || p.C > 128 || p.C % 8 || p.Hd < 8 || p.Hd > 256 || p.Hd % 8) return COBEVT_ERR_SHAPE;
-    if (p.Hdp % 128 || p.Hdp < p.Hd || p.Hdp > 256) return COBEVT_ERR_SHAPE;
-    if (p.skip_rows > p.M || p.M % p.skip_rows) return COBEVT_ERR_SHAPE;
-    if ((post_gamma == nullptr) != (post_beta == nullptr)) return COBEVT_ERR_ARG;
-    if ((wnext == nullptr) != (out_next == nullptr)) return COBEVT_ERR_ARG;
-    if (wnext && (p.Nn < 8 || p.Nn % 8 || p.Nn > kRcBnMax || p.next_act < 0 || p.next_act > 2)) return COBEVT_ERR_SHAPE;
-    if (dims[8] == 0) {                                        // automatic: 64-channel chains on big maps take the persistent form
-        const int rc = launch_row_chain64(p, stream);
-        if (rc >= 0) return rc;
-    }
-    const int rows = dims[8] == 64 ? 64 : 32;                  // dims[8]: rows per workgroup (0 = default 32; 32 / 64 pin the generic kernel)
-    const bool two = p.Hd > 128, full = p.C == 128;
-    if (rows == 64) {
-        if (two) { if (full) launch_chain<2, 64, true>(p, stream); else launch_chain<2, 64, false>(p, stream); }
-        else { if (full) launch_chain<1, 64, true>(p, stream); else launch_chain<1, 64, false>(p, stream); }
-    } else {
-        if (two) { if (full) launch_chain<2, 32, true>(p, stream); else launch_chain<2, 32, false>(p, stream); }
-        else { if (full) launch_chain<1, 32, true>(p, stream); else launch_chain<1, 32, false>(p, stream); }
-    }
-    return cobevt::launch_status();
+    return launch_chain(p, l, stream);
 }
 
 // Projection chain, see include/cobevt_hip.h: y = ReLU?(a * pre_scale + pre_shift) . Wp^T + bp + skip ; next = act(LN?(y) . Wn'^T + bn')
 extern "C" int cobevt_proj_chain(const void* a, const float* pre_scale, const float* pre_shift, const void* skip, const void* wp,
                                  const float* bp, void* out, const void* wnext, const float* bnext, void* out_next, const int* dims,
                                  float eps_next, hipStream_t stream) {
-    // dims: [dtype, M, C (= 128), Nn, next_ln, next_act, skip_rows, pre_relu, variant (0 = automatic, 1 = the barrier-phased kernel)]
-    if (!a || !wp || !wnext || !bnext || !out_next || !dims) return COBEVT_ERR_ARG;
-    if ((pre_scale == nullptr) != (pre_shift == nullptr)) return COBEVT_ERR_ARG;
-    if (dims[0] != 0) return COBEVT_ERR_UNSUPPORTED;
-    RowChainParams p;
+    ChainShape s;
+    const int rc = proj_parse(dims, a && wp && wnext && bnext && out_next, pre_scale != nullptr, pre_shift != nullptr, skip != nullptr, s);
+    if (rc != COBEVT_OK) return rc;
+    RowChainParams p = chain_params(s, 0.f, 0.f, eps_next);
     p.a = (const bf16_t*)a; p.skip = (const bf16_t*)skip; p.out = (bf16_t*)out;
     p.wp = (const uint4*)wp; p.bp = bp;
     p.w1 = (const uint4*)wnext; p.b1 = bnext; p.w2 = (const uint4*)wnext; p.b2 = bnext;      // unused by the projection chain (valid stand-ins)
-    p.post_g = p.post_b = nullptr;
     p.wn = (const uint4*)wnext; p.bn = bnext; p.out_next = (bf16_t*)out_next;
-    p.M = dims[1]; p.C = dims[2]; p.Hd = 8; p.Hdp = 128;
-    p.Nn = dims[3]; p.next_ln = dims[4]; p.next_act = dims[5];
-    p.skip_rows = dims[6] > 0 ? dims[6] : p.M;
-    p.pre_scale = pre_scale; p.pre_shift = pre_shift; p.pre_relu = dims[7];
-    p.eps1 = 0.f; p.eps_post = 0.f; p.eps_next = eps_next;
-    if (p.M < 1 || p.C != 128) return COBEVT_ERR_SHAPE;             // K = C = 128 (the level-0 feature / embedding width)
-    if (p.Nn < 8 || p.Nn % 8 || p.Nn > kRcBnMax || p.next_act < 0 || p.next_act > 2) return COBEVT_ERR_SHAPE;
-    if (p.skip_rows > p.M || p.M % p.skip_rows) return COBEVT_ERR_SHAPE;
-    if (dims[8] == 0) {
-        const int rc = launch_proj_chain128(p, stream);         // big maps: rows in registers, weights in LDS (proj_chain128.hip)
-        if (rc >= 0) return rc;
-    }
-    launch_chain<1, 32, true, false>(p, stream);
-    return cobevt::launch_status();
+    p.pre_scale = pre_scale; p.pre_shift = pre_shift;
+    return launch_chain(p, proj_select(s), stream);
 }

@@ -1,6 +1,7 @@
-// Parameter block of the fused row-local chain (row_chain.hip) and of its 64-channel persistent form (row_chain64.hip).
+// Parameter block of the fused row-local chain: row_chain.hip, its wave-level forms row_chain64.hip (64 channels) and proj_chain128.hip
+// (projection chain, 128 channels), its fp32-storage form row_chain_f32.hip, and proj_chain_k.hip.
 #pragma once
-#include "common.hpp"
+#include "rows_launch.hpp"
 
 namespace cobevt {
 
@@ -30,17 +31,15 @@ struct RowChainParams {
     int pre_relu;
 };
 
+// What row_chain.hip's two entry points hand a call to when csrc/rows_select.hpp selects another family than the generic kernel
+// (`l` is the selection: instantiation, grid, LDS):
 // row_chain64.hip: the chain for C = 64 / hidden 128 (LiDAR FuseBEVT, swap_fusion_modules.py:87-128 with input_dim 64) as persistent
-// workgroups with every weight fragment resident in registers; returns COBEVT_OK, an error code, or -1 when the shape does not
-// qualify (the caller then launches the generic kernel)
-int launch_row_chain64(const RowChainParams& p, hipStream_t stream);
+// workgroups with every weight fragment resident in LDS and the rows in registers
+int launch_row_chain64(const RowChainParams& p, const RowsLaunch& l, hipStream_t stream);
 // proj_chain128.hip: the projection chain (MLP = false form: pre-activation -> Wp + skip -> LN -> Wn) on big 128-channel maps, same idea
-int launch_proj_chain128(const RowChainParams& p, hipStream_t stream);
-
-// row_chain_f32.hip: the same chain for fp32 storage (C = 128, hidden 256; exact / split-bf16 matrix path by library); -1 = shape does not qualify
-int launch_row_chain_f32(const void* a, const void* skip, void* out, const void* wp, const float* bp, const void* w1, const float* b1,
-                         const void* w2, const float* b2, const float* post_g, const float* post_b, const void* wnext, const float* bnext,
-                         void* out_next, int M, int C, int Hd, int Hdp, int Nn, int next_ln, int next_act, int skip_rows, float eps1,
-                         float eps_post, float eps_next, hipStream_t stream);
+int launch_proj_chain128(const RowChainParams& p, const RowsLaunch& l, hipStream_t stream);
+// row_chain_f32.hip: the same chain for fp32 storage (C = 128, hidden 256; exact / split-bf16 matrix path by library); p's tensor
+// pointers are fp32 tensors
+int launch_row_chain_f32(const RowChainParams& p, const RowsLaunch& l, hipStream_t stream);
 
 }  // namespace cobevt

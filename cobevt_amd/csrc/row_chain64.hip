@@ -19,7 +19,6 @@
 //     the two 8-byte column runs of the accumulator order and back;
 //   * waves never synchronise, so 12-16 independent waves per CU hide each other's load latency (the barrier-phased form ran
 //     157 us per launch, a 64-row tile costing ~20k cycles of mostly exposed round trips).
-#include <stdlib.h>
 #include "row_chain.hpp"
 #include "wave_ops.hpp"
 
@@ -32,6 +31,7 @@ namespace {
 constexpr int kFp = 0, kF1 = kFp + 8, kF2 = kF1 + 16, kFn = kF2 + 16, kFrags = kFn + 24;      // in 1-KB fragments
 constexpr int kBp = 0, kB1 = 64, kB2 = 192, kPg = 256, kPb = 320, kBn = 384, kBiasFloats = 576;
 constexpr int kLdsBytes = kFrags * 1024 + kBiasFloats * 4;                                    // 67,840 B: two workgroups per CU
+static_assert(kLdsBytes == kRc64Lds, "rows_select.hpp");
 
 // v[t][r]: the lane's 32 values of its row (2 column tiles x 16 accumulator registers) -> normalised over the row's 64 channels
 __device__ __forceinline__ void row_normalise(float (&v)[2][16], float eps) {
@@ -55,7 +55,7 @@ __device__ __forceinline__ void row_normalise(float (&v)[2][16], float eps) {
 
 // NNT2: 32-column tiles of the next projection (Nn = 32 NNT2 <= 192; 0 = none).  NW waves per workgroup.
 // PF (round 6): the NEXT block's a / skip rows are requested before the current block's chain starts (32 more registers: four waves per
-// workgroup instead of six) - the shipped form, launch64 below.
+// workgroup instead of six) - the shipped form (rows_select.hpp: chain_select).
 template <int NNT2, int NW, bool PF = false>
 __global__ __launch_bounds__(NW * 64, 2) void row_chain64_kernel(RowChainParams p, int nblk) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -291,36 +291,21 @@ __global__ __launch_bounds__(NW * 64, 2) void row_chain64_kernel(RowChainParams 
     }
 }
 
-template <int NNT2, int NW, bool PF> int launch64v(const RowChainParams& p, hipStream_t stream) {
-    cobevt::allow_dynamic_lds<row_chain64_kernel<NNT2, NW, PF>>(kLdsBytes);
-    const int nblk = (p.M + 31) / 32;
-    int blocks = (nblk + NW - 1) / NW;
-    if (blocks > 512) blocks = 512;                        // persistent: two workgroups per CU walk the 32-row blocks
-    hipLaunchKernelGGL((row_chain64_kernel<NNT2, NW, PF>), dim3((unsigned)blocks), dim3(NW * 64), kLdsBytes, stream, p, nblk);
-    return cobevt::launch_status();
-}
-template <int NNT2> int launch64(const RowChainParams& p, hipStream_t stream) {
-    // Round 6, same-job A/B on the LiDAR FuseBEVT workload (profiles/r06_rc64_prefetch_ab.txt): the next block's rows prefetched under the
-    // current block's chain, 2 x 4 waves per CU at 192 VGPRs - 102 -> 87 us per launch (370 MB: 3.6 -> 4.25 TB/s), 525 -> 538 frames/s; the
-    // same prefetch with six waves per workgroup (one workgroup per CU fits) 103 us.  COBEVT_RC64_PREFETCH=0 selects the round-5 form.
-    static const int mode = [] { const char* e = getenv("COBEVT_RC64_PREFETCH"); return e ? atoi(e) : 1; }();
-    if (mode == 1) return launch64v<NNT2, 4, true>(p, stream);
-    if (mode == 2) return launch64v<NNT2, 6, true>(p, stream);
-    return launch64v<NNT2, 6, false>(p, stream);                    // 2 workgroups x 6 waves per CU = 3 waves per SIMD, no prefetch
+// the three forms of COBEVT_RC64_PREFETCH (rows_select.hpp): four waves with prefetch, six with, six without
+template <int NNT2> int launch64(const RowChainParams& p, const RowsLaunch& l, hipStream_t stream) {
+    if (l.PF && l.NW == 4) return launch_rows<row_chain64_kernel<NNT2, 4, true>>(l, kLdsBytes, stream, p, l.nblk);
+    if (l.PF) return launch_rows<row_chain64_kernel<NNT2, 6, true>>(l, kLdsBytes, stream, p, l.nblk);
+    return launch_rows<row_chain64_kernel<NNT2, 6, false>>(l, kLdsBytes, stream, p, l.nblk);
 }
 
 }  // namespace
 
-int launch_row_chain64(const RowChainParams& p, hipStream_t stream) {
-    if (p.C != 64 || p.Hd != 128 || p.Hdp != 128 || !p.skip || p.skip_rows != p.M) return -1;
-    if (p.wn && (p.Nn % 32 != 0 || p.Nn > 192)) return -1;
-    if (p.M < 16384) return -1;                            // small maps: the generic kernel's finer workgroups fill the chip better
-    switch (p.wn ? p.Nn / 32 : 0) {
-        case 0: return launch64<0>(p, stream);
-        case 2: return launch64<2>(p, stream);
-        case 4: return launch64<4>(p, stream);
-        case 6: return launch64<6>(p, stream);
-        default: return -1;
+int launch_row_chain64(const RowChainParams& p, const RowsLaunch& l, hipStream_t stream) {
+    switch (l.NNT) {
+        case 0: return launch64<0>(p, l, stream);
+        case 2: return launch64<2>(p, l, stream);
+        case 4: return launch64<4>(p, l, stream);
+        default: return launch64<6>(p, l, stream);
     }
 }
 

@@ -37,7 +37,9 @@ struct F32Lds {
     static constexpr int BIAS = H + kFRows * kFHRow;         // fp32 table: [0,128) bp, [128,384) b1, [384,512) b2, [512,640) post gamma, [640,768) post beta, [768,1536) bnext
     static constexpr int BYTES = BIAS + 4 * 1536;
 };
-constexpr int kBp = 0, kB1 = 128, kB2 = 384, kPg = 512, kPb = 640, kBn = 768, kBnMax = 768, kBiasFloats = 1536;
+static_assert(F32Lds::BYTES == kRcF32Lds, "rows_select.hpp");
+constexpr int kBp = 0, kB1 = 128, kB2 = 384, kPg = 512, kPb = 640, kBn = 768, kBiasFloats = 1536;
+static_assert(kBn + kRcF32BnMax == kBiasFloats, "rows_select.hpp");
 
 struct RowChainF32Params {
     const float* a; const float* skip; float* out;
@@ -261,23 +263,15 @@ __global__ __launch_bounds__(kFThreads, 2) void row_chain_f32_kernel(RowChainF32
 
 }  // namespace
 
-// the fp32-storage form of cobevt_attn_mlp_chain (row_chain.hip): C = 128, hidden 256; returns -1 when the shape does not qualify
-int launch_row_chain_f32(const void* a, const void* skip, void* out, const void* wp, const float* bp, const void* w1, const float* b1,
-                         const void* w2, const float* b2, const float* post_g, const float* post_b, const void* wnext, const float* bnext,
-                         void* out_next, int M, int C, int Hd, int Hdp, int Nn, int next_ln, int next_act, int skip_rows, float eps1,
-                         float eps_post, float eps_next, hipStream_t stream) {
-    if (C != 128 || Hd != 256 || Hdp != 256) return -1;
-    if (wnext && (Nn < 4 || Nn % 4 || Nn > kBnMax)) return -1;
+// the fp32-storage form of cobevt_attn_mlp_chain (row_chain.hip): C = 128, hidden 256
+int launch_row_chain_f32(const RowChainParams& c, const RowsLaunch& l, hipStream_t stream) {
     RowChainF32Params p;
-    p.a = (const float*)a; p.skip = (const float*)skip; p.out = (float*)out;
-    p.wp = (const uint4*)wp; p.bp = bp; p.w1 = (const uint4*)w1; p.b1 = b1; p.w2 = (const uint4*)w2; p.b2 = b2;
-    p.post_g = post_g; p.post_b = post_b; p.wn = (const uint4*)wnext; p.bn = bnext; p.out_next = (float*)out_next;
-    p.M = M; p.Nn = Nn; p.next_ln = next_ln; p.next_act = next_act; p.skip_rows = skip_rows;
-    p.eps1 = eps1; p.eps_post = eps_post; p.eps_next = eps_next;
-    cobevt::allow_dynamic_lds<row_chain_f32_kernel>(F32Lds::BYTES);
-    const unsigned blocks = (unsigned)((M + kFRows - 1) / kFRows);
-    hipLaunchKernelGGL(row_chain_f32_kernel, dim3(blocks), dim3(kFThreads), F32Lds::BYTES, stream, p);
-    return cobevt::launch_status();
+    p.a = (const float*)c.a; p.skip = (const float*)c.skip; p.out = (float*)c.out;
+    p.wp = c.wp; p.bp = c.bp; p.w1 = c.w1; p.b1 = c.b1; p.w2 = c.w2; p.b2 = c.b2;
+    p.post_g = c.post_g; p.post_b = c.post_b; p.wn = c.wn; p.bn = c.bn; p.out_next = (float*)c.out_next;
+    p.M = c.M; p.Nn = c.Nn; p.next_ln = c.next_ln; p.next_act = c.next_act; p.skip_rows = c.skip_rows;
+    p.eps1 = c.eps1; p.eps_post = c.eps_post; p.eps_next = c.eps_next;
+    return launch_rows<row_chain_f32_kernel>(l, F32Lds::BYTES, stream, p);
 }
 
 }  // namespace cobevt

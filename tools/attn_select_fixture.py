@@ -15,9 +15,11 @@ import gzip
 import json
 import os
 import re
-import subprocess
 import sys
 import tempfile
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import select_fixture as sf  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "attn_select")
@@ -267,31 +269,13 @@ def parse_oracle(text):
 
 
 def record(rev):
-    sys.path.insert(0, ROOT)
-    from cobevt_amd.build import _hipcc
     with tempfile.TemporaryDirectory() as tmp:
-        listing = subprocess.check_output(["git", "-C", ROOT, "ls-tree", "--name-only", rev, "cobevt_amd/csrc/", "include/"]).decode().split()
-        for path in listing:
-            if path.endswith((".hip", ".hpp", ".h")):
-                dst = os.path.join(tmp, path)
-                os.makedirs(os.path.dirname(dst), exist_ok=True)
-                with open(dst, "wb") as f:
-                    f.write(subprocess.check_output(["git", "-C", ROOT, "show", "%s:%s" % (rev, path)]))
-        exe = os.path.join(tmp, "oracle")
-        subprocess.check_call([_hipcc(), "--offload-arch=gfx950", "--offload-host-only", "-std=c++17", "-O1", "-Wno-pass-failed", "-x", "hip",
-                               "-include", os.path.join(ROOT, "tools", "attn_select_shim.hpp"), "-I", os.path.join(tmp, "cobevt_amd", "csrc"),
-                               "-c", os.path.join(ROOT, "tools", "attn_select_oracle.cpp"), "-o", exe + ".o"])
-        # a host-only object still names the device image it was not given: left unresolved (null), nothing here launches a kernel
-        subprocess.check_call([_hipcc(), exe + ".o", "-Wl,--unresolved-symbols=ignore-all", "-o", exe])
+        sf.checkout(rev, tmp)
+        exe = sf.build_oracle(tmp, [os.path.join(ROOT, "tools", "attn_select_oracle.cpp")])
         cases = open(CASES).read()
         runs = {}
         for gates, env in [((1, 1), {}), ((0, 1), {"COBEVT_ATTN_BIG": "0"}), ((1, 0), {"COBEVT_ATTN_PERSIST": "0"})]:
-            e = {k: v for k, v in os.environ.items() if not k.startswith("COBEVT_ATTN_")}
-            e.update(env)
-            first = subprocess.run([exe], input=cases.encode(), stdout=subprocess.PIPE, env=e, check=True).stdout
-            if subprocess.run([exe], input=cases.encode(), stdout=subprocess.PIPE, env=e, check=True).stdout != first:
-                raise SystemExit("two runs of the oracle differ")
-            runs[gates] = parse_oracle(first.decode())
+            runs[gates] = parse_oracle(sf.run_twice(exe, cases, "COBEVT_ATTN_", env))
     lines = []
     for ln in cases.splitlines():
         tok = ln.split()
