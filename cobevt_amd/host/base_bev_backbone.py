@@ -1,0 +1,165 @@
+"""BaseBEVBackbone — the 2-D backbone of OpenCOOD's PointPillar models between the scattered BEV canvas and the heads
+(opencood/models/backbones/base_bev_backbone.py): per level ZeroPad2d(1) + 3 x 3 / stride-s conv + layer_nums[i] 3 x 3 convs, each with
+BatchNorm(eps 1e-3) + ReLU; per level a "deblock" ConvTranspose2d(kernel = stride = u) + BN + ReLU whose outputs are concatenated on
+channels into spatial_features_2d.  `blocks` / `deblocks` are ModuleLists of nn.Sequentials at the reference's indices, so the
+state_dict has the reference's keys and shapes (blocks.0.1.weight, blocks.0.2.running_mean, ..., deblocks.2.0.weight, ...).
+
+model_cfg: layer_nums, layer_strides, num_filters; optionally upsample_strides, num_upsample_filter.  The reference's branches:
+  * upsample_strides[i] >= 1: one cobevt_deconv_nhwc launch per level (ops.deconv_into) that writes its channel slice of the ONE
+    preallocated concatenated map - no pixel-shuffle copy, no BN / ReLU pass, no torch.cat.  A stride of 1 is the same kernel.
+  * upsample_strides[i] < 1: Conv2d(kernel = stride = round(1 / u)) through ops.conv2d into a temporary, copied into its slice.
+  * one more entry in upsample_strides than levels: a trailing deblock over the concatenated map (the same kernel, c_off = 0).
+  * no upsample_strides: the levels' own outputs are concatenated (they must share one H x W, as for the reference's torch.cat).
+The blocks run through ops.conv2d (the stride-s conv with pad 1 IS ZeroPad2d(1) + pad 0).  Levels whose deblock outputs do not share
+one H x W raise CobevtHipError before anything is launched.
+
+forward(data_dict) is the reference's contract: reads data_dict['spatial_features'] (N, C, H, W), writes and returns
+data_dict['spatial_features_2d'] (N, sum(num_upsample_filter), H', W') fp32 (the reference's per-level 'spatial_features_%dx' entries
+are not produced).  forward_nhwc(x) takes and returns NHWC tensors in the compute dtype; models use it.  No host synchronisation:
+the forward can be captured in a HIP graph.  Inference only: the backward of the transposed convolution is not implemented, so a
+train()-mode forward raises."""
+import torch
+import torch.nn as nn
+
+from .. import ops
+from ..lib import CobevtHipError
+from . import runtime as rt
+from .runtime import HipModule
+
+
+def _bn(c):
+    return nn.BatchNorm2d(c, eps=1e-3, momentum=0.01)
+
+
+class BaseBEVBackbone(HipModule):
+    def __init__(self, model_cfg, input_channels):
+        super().__init__()
+        self.model_cfg = model_cfg
+        layer_nums = list(model_cfg.get("layer_nums", []))
+        layer_strides = list(model_cfg.get("layer_strides", [])) if layer_nums else []
+        num_filters = list(model_cfg.get("num_filters", [])) if layer_nums else []
+        if not len(layer_nums) == len(layer_strides) == len(num_filters):
+            raise CobevtHipError("BaseBEVBackbone: layer_nums, layer_strides and num_filters must have one entry per level")
+        up_strides = list(model_cfg.get("upsample_strides", []))
+        up_filters = list(model_cfg.get("num_upsample_filter", [])) if up_strides else []
+        if len(up_strides) != len(up_filters):
+            raise CobevtHipError("BaseBEVBackbone: upsample_strides and num_upsample_filter must have the same length")
+        levels = len(layer_nums)
+        if up_strides and len(up_strides) not in (levels, levels + 1):
+            raise CobevtHipError("BaseBEVBackbone: %d upsample_strides for %d levels (one per level, or one more for a trailing deblock)"
+                                 % (len(up_strides), levels))
+        self.layer_strides, self.upsample_strides = [int(s) for s in layer_strides], up_strides
+        c_in = [input_channels] + num_filters[:-1]
+        self.blocks, self.deblocks = nn.ModuleList(), nn.ModuleList()
+        c_off = 0
+        for i in range(levels):
+            layers = [nn.ZeroPad2d(1), nn.Conv2d(c_in[i], num_filters[i], 3, stride=self.layer_strides[i], padding=0, bias=False),
+                      _bn(num_filters[i]), nn.ReLU()]
+            for _ in range(layer_nums[i]):
+                layers += [nn.Conv2d(num_filters[i], num_filters[i], 3, padding=1, bias=False), _bn(num_filters[i]), nn.ReLU()]
+            self.blocks.append(nn.Sequential(*layers))
+            if up_strides:
+                u, c = up_strides[i], up_filters[i]
+                if u >= 1:
+                    self._check_deblock(i, u, c, c_off)
+                    conv = nn.ConvTranspose2d(num_filters[i], c, int(u), stride=int(u), bias=False)
+                else:
+                    r = int(round(1.0 / u))
+                    conv = nn.Conv2d(num_filters[i], c, r, stride=r, bias=False)
+                self.deblocks.append(nn.Sequential(conv, _bn(c), nn.ReLU()))
+                c_off += c
+        # the reference sizes the trailing deblock sum(num_upsample_filter) -> the same, over ALL entries: its own entry has to be 0
+        # for that to be the width of the concatenated map it reads (the reference's forward throws otherwise)
+        total = sum(up_filters)
+        if len(up_strides) > levels:
+            if total != sum(up_filters[:levels]):
+                raise CobevtHipError("BaseBEVBackbone: the trailing deblock is sum(num_upsample_filter) = %d channels wide, the map it reads "
+                                     "%d: num_upsample_filter[-1] must be 0" % (total, sum(up_filters[:levels])))
+            self._check_deblock(levels, up_strides[-1], total, 0)
+            self.deblocks.append(nn.Sequential(nn.ConvTranspose2d(total, total, int(up_strides[-1]), stride=int(up_strides[-1]), bias=False),
+                                               _bn(total), nn.ReLU()))
+        # (without deblocks the reference reports sum([]) = 0; here it is the width of the map the forward returns)
+        self.num_bev_features = total if up_strides else sum(num_filters)
+
+    @staticmethod
+    def _check_deblock(i, u, c, c_off):
+        if int(u) != u or not 1 <= int(u) <= ops.DECONV_MAX_STRIDE:
+            raise CobevtHipError("BaseBEVBackbone: upsample_strides[%d] = %r: the transposed-conv kernel takes integer strides 1 .. %d"
+                                 % (i, u, ops.DECONV_MAX_STRIDE))
+        if c % 32 != 0 or c_off % 8 != 0:
+            raise CobevtHipError("BaseBEVBackbone: deblock %d writes %d channels at channel %d of the concatenated map; the transposed-conv "
+                                 "kernel needs a multiple of 32 channels at a multiple of 8" % (i, c, c_off))
+
+    # ---- plans
+    def _conv_plan(self, name, conv, bn, pad):
+        def build(dt, dev):
+            return ops.ConvPlan(conv.weight, None, bn=bn, stride=conv.stride[0], pad=pad, act=1, dtype=dt, device=dev)
+        return self._plan(name, rt.module_tensors(conv, bn), build)
+
+    def _deconv_plan(self, name, conv, bn):
+        def build(dt, dev):
+            return ops.DeconvPlan(conv.weight, bn, conv.stride[0], dt, dev)
+        return self._plan(name, rt.module_tensors(conv, bn), build)
+
+    # ---- shapes
+    def _level_sizes(self, h, w):
+        sizes = []
+        for s in self.layer_strides:
+            h, w = (h - 1) // s + 1, (w - 1) // s + 1           # 3 x 3, stride s, one zero row / column on every side
+            sizes.append((h, w))
+        return sizes
+
+    def _up_sizes(self, sizes):
+        if not len(self.deblocks):
+            return sizes
+        out = []
+        for (h, w), u in zip(sizes, self.upsample_strides):
+            if u >= 1:
+                out.append((h * int(u), w * int(u)))
+            else:
+                r = int(round(1.0 / u))
+                out.append(((h - r) // r + 1, (w - r) // r + 1))
+        return out
+
+    def forward_nhwc(self, x):
+        """(N, H, W, C) in the compute dtype -> (N, H', W', num_bev_features) in the compute dtype"""
+        self._require_inference(x)
+        n, h, w, _ = x.shape
+        levels = len(self.blocks)
+        if levels == 0:
+            return x
+        ups = self._up_sizes(self._level_sizes(h, w))
+        if any(hw != ups[0] for hw in ups) or min(ups[0]) < 1:
+            raise CobevtHipError("BaseBEVBackbone: the levels' outputs must share one H x W to be concatenated; a %d x %d input gives %s"
+                                 % (h, w, ", ".join("%d x %d" % hw for hw in ups)))
+        widths = [(self.deblocks[i][0] if len(self.deblocks) else self.blocks[i][1]).out_channels for i in range(levels)]
+        cat = None
+        if levels > 1 or len(self.deblocks):
+            cat = torch.empty((n, ups[0][0], ups[0][1], sum(widths)), device=x.device, dtype=x.dtype)
+        c_off = 0
+        for i, block in enumerate(self.blocks):
+            x = ops.conv2d(x, self._conv_plan("b%d.0" % i, block[1], block[2], 1))
+            for k in range(4, len(block), 3):
+                x = ops.conv2d(x, self._conv_plan("b%d.%d" % (i, k), block[k], block[k + 1], 1))
+            if len(self.deblocks):
+                conv, bn = self.deblocks[i][0], self.deblocks[i][1]
+                if isinstance(conv, nn.ConvTranspose2d):
+                    ops.deconv_into(x, self._deconv_plan("d%d" % i, conv, bn), cat, c_off)
+                else:
+                    cat[..., c_off:c_off + widths[i]] = ops.conv2d(x, self._conv_plan("d%d" % i, conv, bn, 0))
+            elif cat is not None:
+                cat[..., c_off:c_off + widths[i]] = x
+            c_off += widths[i]
+        y = x if cat is None else cat
+        if len(self.deblocks) > levels:
+            conv, bn = self.deblocks[-1][0], self.deblocks[-1][1]
+            s = conv.stride[0]
+            y = ops.deconv_into(y, self._deconv_plan("d%d" % levels, conv, bn),
+                                torch.empty((n, s * y.shape[1], s * y.shape[2], conv.out_channels), device=y.device, dtype=y.dtype), 0)
+        return y
+
+    def forward(self, data_dict):
+        x = data_dict["spatial_features"]
+        self._require_inference(x)
+        data_dict["spatial_features_2d"] = rt.nchw_view(self.forward_nhwc(rt.to_nhwc(x))).float()
+        return data_dict

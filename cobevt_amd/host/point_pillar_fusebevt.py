@@ -19,7 +19,17 @@ graph of host/training.point_pillar_fusebevt (batch statistics over the pillars 
 Optional args['anchor_number'] = A adds the detection head OpenCOOD's PointPillar models carry: cls_head (64 -> A, 1 x 1, bias) and
 reg_head (64 -> 7A), and the forward adds 'psm' (B, A, ny, nx) and 'rm' (B, 7A, ny, nx) in fp32 - both from ONE dense product of the
 concatenated weights over the fused rows (ops.linear) - for host.VoxelPostprocessor.post_process.  Inference only: the reference has
-no detection loss, so train() with the argument set raises.  Without the argument the state_dict and the outputs are unchanged."""
+no detection loss, so train() with the argument set raises.  Without the argument the state_dict and the outputs are unchanged.
+
+Optional args['base_bev_backbone'] = model_cfg (BaseBEVBackbone's: layer_nums, layer_strides, num_filters, upsample_strides,
+num_upsample_filter) puts OpenCOOD's 2-D backbone, parameters under backbone.*, on the fused (B, ny, nx, 64) map, between FuseBEVT and
+the heads.  The reference ships no model that wires this class behind FuseBEVT, so the position is this package's choice, for two
+reasons: FuseBEVT's kernels are built for 64 / 128 channels (not the backbone's 384), and after fusion the backbone runs on B maps
+instead of B * max_cav.  With it cls_head / reg_head take backbone.num_bev_features inputs, psm / rm come out at the backbone's
+resolution (the standard layer_strides [2, 2, 2] / upsample_strides [1, 2, 4] give ny / 2 x nx / 2, what VoxelPostprocessor's default
+feature_stride = 2 expects), the output gains 'spatial_features_2d' (B, num_bev_features, H', W') fp32 and 'fused_feature' is
+unchanged.  Inference only (the transposed convolution has no backward here): train() with the argument set raises.  Without the
+argument the state_dict, the outputs and the launch sequence are unchanged."""
 import torch
 import torch.nn as nn
 
@@ -27,6 +37,7 @@ from .. import ops
 from ..lib import CobevtHipError
 from . import runtime as rt
 from . import training
+from .base_bev_backbone import BaseBEVBackbone
 from .pillar_vfe import PillarVFE
 from .point_pillar_scatter import PointPillarScatter
 from .runtime import HipModule
@@ -54,6 +65,10 @@ class PointPillarFuseBEVT(HipModule):
                                  "PFN layer's %d channels" % c)
         if self.max_cav < 1:
             raise CobevtHipError("PointPillarFuseBEVT: max_cav must be at least 1")
+        self.backbone = None
+        if args.get("base_bev_backbone") is not None:
+            self.backbone = BaseBEVBackbone(args["base_bev_backbone"], c)
+            c = self.backbone.num_bev_features
         self.anchor_number = args.get("anchor_number")
         if self.anchor_number is not None:
             if int(self.anchor_number) < 1:
@@ -97,7 +112,7 @@ class PointPillarFuseBEVT(HipModule):
                                       with_distance=self.pillar_vfe.with_distance, record_len=rl, max_cav=self.max_cav, out=out)
 
     def _head_plan(self):
-        """cls_head and reg_head as one (8A, 64) dense layer"""
+        """cls_head and reg_head as one (8A, C) dense layer"""
         tensors = [self.cls_head.weight, self.cls_head.bias, self.reg_head.weight, self.reg_head.bias]
 
         def build(dt, dev):
@@ -109,6 +124,9 @@ class PointPillarFuseBEVT(HipModule):
         if self.training and self.anchor_number is not None:
             raise CobevtHipError("PointPillarFuseBEVT: the detection head (args['anchor_number']) is inference only - the reference has no "
                                  "detection loss to train it with; call .eval(), or build the model without anchor_number to train")
+        if self.training and self.backbone is not None:
+            raise CobevtHipError("PointPillarFuseBEVT: the 2-D backbone (args['base_bev_backbone']) is inference only - its transposed "
+                                 "convolutions have no backward; call .eval(), or build the model without base_bev_backbone to train")
         batch_dict = self.with_voxels(batch_dict)
         if self.training and training.lidar_trains(self.pillar_vfe.pfn_layers[0], batch_dict["processed_lidar"]["voxel_features"]):
             return training.point_pillar_fusebevt(self, batch_dict)
@@ -119,9 +137,13 @@ class PointPillarFuseBEVT(HipModule):
         com_mask = cav_mask[:, None, None, None, :].expand(b, h, w, 1, l).contiguous()
         fused = self.fusion_net.forward_blhwc(x, com_mask)                      # (B, ny, nx, 64)
         out = {"fused_feature": rt.nchw_view(fused).float()}
+        feat = fused
+        if self.backbone is not None:
+            feat = self.backbone.forward_nhwc(fused)                            # (B, H', W', num_bev_features)
+            out["spatial_features_2d"] = rt.nchw_view(feat).float()
         if self.anchor_number is not None:
             a = self.anchor_number
-            maps = rt.nchw_view(ops.linear(fused, self._head_plan())).float()   # (B, 8A, ny, nx): A class maps, then 7A deltas
+            maps = rt.nchw_view(ops.linear(feat, self._head_plan())).float()    # (B, 8A, H', W'): A class maps, then 7A deltas
             out["psm"] = maps[:, :a].contiguous()
             out["rm"] = maps[:, a:].contiguous()
         return out

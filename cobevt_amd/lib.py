@@ -24,6 +24,7 @@ SIGNATURES = {
     "cobevt_abi_version": (ctypes.c_int, []),
     "cobevt_strerror": (ctypes.c_char_p, [ctypes.c_int]),
     "cobevt_conv2d_nhwc": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_int_p, _vp]),
+    "cobevt_deconv_nhwc": (ctypes.c_int, [_vp, _vp, _vp, _vp, _c_int_p, _vp]),
     "cobevt_conv3x3_nhwc": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _c_int_p, _vp]),
     "cobevt_basicblock_nhwc": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _c_int_p, _vp]),
     "cobevt_dsblock_nhwc": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_int_p, _vp]),

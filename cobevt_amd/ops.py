@@ -516,6 +516,75 @@ def conv2d(x, plan, residual=None, out=None):
     return out
 
 
+DECONV_MAX_STRIDE = 8
+
+
+class DeconvPlan(object):
+    """nn.ConvTranspose2d(Cin, Cout, s, stride=s, bias=False) (+ the eval BatchNorm that follows it) lowered to cobevt_deconv_nhwc:
+    `wgt` [s*s*Cout][Kpad] with row (dy*s + dx)*Cout + co = weight[:, co, dy, dx] * bn_scale[co] (folded in float64, then rounded to the
+    compute dtype; columns >= Cin zero) and `shift` fp32[Cout].  weight: (Cin, Cout, s, s), the ConvTranspose2d layout.  device="cpu"
+    builds the same tensors without a GPU (the layout tests)."""
+
+    def __init__(self, weight, bn=None, stride=1, dtype=torch.bfloat16, device="cuda", act=1):
+        if weight.dim() != 4 or weight.shape[2] != weight.shape[3]:
+            raise CobevtHipError("DeconvPlan: weight must be (Cin, Cout, s, s), got %s" % (tuple(weight.shape),))
+        cin, cout, s, _ = (int(d) for d in weight.shape)
+        if int(stride) != stride or int(stride) != s:
+            raise CobevtHipError("DeconvPlan: only kernel = stride (no overlapping taps) is supported: a %d x %d kernel with stride %r" % (s, s, stride))
+        if not 1 <= s <= DECONV_MAX_STRIDE:
+            raise CobevtHipError("DeconvPlan: stride %d is outside 1 .. %d" % (s, DECONV_MAX_STRIDE))
+        self.dtype, self.code = dtype, dcode(dtype)
+        bke, ch = (32, 8) if self.code == BF16 else (16, 4)
+        if cin % ch != 0:
+            raise CobevtHipError("DeconvPlan: Cin=%d must be a multiple of %d for the %s kernel" % (cin, ch, dtype))
+        if cout % 32 != 0:
+            raise CobevtHipError("DeconvPlan: Cout=%d must be a multiple of 32 (one MFMA tile = 32 channels of one tap)" % cout)
+        w = weight.detach().double().cpu()
+        shift = torch.zeros(cout, dtype=torch.float64)
+        if bn is not None:
+            sc, shift = (t.cpu() for t in bn_affine(bn))
+            w = w * sc[None, :, None, None]
+        kpad = (cin + bke - 1) // bke * bke
+        wk = torch.zeros(s * s * cout, kpad, dtype=torch.float64)
+        wk[:, :cin] = w.permute(2, 3, 1, 0).reshape(s * s * cout, cin)
+        self.wgt = wk.to(torch.float32).to(dtype).to(device).contiguous()
+        self.shift = shift.to(torch.float32).to(device).contiguous()
+        self.cin, self.cout, self.stride, self.kpad, self.act = cin, cout, s, kpad, int(act)
+
+
+def deconv_into(x, plan, out, c_off=0):
+    """x (N,H,W,Cin) contiguous in plan.dtype -> out[:, :, :, c_off : c_off + Cout] of the contiguous (N, s*H, s*W, ldc) map `out` (same
+    dtype), pixel-shuffled, with the plan's shift and activation: one cobevt_deconv_nhwc launch that writes exactly that slice.
+    Returns `out`."""
+    p, s = plan, plan.stride
+    if x.dim() != 4 or x.shape[3] != p.cin or not x.is_contiguous():
+        raise CobevtHipError("deconv_into: bad input %s (contiguous=%s) for Cin=%d" % (tuple(x.shape), x.is_contiguous(), p.cin))
+    if x.dtype != p.dtype or out.dtype != p.dtype:
+        raise CobevtHipError("deconv_into: input %s / out %s do not match the plan's %s" % (x.dtype, out.dtype, p.dtype))
+    n, h, w, _ = x.shape
+    if out.dim() != 4 or tuple(out.shape[:3]) != (n, s * h, s * w) or not out.is_contiguous():
+        raise CobevtHipError("deconv_into: `out` must be contiguous (%d, %d, %d, ldc) for a stride-%d deconv of %s, got %s"
+                             % (n, s * h, s * w, s, tuple(x.shape), tuple(out.shape)))
+    ldc, c_off = int(out.shape[3]), int(c_off)
+    if c_off < 0 or c_off % 8 != 0 or ldc % 8 != 0:
+        raise CobevtHipError("deconv_into: c_off=%d and the destination's %d channels must be multiples of 8 (16-byte stores)" % (c_off, ldc))
+    if c_off + p.cout > ldc:
+        raise CobevtHipError("deconv_into: channels [%d, %d) do not fit the destination's %d" % (c_off, c_off + p.cout, ldc))
+    if n * h * w * s * s >= 2 ** 31:
+        raise CobevtHipError("deconv_into: %d destination pixels overflow the kernel's 32-bit pixel index" % (n * h * w * s * s))
+    _need_cuda(x, out)
+
+    def cost():
+        esz = 2 if p.code == BF16 else 4
+        m = n * h * w
+        return 2.0 * m * s * s * p.cout * p.cin, float(esz * (m * p.cin + s * s * p.cout * p.cin + m * s * s * p.cout))
+
+    dims = _ints([p.code, n, h, w, p.cin, p.cout, p.kpad, s, c_off, ldc, p.act])
+    with _timed("deconv|s%d %d->%d M=%d" % (s, p.cin, p.cout, n * h * w), cost):
+        _L.call("cobevt_deconv_nhwc", _p(x), _p(p.wgt), _p(p.shift), _p(out), dims, _stream())
+    return out
+
+
 def basicblock_fusable(x, plan1, plan2):
     """stride-1 BasicBlock without downsample on 64 / 128 channels: both 3x3 convs in one launch (basicblock.hip)"""
     return (USE_BASICBLOCK and plan1.wfrag is not None and plan2.wfrag is not None and plan1.cin == plan1.cout == plan2.cin

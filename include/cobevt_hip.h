@@ -60,6 +60,21 @@ int cobevt_conv2d_nhwc(const void* in, const void* wgt, const float* bias, const
                        const int* dims, hipStream_t stream);
 
 /*
+ * Transposed convolution with kernel = stride = s (no overlapping taps) + folded eval BatchNorm + activation, written pixel-shuffled
+ * into a channel slice of a wider NHWC map.  Replaces: the deblocks nn.ConvTranspose2d(Cin, Cout, s, stride=s, bias=False) ->
+ * BatchNorm2d -> ReLU of opv2v/opencood/models/backbones/base_bev_backbone.py:58-69,85-90 and the torch.cat of their outputs (:113):
+ *   out[n, s*y + dy, s*x + dx, c_off + co] = act(shift[co] + sum_ci in[n, y, x, ci] * wgt[(dy*s + dx)*Cout + co][ci])
+ * in (N,H,W,Cin) NHWC and out (N, s*H, s*W, ldc) NHWC in the compute dtype; wgt [s*s*Cout][Kpad] in the compute dtype, tap-major rows
+ * with the BatchNorm scale folded in, columns >= Cin zero; shift fp32[Cout].  One GEMM (M = N*H*W, K = Cin, s*s*Cout columns) on
+ * the matrix path of the library it is linked into; every element of out[..., c_off : c_off + Cout] is written exactly once with
+ * 16-byte stores, nothing else of `out` is touched (no atomics, no zero-fill needed).  s = 1 is a 1x1 convolution into a slice.
+ * dims (int32[11]): dtype (0 bf16, 1 fp32), N, H, W, Cin, Cout, Kpad, s, c_off, ldc, act (0 none, 1 ReLU, 2 GELU, 3 swish, 4 sigmoid).
+ * COBEVT_ERR_SHAPE unless 1 <= s <= 8, Cin % 8 == 0 (bf16) / % 4 == 0 (fp32), Cout % 32 == 0, Kpad >= Cin and Kpad % 32 == 0 (bf16) /
+ * % 16 == 0 (fp32), c_off % 8 == 0, ldc % 8 == 0, c_off + Cout <= ldc, and N*H*W*s*s < 2^31.
+ */
+int cobevt_deconv_nhwc(const void* in, const void* wgt, const float* shift, void* out, const int* dims, hipStream_t stream);
+
+/*
  * 3x3 / stride 1 / pad 1 convolution with an LDS-resident input patch (the fast path of cobevt_conv2d_nhwc for the
  * ResNet BasicBlocks resnet_ms.py:67-74, FAX Bottleneck / downsample convs fax_modules.py:472-489 and NaiveDecoder
  * naive_decoder.py:78-87).  Weights [Cout][Cin/cc][9][cc].  dims (int32[10]): dtype, N, H, W, Cin, Cout,
