@@ -25,6 +25,10 @@ from .point_pillar_scatter import PointPillarScatter  # noqa: F401
 from .sp_voxel_preprocessor import SpVoxelPreprocessor  # noqa: F401
 from .base_bev_backbone import BaseBEVBackbone  # noqa: F401
 from .point_pillar_fusebevt import PointPillarFuseBEVT  # noqa: F401
+from .self_attn import AttFusion  # noqa: F401
+from .auto_encoder import AutoEncoder  # noqa: F401
+from .att_bev_backbone import AttBEVBackbone  # noqa: F401
+from .point_pillar_intermediate import PointPillarIntermediate  # noqa: F401
 from .pipeline import CapturedCall, CapturedCorpBEVT, HostFrameFeeder, PipelinedCorpBEVT  # noqa: F401
 # the data formats either side of the path
 from .camera_bev_postprocessor import CameraBevPostprocessor  # noqa: F401

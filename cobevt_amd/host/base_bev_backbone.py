@@ -39,15 +39,15 @@ class BaseBEVBackbone(HipModule):
         layer_strides = list(model_cfg.get("layer_strides", [])) if layer_nums else []
         num_filters = list(model_cfg.get("num_filters", [])) if layer_nums else []
         if not len(layer_nums) == len(layer_strides) == len(num_filters):
-            raise CobevtHipError("BaseBEVBackbone: layer_nums, layer_strides and num_filters must have one entry per level")
+            raise CobevtHipError("%s: layer_nums, layer_strides and num_filters must have one entry per level" % type(self).__name__)
         up_strides = list(model_cfg.get("upsample_strides", []))
         up_filters = list(model_cfg.get("num_upsample_filter", [])) if up_strides else []
         if len(up_strides) != len(up_filters):
-            raise CobevtHipError("BaseBEVBackbone: upsample_strides and num_upsample_filter must have the same length")
+            raise CobevtHipError("%s: upsample_strides and num_upsample_filter must have the same length" % type(self).__name__)
         levels = len(layer_nums)
         if up_strides and len(up_strides) not in (levels, levels + 1):
-            raise CobevtHipError("BaseBEVBackbone: %d upsample_strides for %d levels (one per level, or one more for a trailing deblock)"
-                                 % (len(up_strides), levels))
+            raise CobevtHipError("%s: %d upsample_strides for %d levels (one per level, or one more for a trailing deblock)"
+                                 % (type(self).__name__, len(up_strides), levels))
         self.layer_strides, self.upsample_strides = [int(s) for s in layer_strides], up_strides
         c_in = [input_channels] + num_filters[:-1]
         self.blocks, self.deblocks = nn.ModuleList(), nn.ModuleList()
@@ -73,22 +73,22 @@ class BaseBEVBackbone(HipModule):
         total = sum(up_filters)
         if len(up_strides) > levels:
             if total != sum(up_filters[:levels]):
-                raise CobevtHipError("BaseBEVBackbone: the trailing deblock is sum(num_upsample_filter) = %d channels wide, the map it reads "
-                                     "%d: num_upsample_filter[-1] must be 0" % (total, sum(up_filters[:levels])))
+                raise CobevtHipError("%s: the trailing deblock is sum(num_upsample_filter) = %d channels wide, the map it reads "
+                                     "%d: num_upsample_filter[-1] must be 0" % (type(self).__name__, total, sum(up_filters[:levels])))
             self._check_deblock(levels, up_strides[-1], total, 0)
             self.deblocks.append(nn.Sequential(nn.ConvTranspose2d(total, total, int(up_strides[-1]), stride=int(up_strides[-1]), bias=False),
                                                _bn(total), nn.ReLU()))
         # (without deblocks the reference reports sum([]) = 0; here it is the width of the map the forward returns)
         self.num_bev_features = total if up_strides else sum(num_filters)
 
-    @staticmethod
-    def _check_deblock(i, u, c, c_off):
+    @classmethod
+    def _check_deblock(cls, i, u, c, c_off):
         if int(u) != u or not 1 <= int(u) <= ops.DECONV_MAX_STRIDE:
-            raise CobevtHipError("BaseBEVBackbone: upsample_strides[%d] = %r: the transposed-conv kernel takes integer strides 1 .. %d"
-                                 % (i, u, ops.DECONV_MAX_STRIDE))
+            raise CobevtHipError("%s: upsample_strides[%d] = %r: the transposed-conv kernel takes integer strides 1 .. %d"
+                                 % (cls.__name__, i, u, ops.DECONV_MAX_STRIDE))
         if c % 32 != 0 or c_off % 8 != 0:
-            raise CobevtHipError("BaseBEVBackbone: deblock %d writes %d channels at channel %d of the concatenated map; the transposed-conv "
-                                 "kernel needs a multiple of 32 channels at a multiple of 8" % (i, c, c_off))
+            raise CobevtHipError("%s: deblock %d writes %d channels at channel %d of the concatenated map; the transposed-conv "
+                                 "kernel needs a multiple of 32 channels at a multiple of 8" % (cls.__name__, i, c, c_off))
 
     # ---- plans
     def _conv_plan(self, name, conv, bn, pad):
@@ -123,39 +123,47 @@ class BaseBEVBackbone(HipModule):
 
     def forward_nhwc(self, x):
         """(N, H, W, C) in the compute dtype -> (N, H', W', num_bev_features) in the compute dtype"""
+        return self._forward_levels(x, x.shape[0])
+
+    def _forward_levels(self, x, n_out, after_block=None):
+        """the levels' loop.  after_block(i, x) -> (the map the next level reads, the n_out maps the level's deblock reads) is the
+        subclasses' hook between a block and its deblock (AttBEVBackbone: compression, agent fusion); without it both are x"""
         self._require_inference(x)
-        n, h, w, _ = x.shape
+        _, h, w, _ = x.shape
         levels = len(self.blocks)
         if levels == 0:
             return x
         ups = self._up_sizes(self._level_sizes(h, w))
         if any(hw != ups[0] for hw in ups) or min(ups[0]) < 1:
-            raise CobevtHipError("BaseBEVBackbone: the levels' outputs must share one H x W to be concatenated; a %d x %d input gives %s"
-                                 % (h, w, ", ".join("%d x %d" % hw for hw in ups)))
+            raise CobevtHipError("%s: the levels' outputs must share one H x W to be concatenated; a %d x %d input gives %s"
+                                 % (type(self).__name__, h, w, ", ".join("%d x %d" % hw for hw in ups)))
         widths = [(self.deblocks[i][0] if len(self.deblocks) else self.blocks[i][1]).out_channels for i in range(levels)]
         cat = None
         if levels > 1 or len(self.deblocks):
-            cat = torch.empty((n, ups[0][0], ups[0][1], sum(widths)), device=x.device, dtype=x.dtype)
+            cat = torch.empty((n_out, ups[0][0], ups[0][1], sum(widths)), device=x.device, dtype=x.dtype)
         c_off = 0
         for i, block in enumerate(self.blocks):
             x = ops.conv2d(x, self._conv_plan("b%d.0" % i, block[1], block[2], 1))
             for k in range(4, len(block), 3):
                 x = ops.conv2d(x, self._conv_plan("b%d.%d" % (i, k), block[k], block[k + 1], 1))
+            y = x
+            if after_block is not None:
+                x, y = after_block(i, x)
             if len(self.deblocks):
                 conv, bn = self.deblocks[i][0], self.deblocks[i][1]
                 if isinstance(conv, nn.ConvTranspose2d):
-                    ops.deconv_into(x, self._deconv_plan("d%d" % i, conv, bn), cat, c_off)
+                    ops.deconv_into(y, self._deconv_plan("d%d" % i, conv, bn), cat, c_off)
                 else:
-                    cat[..., c_off:c_off + widths[i]] = ops.conv2d(x, self._conv_plan("d%d" % i, conv, bn, 0))
+                    cat[..., c_off:c_off + widths[i]] = ops.conv2d(y, self._conv_plan("d%d" % i, conv, bn, 0))
             elif cat is not None:
-                cat[..., c_off:c_off + widths[i]] = x
+                cat[..., c_off:c_off + widths[i]] = y
             c_off += widths[i]
-        y = x if cat is None else cat
+        y = y if cat is None else cat
         if len(self.deblocks) > levels:
             conv, bn = self.deblocks[-1][0], self.deblocks[-1][1]
             s = conv.stride[0]
             y = ops.deconv_into(y, self._deconv_plan("d%d" % levels, conv, bn),
-                                torch.empty((n, s * y.shape[1], s * y.shape[2], conv.out_channels), device=y.device, dtype=y.dtype), 0)
+                                torch.empty((n_out, s * y.shape[1], s * y.shape[2], conv.out_channels), device=y.device, dtype=y.dtype), 0)
         return y
 
     def forward(self, data_dict):

@@ -1563,6 +1563,43 @@ def agent_softmax_sum(score, nb, roi, record_len, n_agents, use_mask=True):
     return out
 
 
+def att_fuse_group_ok(c):
+    """csrc/pairwise_fusion.hip's group_ok: 8 channels per lane, a power-of-two group of at most 64 lanes per pixel"""
+    g = c >> 3
+    return c % 8 == 0 and 1 <= g <= 64 and (g & (g - 1)) == 0
+
+
+def att_fuse(x, record_len, out=None):
+    """AttFusion (fusion_modules/self_attn.py:36-57) in one cobevt_att_fuse_nhwc launch: x (N, H, W, C) contiguous un-grouped agent maps
+    in the compute dtype, record_len (B,) int32 on the device -> (B, H, W, C): per pixel the ego's row of the scaled-dot-product
+    attention over its sample's agents.  record_len is read on the device (no host synchronisation); a sample whose record_len is
+    <= 0 gets zeros.  out=: a contiguous (B, H, W, C) tensor of x's dtype to write into."""
+    if x.dim() != 4 or not x.is_contiguous() or min(x.shape) < 1:
+        raise CobevtHipError("att_fuse: x must be a contiguous non-empty (N, H, W, C) tensor, got %s (contiguous=%s)"
+                             % (tuple(x.shape), x.is_contiguous()))
+    code = dcode(x.dtype)
+    n, h, w, c = (int(d) for d in x.shape)
+    if not att_fuse_group_ok(c):
+        raise CobevtHipError("att_fuse: C=%d must be 8 times a power of two, at most 512 (8 channels per lane, one group of lanes per pixel)" % c)
+    if record_len.dtype != torch.int32 or record_len.dim() != 1 or not record_len.is_contiguous() or record_len.shape[0] < 1:
+        raise CobevtHipError("att_fuse: record_len must be a contiguous int32 (B,) tensor with B >= 1, got %s %s"
+                             % (record_len.dtype, tuple(record_len.shape)))
+    b = int(record_len.shape[0])
+    if b > 65535:
+        raise CobevtHipError("att_fuse: %d samples exceed the grid's 65535" % b)
+    if out is None:
+        out = torch.empty((b, h, w, c), device=x.device, dtype=x.dtype)
+    elif tuple(out.shape) != (b, h, w, c) or out.dtype != x.dtype or not out.is_contiguous():
+        raise CobevtHipError("att_fuse: out= must be a contiguous %s tensor of shape %s, got %s %s"
+                             % (x.dtype, (b, h, w, c), out.dtype, tuple(out.shape)))
+    _need_cuda(x, record_len, out)
+    esz = 2 if code == BF16 else 4
+    cost = lambda: (2.0 * 2 * n * h * w * c, float(esz * (n + b) * h * w * c))         # noqa: E731
+    with _timed("att_fuse|N%d B%d HW=%d C=%d" % (n, b, h * w, c), cost):
+        _L.call("cobevt_att_fuse_nhwc", _p(x), _p(record_len), _p(out), code, b, n, h * w, c, ctypes.c_float(1.0 / math.sqrt(c)), _stream())
+    return out
+
+
 def invert_small(m):
     """Batched inverse of (..., 3, 3) or (..., 4, 4) fp32 matrices on the device."""
     _need_cuda(m)

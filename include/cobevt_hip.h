@@ -387,6 +387,16 @@ int cobevt_gru_zero_state(const void* in, void* out, int dtype, long rows, int C
 int cobevt_agent_softmax_sum(const void* score, int lds, const void* nb, const float* roi, const int* record_len, void* out, int dtype,
                              int B, int L, int HW, int C, int use_mask, hipStream_t stream);
 
+/* AttFusion (fusion_modules/self_attn.py:36-57) on channels-last maps, one launch: x (N, HW, C) and out (B, HW, C) contiguous in the
+ * compute dtype (0 bf16, 1 fp32), N = sum(record_len).  For sample b with agents off .. off + n - 1 (off = sum record_len[:b]) and
+ * every pixel p:  s_j = <x[off, p], x[off + j, p]> * scale;  out[b, p] = sum_j softmax_j(s) x[off + j, p]  - the ego's row of the
+ * reference's n x n attention, the only one it keeps.  scale = 1 / sqrt(C), passed by the host.  fp32 arithmetic, online softmax
+ * with a running maximum, one rounding to the storage type.  record_len (device int32[B]) is read on the device; n is clamped to
+ * [0, N - off], so a wrong record_len reads nothing outside x, and a sample with n <= 0 gets zeros.  Every element of out is
+ * written once.  COBEVT_ERR_SHAPE unless C = 8 * 2^k <= 512, 1 <= B <= 65535, N >= 1, HW >= 1. */
+int cobevt_att_fuse_nhwc(const void* x, const int* record_len, void* out, int dtype, int B, int N, long HW, int C, float scale,
+                         hipStream_t stream);
+
 /* regroup: split by record_len (device int32[B]), zero pad to max_cav, agent mask (B,max_cav) fp32.
  * Replaces fuse_utils.py:8-61 without its host synchronisation (:26). */
 int cobevt_regroup(const void* in, const int* record_len, void* out, float* mask, int dtype, int B, int max_cav,
