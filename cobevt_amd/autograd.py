@@ -886,8 +886,8 @@ def _nhwc(x):
 
 class BatchNormActFn(torch.autograd.Function):
     """act(BatchNorm2d(x) [+ residual]) with nn.BatchNorm2d semantics: batch statistics and the in-place running-stat update when
-    `training`, the frozen running statistics otherwise; act 1 = ReLU.  Forward: cobevt_channel_sums -> cobevt_bn_finalize ->
-    cobevt_bn_apply; backward: cobevt_bn_backward (per-channel reductions in fp64, then dx / d(residual)) - what torch's batch_norm
+    `training`, the frozen running statistics otherwise; act 1 = ReLU.  Forward: cobevt_bn_batch_stats (or cobevt_bn_finalize on the
+    frozen statistics) -> cobevt_bn_apply; backward: cobevt_bn_backward (per-channel reductions in fp64, then dx / d(residual)) - what torch's batch_norm
     + add + relu do under train_camera.py:143-179 for torchvision's BasicBlock / Bottleneck and the NaiveDecoder."""
 
     @staticmethod
@@ -906,8 +906,8 @@ class BatchNormActFn(torch.autograd.Function):
         track = bn.track_running_stats and bn.running_mean is not None
         momentum = 0.1 if bn.momentum is None else bn.momentum
         if training:
-            # batch statistics: sums of x - running_mean (when there is one: no cancellation in the variance, fp32 partial sums suffice)
-            # per workgroup, then one launch that reduces them and finishes every channel incl. the running-stat update
+            # batch statistics: sums of x - (row 0 of x) (a pivot inside the data: no cancellation in the variance, fp32 partial sums
+            # suffice) per workgroup, then one launch that reduces them and finishes every channel incl. the running-stat update
             _call("cobevt_bn_batch_stats", _p(xl), _p(g), _p(b), _p(bn.running_mean) if track else None,
                   _p(bn.running_var) if track else None, _p(scale), _p(shift), _p(mean), _p(rstd), _p(_scratch(c, dev)), _SCRATCH_BLOCKS,
                   dt, rows, c, ctypes.c_float(bn.eps), ctypes.c_float(momentum),

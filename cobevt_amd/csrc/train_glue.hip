@@ -6,9 +6,10 @@
 //   MaxPool2d(3, 2, 1) of the ResNet stem (resnet_ms.py:70) backward; nn.PixelUnshuffle(2) (fax_modules.py:479) and nearest x2
 //     up-sampling (naive_decoder.py:84) in both directions; the STTF bilinear warp's input gradient (corpbevt.py:28-64,
 //     torch_transformation_utils.py:317-355); bias gradients (column sums).
-// All of it is HBM-bound streaming work: one 16-byte piece (8 channels) per lane, per-channel reductions in fp64 partial sums
-// per workgroup + one fp64 atomic per (workgroup, channel) (E[x^2] - E[x]^2 in fp32 loses the variance of activations whose
-// mean dominates; torch's batch_norm uses Welford), scatter-type gradients as fp32 atomics on the input-gradient map.
+// All of it is HBM-bound streaming work: one 16-byte piece (8 channels) per lane, per-channel reductions as fp32 sums per thread about
+// a pivot inside the data, fp64 partial sums per workgroup and a wave per channel that combines them (E[x^2] - E[x]^2 in fp32 loses
+// the variance of activations whose mean dominates; torch's batch_norm uses Welford), scatter-type gradients as fp32 atomics on the
+// input-gradient map.
 #include "warp_common.hpp"
 
 namespace cobevt {
@@ -18,21 +19,28 @@ constexpr int kThreads = 256;
 
 // ---- per-channel sums over rows: sum[c] += x, sumsq[c] += x^2 (BatchNorm statistics; column sum for bias gradients) ----
 // grid.x = row blocks; a thread owns one 8-channel group (gl) and walks rows gid, gid + stride, ...
-template <typename T, bool SQ>
-__global__ __launch_bounds__(kThreads) void channel_sums_kernel(const T* __restrict__ x, const float* __restrict__ shift,
+// Acc: the type of a thread's partial sums.  float for the streaming maps; double where the launch gives a thread more rows than
+// ceil(rows / scratch_blocks) (row_blocks(): maps too small to use every scratch slot at 8 rows a thread - launch-bound, the fp64
+// arithmetic is free there), so that a partial's rounding error stays within that many terms' whatever the map size.
+template <typename T, bool SQ, typename Acc>
+__global__ __launch_bounds__(kThreads) void channel_sums_kernel(const T* __restrict__ x, const float* __restrict__ shift, int pivot_row0,
                                                                 double* __restrict__ partial, long rows, int C, int rows_per_block) {
     // partial: [gridDim.x][2][C] fp64 - this workgroup's sums; combined by reduce_partials_kernel.  (Atomics on the C result
     // words serialise: with 1024 workgroups a launch took ~50 us whatever the map size.)
-    // sums of (x - shift[c]) and (x - shift[c])^2 (shift nullable = 0): with the shift near the mean (BatchNorm passes its running
-    // mean) the variance no longer comes out of a cancellation, so a thread accumulates its <= ~64 rows in fp32 (v_pk_add rate
-    // instead of fp64 conversions per element); threads and workgroups are combined in fp64
+    // sums of (x - shift[c]) and (x - shift[c])^2 (shift nullable = 0; pivot_row0: shift = row 0 of x itself, as stored): with the
+    // shift inside the data the variance no longer comes out of a cancellation, so a thread accumulates its <= ~64 rows in fp32
+    // (v_pk_add rate instead of fp64 conversions per element); threads and workgroups are combined in fp64.  BatchNorm takes
+    // row 0: a running mean is only near the batch while it is neither fresh (0) nor stale, and an untracked layer has none - 100
+    // standard deviations off, the fp32 sums lost the variance to 1e-4 relative ("BatchNorm statistics")
     const int G = C >> 3;
     const int gl = threadIdx.x % G, r0 = threadIdx.x / G, rstep = kThreads / G;      // threads with r0 >= rstep idle (256 % G != 0)
     const long row_lo = (long)blockIdx.x * rows_per_block;
     const long row_hi = row_lo + rows_per_block < rows ? row_lo + rows_per_block : rows;
-    float s[8], q[8], sh[8];
+    Acc s[8], q[8];
+    float sh[8];
 #pragma unroll
-    for (int e = 0; e < 8; ++e) { s[e] = 0.f; q[e] = 0.f; sh[e] = shift ? shift[gl * 8 + e] : 0.f; }
+    for (int e = 0; e < 8; ++e) { s[e] = 0; q[e] = 0; sh[e] = shift ? shift[gl * 8 + e] : 0.f; }
+    if (pivot_row0) load8<T>(x + gl * 8, sh);
     if (r0 < rstep) {
         long r = row_lo + r0;
         for (; r + rstep < row_hi; r += 2 * rstep) {          // two rows in flight
@@ -41,7 +49,7 @@ __global__ __launch_bounds__(kThreads) void channel_sums_kernel(const T* __restr
             load8<T>(x + (r + rstep) * C + gl * 8, u);
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
-                const float a = v[e] - sh[e], b = u[e] - sh[e];
+                const Acc a = (Acc)v[e] - (Acc)sh[e], b = (Acc)u[e] - (Acc)sh[e];
                 s[e] += a + b;
                 if (SQ) q[e] += a * a + b * b;
             }
@@ -50,14 +58,14 @@ __global__ __launch_bounds__(kThreads) void channel_sums_kernel(const T* __restr
             float v[8];
             load8<T>(x + r * C + gl * 8, v);
 #pragma unroll
-            for (int e = 0; e < 8; ++e) { const float a = v[e] - sh[e]; s[e] += a; if (SQ) q[e] += a * a; }
+            for (int e = 0; e < 8; ++e) { const Acc a = (Acc)v[e] - (Acc)sh[e]; s[e] += a; if (SQ) q[e] += a * a; }
         }
     }
     __shared__ float red[kThreads][9];
     for (int pass = 0; pass < (SQ ? 2 : 1); ++pass) {
         if (pass) __syncthreads();
 #pragma unroll
-        for (int e = 0; e < 8; ++e) red[threadIdx.x][e] = pass ? q[e] : s[e];
+        for (int e = 0; e < 8; ++e) red[threadIdx.x][e] = (float)(pass ? q[e] : s[e]);
         __syncthreads();
         if (threadIdx.x < G) {
             double t[8];
@@ -91,11 +99,12 @@ __global__ __launch_bounds__(256) void reduce_partials_strided_kernel(const doub
 // ---- BatchNorm finalize: stats (training: from the sums; eval: the running statistics) -> per-channel scale / shift, mean / rstd
 // saved for backward, running statistics updated in place (momentum, unbiased variance) as nn.BatchNorm2d does
 // reduce_partials_strided_kernel + bn_finalize_kernel in one launch (training statistics): a wave per channel sums the workgroups' partial
-// pairs [blk][2][C] and its first lane finishes the channel (statistics of x - running_mean when `shifted`, read before the update)
-__global__ __launch_bounds__(256) void bn_reduce_finalize_kernel(const double* __restrict__ partial, int nblk, const float* gamma, const float* beta,
-                                                                 float* running_mean, float* running_var, float* scale, float* shift, float* mean_out,
-                                                                 float* rstd_out, int C, double rows, float eps, float momentum, int shifted,
-                                                                 long long* batches_tracked) {
+// pairs [blk][2][C] and its first lane finishes the channel (statistics of x - pivot[c], pivot = row 0 of the map in its own type T)
+template <typename T>
+__global__ __launch_bounds__(256) void bn_reduce_finalize_kernel(const double* __restrict__ partial, int nblk, const T* __restrict__ pivot,
+                                                                 const float* gamma, const float* beta, float* running_mean, float* running_var,
+                                                                 float* scale, float* shift, float* mean_out, float* rstd_out, int C, double rows,
+                                                                 float eps, float momentum, long long* batches_tracked) {
     const int c = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (c >= C) return;
     double s = 0.0, q = 0.0;
@@ -109,7 +118,7 @@ __global__ __launch_bounds__(256) void bn_reduce_finalize_kernel(const double* _
     if (c == 0 && batches_tracked) *batches_tracked += 1;
     const double d = s / rows;
     double var = q / rows - d * d;
-    const double mean = d + (shifted ? (double)running_mean[c] : 0.0);
+    const double mean = d + (double)load_elem<T>(pivot, (size_t)c);
     if (var < 0.0) var = 0.0;
     if (running_mean) {
         const double unbiased = rows > 1.0 ? var * rows / (rows - 1.0) : var;
@@ -229,13 +238,16 @@ __global__ __launch_bounds__(kThreads) void bn_bwd_reduce_kernel(const T* __rest
     const int gl = threadIdx.x % G, r0 = threadIdx.x / G, rstep = kThreads / G;
     const long row_lo = (long)blockIdx.x * rows_per_block;
     const long row_hi = row_lo + rows_per_block < rows ? row_lo + rows_per_block : rows;
-    float sg[8], sb[8];                              // per-thread partials in fp32 (<= ~64 rows), combined in fp64
+    // per-thread partials (<= ~64 rows) in fp64, rounded once on the way to the LDS and combined in fp64: a partial is then off by one
+    // rounding whatever the number of its rows.  A term g xhat formed in fp32 is three roundings (x - mean, rstd, g) before any summation,
+    // which at a few rows per thread is all of the error (3 x 2^-24 of sum|terms| on a 4-row map); the kernel stays HBM-bound
+    double sb[8], sg[8];
 #pragma unroll
-    for (int e = 0; e < 8; ++e) { sg[e] = 0.f; sb[e] = 0.f; }
+    for (int e = 0; e < 8; ++e) { sg[e] = 0.0; sb[e] = 0; }
     if (r0 < rstep) {
-        float mu[8], rs[8];
+        double mu[8], rs[8];
 #pragma unroll
-        for (int e = 0; e < 8; ++e) { mu[e] = mean[gl * 8 + e]; rs[e] = rstd[gl * 8 + e]; }
+        for (int e = 0; e < 8; ++e) { mu[e] = (double)mean[gl * 8 + e]; rs[e] = (double)rstd[gl * 8 + e]; }
         for (long r = row_lo + r0; r < row_hi; r += rstep) {
             float xv[8], gv[8], yv[8];
             load8<T>(x + r * C + gl * 8, xv);
@@ -244,8 +256,8 @@ __global__ __launch_bounds__(kThreads) void bn_bwd_reduce_kernel(const T* __rest
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 const float g = (act == 1 && !(yv[e] > 0.f)) ? 0.f : gv[e];
-                sb[e] += g;
-                sg[e] += g * ((xv[e] - mu[e]) * rs[e]);
+                sb[e] += (double)g;
+                sg[e] += (double)g * (((double)xv[e] - mu[e]) * rs[e]);
             }
         }
     }
@@ -253,7 +265,7 @@ __global__ __launch_bounds__(kThreads) void bn_bwd_reduce_kernel(const T* __rest
     for (int pass = 0; pass < 2; ++pass) {
         if (pass) __syncthreads();
 #pragma unroll
-        for (int e = 0; e < 8; ++e) red[threadIdx.x][e] = pass ? sb[e] : sg[e];
+        for (int e = 0; e < 8; ++e) red[threadIdx.x][e] = (float)(pass ? sb[e] : sg[e]);
         __syncthreads();
         if (threadIdx.x < G) {
             double t[8];
@@ -270,72 +282,94 @@ __global__ __launch_bounds__(kThreads) void bn_bwd_reduce_kernel(const T* __rest
 
 // ---- backward, pass 2: dx = gamma rstd (g - (dbeta + xhat dgamma) / rows)   (training)   |   dx = gamma rstd g   (frozen statistics)
 //      dres = g (the gradient of the residual branch), when wanted
+// Evaluated as dx = k g - (B + (x - mean) A) with the per-channel k = gamma rstd, A = k rstd dgamma / rows, B = k dbeta / rows formed in
+// fp64 and rounded once: an element then carries at most four roundings on any of its three terms (x - mean, A, two fmas).  Written
+// out in fp32 as in the headline (xhat, the fp32 dgamma / dbeta, 1 / rows, the product with k) it carried eight, and where the ReLU
+// mask zeroes g - no dominant term left - that showed as errors above 4 x 2^-24 of the terms' magnitudes.
+
+// reduce_partials_strided_kernel for the backward: a wave per channel sums the workgroups' (dgamma, dbeta) pairs [blk][2][C]; its first lane
+// writes the sums and leaves the channel's pass-2 coefficients as four floats in the two fp64 words of workgroup 0's pair that only this
+// wave has read: words c -> (k, A), C + c -> (B, mean).  Pass 2 then loads 32 contiguous bytes per coefficient pair and 8 channels
+// instead of gamma, rstd, mean and the two fp64 sums, and forms nothing per element.
+__global__ __launch_bounds__(256) void bn_bwd_finish_kernel(double* partial, int nblk, const float* __restrict__ gamma, const float* __restrict__ mean,
+                                                            const float* __restrict__ rstd, double* __restrict__ out_d, float* __restrict__ out_f,
+                                                            int C, double inv_rows, int training) {
+    const int c = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (c >= C) return;
+    double s = 0.0, q = 0.0;
+    for (int b = lane; b < nblk; b += 64) {
+        s += partial[((size_t)b * 2) * C + c];
+        q += partial[((size_t)b * 2 + 1) * C + c];
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { s += __shfl_xor(s, o, 64); q += __shfl_xor(q, o, 64); }
+    if (lane) return;
+    out_d[c] = s;
+    out_d[C + c] = q;
+    if (out_f) { out_f[c] = (float)s; out_f[C + c] = (float)q; }
+    const double kd = (double)(gamma ? gamma[c] : 1.f) * (double)rstd[c];
+    const float A = training ? (float)(kd * (double)rstd[c] * s * inv_rows) : 0.f;
+    const float B = training ? (float)(kd * q * inv_rows) : 0.f;
+    // two floats per fp64 word, the first in the low half (stored as doubles: the same type as the loads above, so no reordering)
+    partial[c] = __hiloint2double(__float_as_int(A), __float_as_int((float)kd));
+    partial[C + c] = __hiloint2double(__float_as_int(mean[c]), __float_as_int(B));
+}
+
+// the 8 channels' coefficients of group gl, as bn_bwd_finish_kernel left them
+__device__ __forceinline__ void load_bwd_coef(const float* __restrict__ coef, int C, int gl, float* k, float* A, float* B, float* mu) {
+    float ka[16], bm[16];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        *(float4*)(ka + 4 * i) = *(const float4*)(coef + 16 * gl + 4 * i);
+        *(float4*)(bm + 4 * i) = *(const float4*)(coef + 2 * C + 16 * gl + 4 * i);
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { k[e] = ka[2 * e]; A[e] = ka[2 * e + 1]; B[e] = bm[2 * e]; mu[e] = bm[2 * e + 1]; }
+}
+
 template <typename T>
 __global__ __launch_bounds__(kThreads) void bn_bwd_apply_kernel(const T* __restrict__ x, const T* __restrict__ y, const T* __restrict__ dy,
-                                                                const float* __restrict__ mean, const float* __restrict__ rstd,
-                                                                const float* __restrict__ gamma, const double* __restrict__ dgamma,
-                                                                const double* __restrict__ dbeta, T* __restrict__ dx, T* __restrict__ dres,
-                                                                long items, int C, float inv_rows, int act, int training) {
+                                                                const float* __restrict__ coef, T* __restrict__ dx, T* __restrict__ dres,
+                                                                long items, int C, int act, int training) {
     const long gid = (long)blockIdx.x * kThreads + threadIdx.x;
     if (gid >= items) return;
     const int G = C >> 3;
     const int gl = (int)(gid % G);
-    float xv[8], gv[8], yv[8], o[8];
+    float xv[8], gv[8], yv[8], o[8], k[8], mu[8], A[8], B[8];
     load8<T>(x + gid * 8, xv);
     load8<T>(dy + gid * 8, gv);
     if (act == 1) load8<T>(y + gid * 8, yv);
+    load_bwd_coef(coef, C, gl, k, A, B, mu);
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-        const int c = gl * 8 + e;
         const float g = (act == 1 && !(yv[e] > 0.f)) ? 0.f : gv[e];
         gv[e] = g;
-        const float k = (gamma ? gamma[c] : 1.f) * rstd[c];
-        if (training) {
-            const float xhat = (xv[e] - mean[c]) * rstd[c];
-            o[e] = k * (g - ((float)dbeta[c] + xhat * (float)dgamma[c]) * inv_rows);
-        } else {
-            o[e] = k * g;
-        }
+        o[e] = training ? fmaf(k[e], g, -fmaf(xv[e] - mu[e], A[e], B[e])) : k[e] * g;
     }
     store8<T>(dx + gid * 8, o);
     if (dres) store8<T>(dres + gid * 8, gv);
 }
 
-// bn_bwd_apply_kernel as a walk (see bn_apply_walk_kernel): the 8 channels' k = gamma rstd, mean, rstd, dbeta, dgamma in registers; the
-// arithmetic per element is unchanged.  Two pieces in flight (three or four 16-byte streams each).
+// bn_bwd_apply_kernel as a walk (see bn_apply_walk_kernel): the 8 channels' k, A, B and mean in registers; the arithmetic per element is
+// unchanged.  Two pieces in flight (three or four 16-byte streams each).
 template <typename T>
 __global__ __launch_bounds__(kThreads) void bn_bwd_apply_walk_kernel(const T* __restrict__ x, const T* __restrict__ y, const T* __restrict__ dy,
-                                                                     const float* __restrict__ mean, const float* __restrict__ rstd,
-                                                                     const float* __restrict__ gamma, const double* __restrict__ dgamma,
-                                                                     const double* __restrict__ dbeta, T* __restrict__ dx, T* __restrict__ dres,
-                                                                     long items, int C, float inv_rows, int act, int training) {
+                                                                     const float* __restrict__ coef, T* __restrict__ dx, T* __restrict__ dres,
+                                                                     long items, int C, int act, int training) {
     const int G = C >> 3;
     constexpr long step = kThreads;                  // one contiguous span per workgroup, see bn_apply_walk_kernel
     const long span = ((items + gridDim.x - 1) / gridDim.x + kThreads - 1) / kThreads * kThreads;
     long gid = (long)blockIdx.x * span + threadIdx.x;
     items = items < (long)(blockIdx.x + 1) * span ? items : (long)(blockIdx.x + 1) * span;
     const int gl = (int)(gid % G);
-    float k[8], mu[8], rs[8], db[8], dg[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const int c = gl * 8 + e;
-        rs[e] = rstd[c];
-        mu[e] = mean[c];
-        k[e] = (gamma ? gamma[c] : 1.f) * rs[e];
-        db[e] = training ? (float)dbeta[c] : 0.f;
-        dg[e] = training ? (float)dgamma[c] : 0.f;
-    }
+    float k[8], mu[8], A[8], B[8];
+    load_bwd_coef(coef, C, gl, k, A, B, mu);
     auto finish = [&](const float* xv, float* gv, const float* yv, float* o) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             const float g = (act == 1 && !(yv[e] > 0.f)) ? 0.f : gv[e];
             gv[e] = g;
-            if (training) {
-                const float xhat = (xv[e] - mu[e]) * rs[e];
-                o[e] = k[e] * (g - (db[e] + xhat * dg[e]) * inv_rows);
-            } else {
-                o[e] = k[e] * g;
-            }
+            o[e] = training ? fmaf(k[e], g, -fmaf(xv[e] - mu[e], A[e], B[e])) : k[e] * g;
         }
     };
     for (; gid + step < items; gid += 2 * step) {
@@ -628,13 +662,24 @@ __global__ __launch_bounds__(kThreads) void channel_sums_generic_kernel(const T*
     if (sumsq) atomicAdd(sumsq + c, q);
 }
 
-inline int row_blocks(long rows, int C, int* rows_per_block, int cap = 1024) {
+// workgroups of a row reduction and the rows of each.  *f64: a thread gets more rows than ceil(rows / cap) - the launch then takes the
+// kernels that keep a thread's partial sums in fp64, so that "at most ceil(rows / scratch_blocks) terms' fp32 summation error per
+// partial" holds for every map and can be stated from a call's own arguments
+inline int row_blocks(long rows, int C, int* rows_per_block, int cap, bool* f64) {
     const int rstep = kThreads / (C >> 3);
     long want = (rows + (long)rstep * 8 - 1) / ((long)rstep * 8);            // >= 8 rows per thread
     if (want > cap) want = cap;
     if (want < 1) want = 1;
     *rows_per_block = (int)((rows + want - 1) / want);
+    *f64 = (*rows_per_block + rstep - 1) / rstep > (rows + cap - 1) / cap;
     return (int)((rows + *rows_per_block - 1) / *rows_per_block);
+}
+
+template <typename T, bool SQ>
+inline void launch_channel_sums(bool f64, int blocks, hipStream_t stream, const T* x, const float* shift, int pivot_row0, double* partial, long rows,
+                                int C, int rpb) {
+    if (f64) hipLaunchKernelGGL((channel_sums_kernel<T, SQ, double>), dim3(blocks), dim3(kThreads), 0, stream, x, shift, pivot_row0, partial, rows, C, rpb);
+    else hipLaunchKernelGGL((channel_sums_kernel<T, SQ, float>), dim3(blocks), dim3(kThreads), 0, stream, x, shift, pivot_row0, partial, rows, C, rpb);
 }
 
 // workgroups of a walking kernel: about `per_thread` pieces per thread per round, at most 8 workgroups of 256 per CU
@@ -669,13 +714,14 @@ extern "C" int cobevt_channel_sums(const void* x, const float* shift, double* su
     if (!scratch || scratch_blocks < 1) return COBEVT_ERR_ARG;
     if (sumsq && sumsq != sum + C) return COBEVT_ERR_ARG;                  // the pair is reduced as one 2 C vector
     int rpb;
-    const int blocks = row_blocks(rows, C, &rpb, scratch_blocks);
+    bool f64;
+    const int blocks = row_blocks(rows, C, &rpb, scratch_blocks, &f64);
     if (dtype == 0) {
-        if (sumsq) hipLaunchKernelGGL((channel_sums_kernel<bf16_t, true>), dim3(blocks), dim3(kThreads), 0, stream, (const bf16_t*)x, shift, scratch, rows, C, rpb);
-        else hipLaunchKernelGGL((channel_sums_kernel<bf16_t, false>), dim3(blocks), dim3(kThreads), 0, stream, (const bf16_t*)x, shift, scratch, rows, C, rpb);
+        if (sumsq) launch_channel_sums<bf16_t, true>(f64, blocks, stream, (const bf16_t*)x, shift, 0, scratch, rows, C, rpb);
+        else launch_channel_sums<bf16_t, false>(f64, blocks, stream, (const bf16_t*)x, shift, 0, scratch, rows, C, rpb);
     } else {
-        if (sumsq) hipLaunchKernelGGL((channel_sums_kernel<float, true>), dim3(blocks), dim3(kThreads), 0, stream, (const float*)x, shift, scratch, rows, C, rpb);
-        else hipLaunchKernelGGL((channel_sums_kernel<float, false>), dim3(blocks), dim3(kThreads), 0, stream, (const float*)x, shift, scratch, rows, C, rpb);
+        if (sumsq) launch_channel_sums<float, true>(f64, blocks, stream, (const float*)x, shift, 0, scratch, rows, C, rpb);
+        else launch_channel_sums<float, false>(f64, blocks, stream, (const float*)x, shift, 0, scratch, rows, C, rpb);
     }
     // without sumsq only the first C words of every partial pair were written: reduce them with stride 2 C
     const int n = sumsq ? 2 * C : C;
@@ -705,8 +751,8 @@ extern "C" int cobevt_bn_finalize(const double* sum, const double* sumsq, const 
     return cobevt::launch_status();
 }
 
-// cobevt_channel_sums (with the square sums, shifted by running_mean when it is given) + cobevt_bn_finalize (training = 1) in two launches
-// instead of three; running_mean / running_var nullable together (no tracking: plain batch statistics); 8 | C
+// cobevt_channel_sums (with the square sums, taken about row 0 of x) + cobevt_bn_finalize (training = 1) in two launches instead of
+// three; running_mean / running_var nullable together (no tracking: plain batch statistics); 8 | C
 extern "C" int cobevt_bn_batch_stats(const void* x, const float* gamma, const float* beta, float* running_mean, float* running_var, float* scale,
                                      float* shift, float* mean, float* rstd, double* scratch, int scratch_blocks, int dtype, long rows, int C,
                                      float eps, float momentum, long long* batches_tracked, hipStream_t stream) {
@@ -714,11 +760,17 @@ extern "C" int cobevt_bn_batch_stats(const void* x, const float* gamma, const fl
     if ((running_mean == nullptr) != (running_var == nullptr)) return COBEVT_ERR_ARG;
     if (!groups_ok(C) || rows < 1 || (dtype != 0 && dtype != 1)) return COBEVT_ERR_SHAPE;
     int rpb;
-    const int blocks = row_blocks(rows, C, &rpb, scratch_blocks);
-    if (dtype == 0) hipLaunchKernelGGL((channel_sums_kernel<bf16_t, true>), dim3(blocks), dim3(kThreads), 0, stream, (const bf16_t*)x, running_mean, scratch, rows, C, rpb);
-    else hipLaunchKernelGGL((channel_sums_kernel<float, true>), dim3(blocks), dim3(kThreads), 0, stream, (const float*)x, running_mean, scratch, rows, C, rpb);
-    hipLaunchKernelGGL(bn_reduce_finalize_kernel, dim3((C + 3) / 4), dim3(256), 0, stream, scratch, blocks, gamma, beta, running_mean, running_var, scale,
-                       shift, mean, rstd, C, (double)rows, eps, momentum, running_mean != nullptr, batches_tracked);
+    bool f64;
+    const int blocks = row_blocks(rows, C, &rpb, scratch_blocks, &f64);
+    if (dtype == 0) {
+        launch_channel_sums<bf16_t, true>(f64, blocks, stream, (const bf16_t*)x, nullptr, 1, scratch, rows, C, rpb);
+        hipLaunchKernelGGL(bn_reduce_finalize_kernel<bf16_t>, dim3((C + 3) / 4), dim3(256), 0, stream, scratch, blocks, (const bf16_t*)x, gamma, beta,
+                           running_mean, running_var, scale, shift, mean, rstd, C, (double)rows, eps, momentum, batches_tracked);
+    } else {
+        launch_channel_sums<float, true>(f64, blocks, stream, (const float*)x, nullptr, 1, scratch, rows, C, rpb);
+        hipLaunchKernelGGL(bn_reduce_finalize_kernel<float>, dim3((C + 3) / 4), dim3(256), 0, stream, scratch, blocks, (const float*)x, gamma, beta,
+                           running_mean, running_var, scale, shift, mean, rstd, C, (double)rows, eps, momentum, batches_tracked);
+    }
     return cobevt::launch_status();
 }
 
@@ -747,37 +799,28 @@ extern "C" int cobevt_bn_backward(const void* x, const void* y, const void* dy, 
                                   double* dgamma_dbeta, float* grads_f, double* scratch, int scratch_blocks, void* dx, void* dres,
                                   int dtype, long rows, int C, int act, int training, hipStream_t stream) {
     if (!x || !dy || !mean || !rstd || !dgamma_dbeta || !scratch || !dx || (act == 1 && !y)) return COBEVT_ERR_ARG;
+    if ((uintptr_t)scratch & 15) return COBEVT_ERR_ARG;                    // pass 2 reads its coefficients from it 16 bytes at a time
     if (!groups_ok(C) || rows < 1 || act < 0 || act > 1 || scratch_blocks < 1) return COBEVT_ERR_SHAPE;
     int rpb;
-    const int blocks = row_blocks(rows, C, &rpb, scratch_blocks);
+    bool f64;
+    const int blocks = row_blocks(rows, C, &rpb, scratch_blocks, &f64);
     const long items = rows * (C >> 3);
     const dim3 grid((unsigned)((items + kThreads - 1) / kThreads));
-    const float inv_rows = 1.0f / (float)rows;
-    double* dgamma = dgamma_dbeta;
-    double* dbeta = dgamma_dbeta + C;
+    const double inv_rows = 1.0 / (double)rows;
+    const float* coef = (const float*)scratch;                 // bn_bwd_finish_kernel leaves the pass-2 coefficients in workgroup 0's pair
     const bool walk = kThreads % (C >> 3) == 0 && items >= 4L * kThreads;
     const dim3 wgrid(walk_blocks(items, 2));
-    if (walk && (dtype == 0 || dtype == 1)) {
-        if (dtype == 0) {
-            hipLaunchKernelGGL(bn_bwd_reduce_kernel<bf16_t>, dim3(blocks), dim3(kThreads), 0, stream, (const bf16_t*)x, (const bf16_t*)y, (const bf16_t*)dy, mean, rstd, scratch, rows, C, act, rpb);
-            hipLaunchKernelGGL(reduce_partials_strided_kernel, dim3((2 * C + 3) / 4), dim3(256), 0, stream, scratch, blocks, 2 * C, 2 * C, dgamma_dbeta, grads_f);
-            hipLaunchKernelGGL(bn_bwd_apply_walk_kernel<bf16_t>, wgrid, dim3(kThreads), 0, stream, (const bf16_t*)x, (const bf16_t*)y, (const bf16_t*)dy, mean, rstd, gamma, dgamma, dbeta, (bf16_t*)dx, (bf16_t*)dres, items, C, inv_rows, act, training);
-        } else {
-            hipLaunchKernelGGL(bn_bwd_reduce_kernel<float>, dim3(blocks), dim3(kThreads), 0, stream, (const float*)x, (const float*)y, (const float*)dy, mean, rstd, scratch, rows, C, act, rpb);
-            hipLaunchKernelGGL(reduce_partials_strided_kernel, dim3((2 * C + 3) / 4), dim3(256), 0, stream, scratch, blocks, 2 * C, 2 * C, dgamma_dbeta, grads_f);
-            hipLaunchKernelGGL(bn_bwd_apply_walk_kernel<float>, wgrid, dim3(kThreads), 0, stream, (const float*)x, (const float*)y, (const float*)dy, mean, rstd, gamma, dgamma, dbeta, (float*)dx, (float*)dres, items, C, inv_rows, act, training);
-        }
-        return cobevt::launch_status();
+    if (dtype != 0 && dtype != 1) return COBEVT_ERR_ARG;
+    if (dtype == 0) hipLaunchKernelGGL(bn_bwd_reduce_kernel<bf16_t>, dim3(blocks), dim3(kThreads), 0, stream, (const bf16_t*)x, (const bf16_t*)y, (const bf16_t*)dy, mean, rstd, scratch, rows, C, act, rpb);
+    else hipLaunchKernelGGL(bn_bwd_reduce_kernel<float>, dim3(blocks), dim3(kThreads), 0, stream, (const float*)x, (const float*)y, (const float*)dy, mean, rstd, scratch, rows, C, act, rpb);
+    hipLaunchKernelGGL(bn_bwd_finish_kernel, dim3((C + 3) / 4), dim3(256), 0, stream, scratch, blocks, gamma, mean, rstd, dgamma_dbeta, grads_f, C, inv_rows, training);
+    if (walk) {
+        if (dtype == 0) hipLaunchKernelGGL(bn_bwd_apply_walk_kernel<bf16_t>, wgrid, dim3(kThreads), 0, stream, (const bf16_t*)x, (const bf16_t*)y, (const bf16_t*)dy, coef, (bf16_t*)dx, (bf16_t*)dres, items, C, act, training);
+        else hipLaunchKernelGGL(bn_bwd_apply_walk_kernel<float>, wgrid, dim3(kThreads), 0, stream, (const float*)x, (const float*)y, (const float*)dy, coef, (float*)dx, (float*)dres, items, C, act, training);
+    } else {
+        if (dtype == 0) hipLaunchKernelGGL(bn_bwd_apply_kernel<bf16_t>, grid, dim3(kThreads), 0, stream, (const bf16_t*)x, (const bf16_t*)y, (const bf16_t*)dy, coef, (bf16_t*)dx, (bf16_t*)dres, items, C, act, training);
+        else hipLaunchKernelGGL(bn_bwd_apply_kernel<float>, grid, dim3(kThreads), 0, stream, (const float*)x, (const float*)y, (const float*)dy, coef, (float*)dx, (float*)dres, items, C, act, training);
     }
-    if (dtype == 0) {
-        hipLaunchKernelGGL(bn_bwd_reduce_kernel<bf16_t>, dim3(blocks), dim3(kThreads), 0, stream, (const bf16_t*)x, (const bf16_t*)y, (const bf16_t*)dy, mean, rstd, scratch, rows, C, act, rpb);
-        hipLaunchKernelGGL(reduce_partials_strided_kernel, dim3((2 * C + 3) / 4), dim3(256), 0, stream, scratch, blocks, 2 * C, 2 * C, dgamma_dbeta, grads_f);
-        hipLaunchKernelGGL(bn_bwd_apply_kernel<bf16_t>, grid, dim3(kThreads), 0, stream, (const bf16_t*)x, (const bf16_t*)y, (const bf16_t*)dy, mean, rstd, gamma, dgamma, dbeta, (bf16_t*)dx, (bf16_t*)dres, items, C, inv_rows, act, training);
-    } else if (dtype == 1) {
-        hipLaunchKernelGGL(bn_bwd_reduce_kernel<float>, dim3(blocks), dim3(kThreads), 0, stream, (const float*)x, (const float*)y, (const float*)dy, mean, rstd, scratch, rows, C, act, rpb);
-        hipLaunchKernelGGL(reduce_partials_strided_kernel, dim3((2 * C + 3) / 4), dim3(256), 0, stream, scratch, blocks, 2 * C, 2 * C, dgamma_dbeta, grads_f);
-        hipLaunchKernelGGL(bn_bwd_apply_kernel<float>, grid, dim3(kThreads), 0, stream, (const float*)x, (const float*)y, (const float*)dy, mean, rstd, gamma, dgamma, dbeta, (float*)dx, (float*)dres, items, C, inv_rows, act, training);
-    } else return COBEVT_ERR_ARG;
     return cobevt::launch_status();
 }
 

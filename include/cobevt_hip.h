@@ -596,7 +596,7 @@ int cobevt_swap_fusion_stage(const void* qkv, const void* x, void* out, void* qk
  * C a multiple of 8 (<= 2048) except where noted. --------------------------------------------------------------------------- */
 
 /* sum[c] = sum over rows of (x - shift[c]) and (sumsq nullable; must be sum + C) sumsq[c] = sum of its squares, fp64 (shift nullable
- * = 0; BatchNorm passes its running mean so that the variance is not a cancellation); out_f (nullable): the same values as fp32.
+ * = 0; a shift near the mean keeps the variance from being a cancellation); out_f (nullable): the same values as fp32.
  * scratch: fp64 [scratch_blocks][2][C] for per-workgroup partial sums (no atomics: they serialise on the C result words).
  * BatchNorm batch statistics (torchvision BasicBlock / Bottleneck bn1-3 reached from resnet_ms.py:67-74, fax_modules.py:10,472-489,
  * naive_decoder.py:78-87) and bias gradients (any C: channel counts off the 8-channel piece take a scalar kernel, without shift /
@@ -611,8 +611,9 @@ int cobevt_f64_to_f32(const double* in, float* out, int n, hipStream_t stream);
 int cobevt_bn_finalize(const double* sum, const double* sumsq, const float* gamma, const float* beta, float* running_mean,
                        float* running_var, float* scale, float* shift, float* mean, float* rstd, int C, long rows, float eps,
                        float momentum, int training, int shifted, long long* batches_tracked, hipStream_t stream);
-/* cobevt_channel_sums (x and x^2, shifted by running_mean when given) + cobevt_bn_finalize(training = 1) as two launches instead of three:
- * the batch statistics of a training BatchNorm2d incl. the running-stat update; running_mean / running_var nullable together; 8 | C. */
+/* cobevt_channel_sums (x and x^2, taken about row 0 of x: a pivot inside the data whether or not a running mean exists or is near
+ * the batch) + cobevt_bn_finalize(training = 1) as two launches instead of three: the batch statistics of a training BatchNorm2d
+ * incl. the running-stat update; running_mean / running_var nullable together; 8 | C. */
 int cobevt_bn_batch_stats(const void* x, const float* gamma, const float* beta, float* running_mean, float* running_var, float* scale,
                           float* shift, float* mean, float* rstd, double* scratch, int scratch_blocks, int dtype, long rows, int C,
                           float eps, float momentum, long long* batches_tracked, hipStream_t stream);
@@ -621,7 +622,8 @@ int cobevt_bn_apply(const void* x, const void* residual, const float* scale, con
                     int C, int act, hipStream_t stream);
 /* Backward of cobevt_bn_apply behind the statistics: g = dy [y > 0 when act == 1]; dgamma_dbeta (fp64 [2][C], written) = sum g xhat,
  * sum g; grads_f (nullable) the same as fp32; dx = gamma rstd (g - (dbeta + xhat dgamma) / rows) with batch statistics, gamma rstd g
- * with frozen ones; dres (nullable) = g.  scratch: fp64 [scratch_blocks][2][C]. */
+ * with frozen ones; dres (nullable) = g.  scratch: fp64 [scratch_blocks][2][C], 16-byte aligned or COBEVT_ERR_ARG (the fp32 coefficients
+ * of the dx pass are left in its first 2 C words). */
 int cobevt_bn_backward(const void* x, const void* y, const void* dy, const float* mean, const float* rstd, const float* gamma,
                        double* dgamma_dbeta, float* grads_f, double* scratch, int scratch_blocks, void* dx, void* dres, int dtype,
                        long rows, int C, int act, int training, hipStream_t stream);
