@@ -31,6 +31,7 @@
 // No floating-point atomics, no workgroup waits on another, no host read-back, no allocation: the workspace comes from the caller
 // (cobevt_detect_scratch).  The same select / mask / greedy launches serve cobevt_nms_rotated (boxes and scores given, no filters).
 #include "common.hpp"
+#include "detect_targets.hpp"          // the training side: targets and loss (its entry points are at the end of this file)
 
 namespace cobevt {
 
@@ -557,5 +558,61 @@ extern "C" int cobevt_rotated_iou(const float* a, const float* b, double* iou, l
     if (N == 0 || M == 0) return COBEVT_OK;
     if (!a || !b || !iou) return COBEVT_ERR_ARG;
     hipLaunchKernelGGL(det_pair_iou_kernel, dim3((unsigned)((N * M + 255) / 256)), dim3(256), 0, stream, a, b, iou, (int)N, (int)M);
+    return cobevt::launch_status();
+}
+
+// ---------------------------------------------------------------------------------------------- targets and loss (detect_targets.hpp)
+extern "C" int cobevt_boxes_standup(const float* boxes, float* standup, long n, hipStream_t stream) {
+    if (n < 0 || n > 0x7fffffffL / 8) return COBEVT_ERR_SHAPE;
+    if (n == 0) return COBEVT_OK;
+    if (!boxes || !standup) return COBEVT_ERR_ARG;
+    if ((uintptr_t)standup & 15) return COBEVT_ERR_SHAPE;
+    hipLaunchKernelGGL(tgt_standup_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, boxes, standup, n);
+    return cobevt::launch_status();
+}
+
+extern "C" int cobevt_detect_targets(const float* anchors, const float* anchor_standup, const float* gt_boxes, const float* gt_standup,
+                                     const float* mask, float pos_threshold, float neg_threshold, float* pos_equal_one,
+                                     float* neg_equal_one, float* targets, int* num_pos, void* workspace, int B, int H, int W, int A,
+                                     int G, hipStream_t stream) {
+    if (!anchors || !anchor_standup || !pos_equal_one || !neg_equal_one || !targets || !num_pos || !workspace) return COBEVT_ERR_ARG;
+    if (G < 0 || G > kTgtMaxGt) return COBEVT_ERR_SHAPE;
+    if (G > 0 && (!gt_boxes || !gt_standup || !mask)) return COBEVT_ERR_ARG;
+    if (B < 1 || B > 65535 || H < 1 || W < 1 || A < 1 || (long)H > 0x7fffffffL / W || (long)H * W > (0x7fffffffL / 8) / A
+        || (long)H * W * A > (0x7fffffffL / 8) / B)
+        return COBEVT_ERR_SHAPE;
+    if (((uintptr_t)anchor_standup & 15) || ((uintptr_t)gt_standup & 15) || ((uintptr_t)workspace & 7)) return COBEVT_ERR_SHAPE;
+    const int M = H * W * A;
+    unsigned long long* best = (unsigned long long*)workspace;           // (B, max(G, 1)) keys
+    if (hipMemsetAsync(best, 0, 8 * (size_t)B * (G > 0 ? G : 1), stream) != hipSuccess) return COBEVT_ERR_LAUNCH;
+    if (hipMemsetAsync(num_pos, 0, 4 * (size_t)B, stream) != hipSuccess) return COBEVT_ERR_LAUNCH;
+    const dim3 grid((unsigned)((M + 255) / 256), (unsigned)B);
+    if (G > 0) hipLaunchKernelGGL(tgt_best_kernel, grid, dim3(256), 0, stream, anchor_standup, gt_standup, mask, best, M, G);
+    hipLaunchKernelGGL(tgt_label_kernel, grid, dim3(256), 0, stream, anchors, anchor_standup, gt_boxes, gt_standup, mask, best,
+                       pos_equal_one, neg_equal_one, targets, num_pos, M, G, pos_threshold, neg_threshold);
+    return cobevt::launch_status();
+}
+
+extern "C" int cobevt_pointpillar_loss(const float* psm, const float* rm, const float* pos_equal_one, const float* targets,
+                                       const int* num_pos, float* loss, float* dpsm, float* drm, void* workspace, int B, int H, int W,
+                                       int A, float cls_weight, float reg, hipStream_t stream) {
+    if (!psm || !rm || !pos_equal_one || !targets || !loss || !workspace || ((dpsm == nullptr) != (drm == nullptr))) return COBEVT_ERR_ARG;
+    if (B < 1 || B > 65535 || A < 1 || A > 65535 || H < 1 || W < 1 || (long)H > 0x7fffffffL / W || (long)H * W > (0x7fffffffL / 8) / A
+        || (long)H * W * A > (0x7fffffffL / 8) / B)
+        return COBEVT_ERR_SHAPE;
+    if ((uintptr_t)workspace & 7) return COBEVT_ERR_SHAPE;
+    const int HW = H * W, M = HW * A;
+    const long nblk = ppl_blocks(B, HW, A);
+    double* partial = (double*)workspace;                                // 2 nblk doubles, then B ints
+    int* counts = (int*)(partial + 2 * nblk);
+    if (!num_pos) {
+        if (hipMemsetAsync(counts, 0, 4 * (size_t)B, stream) != hipSuccess) return COBEVT_ERR_LAUNCH;
+        hipLaunchKernelGGL(ppl_count_kernel, dim3((unsigned)((M + 255) / 256), (unsigned)B), dim3(256), 0, stream, pos_equal_one, counts, M);
+        num_pos = counts;
+    }
+    hipLaunchKernelGGL(ppl_main_kernel, dim3((unsigned)((HW + 255) / 256), (unsigned)A, (unsigned)B), dim3(256), 0, stream, psm, rm,
+                       pos_equal_one, targets, num_pos, partial, dpsm, drm, HW, A, cls_weight / (float)B, reg / (float)B);
+    hipLaunchKernelGGL(ppl_finish_kernel, dim3(1), dim3(256), 0, stream, (const double*)partial, nblk, loss,
+                       (double)cls_weight / B, (double)reg / B);
     return cobevt::launch_status();
 }

@@ -154,6 +154,9 @@ SIGNATURES = {
     "cobevt_nms_rotated": (ctypes.c_int, [_vp, _vp, ctypes.c_long, ctypes.c_int, ctypes.c_float] + [_vp] * 5 + [_vp]),
     "cobevt_delta_to_boxes3d": (ctypes.c_int, [_vp, _vp, _vp] + [ctypes.c_int] * 4 + [_vp]),
     "cobevt_rotated_iou": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_long, ctypes.c_long, _vp]),
+    "cobevt_boxes_standup": (ctypes.c_int, [_vp, _vp, ctypes.c_long, _vp]),
+    "cobevt_detect_targets": (ctypes.c_int, [_vp] * 5 + [ctypes.c_float, ctypes.c_float] + [_vp] * 5 + [ctypes.c_int] * 5 + [_vp]),
+    "cobevt_pointpillar_loss": (ctypes.c_int, [_vp] * 9 + [ctypes.c_int] * 4 + [ctypes.c_float, ctypes.c_float, _vp]),
 }
 
 _libs = {}

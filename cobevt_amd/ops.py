@@ -1490,6 +1490,96 @@ def detect_post_process(cavs, score_threshold, nms_thresh, order, out=None, work
     return ob, osc, oi, oc
 
 
+DETECT_MAX_GT = 128        # ground-truth slots per sample cobevt_detect_targets takes (the reference's max_num is 100)
+
+
+def _dev_f32(t, what, shape=None, dims=None):
+    """a contiguous fp32 device tensor as it stands, or an error: the target / loss operators convert nothing"""
+    _need_cuda(t)
+    if t.dtype != torch.float32 or not t.is_contiguous() or (dims is not None and t.dim() != dims) or \
+            (shape is not None and tuple(t.shape) != tuple(shape)):
+        raise CobevtHipError("%s must be contiguous fp32%s, got %s %s"
+                             % (what, "" if shape is None else " %s" % (tuple(shape),), t.dtype, tuple(t.shape)))
+    return t
+
+
+def boxes_standup(boxes):
+    """boxes (n, 7) contiguous fp32 on the device, 'hwl' order -> (n, 4) fp32 [x1, y1, x2, y2]: the axis-aligned hull of the four
+    rotated footprint corners, box_utils.boxes_to_corners_3d + corner2d_to_standup_box (length = column 5, width = column 4), every
+    product and sum a separately rounded fp32 operation (csrc/detect_targets.hpp)."""
+    if boxes.dim() != 2 or boxes.shape[1] != 7:
+        raise CobevtHipError("boxes_standup: boxes must be (n, 7), got %s" % (tuple(boxes.shape),))
+    _dev_f32(boxes, "boxes_standup: boxes")
+    out = torch.empty((boxes.shape[0], 4), device=boxes.device, dtype=torch.float32)
+    _L.call("cobevt_boxes_standup", _p(boxes), _p(out), boxes.shape[0], _stream())
+    return out
+
+
+def detect_targets(anchors, anchor_standup, gt_boxes, gt_standup, mask, pos_threshold, neg_threshold):
+    """VoxelPostprocessor.generate_label for a batch, on the device and without a synchronisation (csrc/detect_targets.hpp).
+    anchors (H, W, A, 7) and anchor_standup (H W A, 4); gt_boxes (B, G, 7), gt_standup (B, G, 4), mask (B, G), G <= 128: all
+    contiguous fp32 on the device.  A slot is valid when its mask is 1; IoU column k is the k-th valid box and targets come from
+    that same box.  -> pos_equal_one (B, H, W, A), neg_equal_one (B, H, W, A), targets (B, H, W, 7A) fp32 and num_pos (B,) int32.
+    The IoU is bbox_overlaps' (`+1` convention) on the given standup boxes, bit-identical to the compiled reference's mixed float /
+    double arithmetic; the rules are stated in cobevt_hip.h.  Bitwise reproducible."""
+    if anchors.dim() != 4 or anchors.shape[3] != 7:
+        raise CobevtHipError("detect_targets: anchors must be (H, W, A, 7), got %s" % (tuple(anchors.shape),))
+    h, w, a = anchors.shape[:3]
+    m = h * w * a
+    if gt_boxes.dim() != 3 or gt_boxes.shape[2] != 7:
+        raise CobevtHipError("detect_targets: gt_boxes must be (B, G, 7), got %s" % (tuple(gt_boxes.shape),))
+    b, g = gt_boxes.shape[:2]
+    if g > DETECT_MAX_GT:
+        raise CobevtHipError("detect_targets: at most %d ground-truth slots per sample are supported, got %d" % (DETECT_MAX_GT, g))
+    if b < 1 or m < 1 or m * b > 0x7fffffff // 8:
+        raise CobevtHipError("detect_targets: %d samples of %d anchors are outside what the operator indexes" % (b, m))
+    _dev_f32(anchors, "detect_targets: anchors")
+    _dev_f32(anchor_standup, "detect_targets: anchor_standup", (m, 4))
+    _dev_f32(gt_boxes, "detect_targets: gt_boxes")
+    _dev_f32(gt_standup, "detect_targets: gt_standup", (b, g, 4))
+    _dev_f32(mask, "detect_targets: mask", (b, g))
+    dev = anchors.device
+    pos = torch.empty((b, h, w, a), device=dev, dtype=torch.float32)
+    neg = torch.empty((b, h, w, a), device=dev, dtype=torch.float32)
+    targets = torch.empty((b, h, w, 7 * a), device=dev, dtype=torch.float32)
+    num_pos = torch.empty((b,), device=dev, dtype=torch.int32)
+    ws = torch.empty((b * max(g, 1),), device=dev, dtype=torch.int64)
+    gp = (lambda t: _p(t) if g else None)
+    with _timed("detect_targets|B%d M%d G%d" % (b, m, g), lambda: (0.0, 16.0 * m * (2 + 9 * b))):
+        _L.call("cobevt_detect_targets", _p(anchors), _p(anchor_standup), gp(gt_boxes), gp(gt_standup), gp(mask), float(pos_threshold),
+                float(neg_threshold), _p(pos), _p(neg), _p(targets), _p(num_pos), _p(ws), b, h, w, a, g, _stream())
+    return pos, neg, targets, num_pos
+
+
+def pointpillar_loss(psm, rm, pos_equal_one, targets, cls_weight, reg, num_pos=None, want_grad=False):
+    """The PointPillar detection loss (upstream OpenCOOD's PointPillarLoss) and, with want_grad, its gradient, in one operator call
+    (csrc/detect_targets.hpp).  psm (B, A, H, W), rm (B, 7A, H, W) NCHW, pos_equal_one (B, H, W, A), targets (B, H, W, 7A): contiguous
+    fp32 on the device; num_pos (B,) int32 from detect_targets, or None to have the positives counted.
+    -> (loss (3,) fp32 = [total, conf_loss, reg_loss], d total / d psm or None, d total / d rm or None).  fp32 per element, fp64 sums
+    in a fixed order: bitwise reproducible, and the same bits with num_pos given or counted."""
+    _dev_f32(psm, "pointpillar_loss: psm", dims=4)
+    b, a, h, w = psm.shape
+    if b < 1 or a < 1 or h < 1 or w < 1 or b * a * h * w > 0x7fffffff // 8:
+        raise CobevtHipError("pointpillar_loss: psm %s is outside what the operator indexes" % (tuple(psm.shape),))
+    _dev_f32(rm, "pointpillar_loss: rm", (b, 7 * a, h, w))
+    _dev_f32(pos_equal_one, "pointpillar_loss: pos_equal_one", (b, h, w, a))
+    _dev_f32(targets, "pointpillar_loss: targets", (b, h, w, 7 * a))
+    if num_pos is not None:
+        _need_cuda(num_pos)
+        if num_pos.dtype != torch.int32 or tuple(num_pos.shape) != (b,) or not num_pos.is_contiguous():
+            raise CobevtHipError("pointpillar_loss: num_pos must be contiguous int32 (%d,), got %s %s" % (b, num_pos.dtype, tuple(num_pos.shape)))
+    dev = psm.device
+    loss = torch.empty((3,), device=dev, dtype=torch.float32)
+    dpsm = torch.empty_like(psm) if want_grad else None
+    drm = torch.empty_like(rm) if want_grad else None
+    nblk = ((h * w + 255) // 256) * a * b
+    ws = torch.empty((2 * nblk + (b + 1) // 2,), device=dev, dtype=torch.int64)
+    with _timed("pointpillar_loss|B%d A%d HW%d" % (b, a, h * w), lambda: (0.0, 4.0 * b * a * h * w * (16 + (8 if want_grad else 0)))):
+        _L.call("cobevt_pointpillar_loss", _p(psm), _p(rm), _p(pos_equal_one), _p(targets), _p(num_pos), _p(loss), _p(dpsm), _p(drm),
+                _p(ws), b, h, w, a, float(cls_weight), float(reg), _stream())
+    return loss, dpsm, drm
+
+
 def sttf_warp(x, tmat, cav_mask, discrete_ratio, downsample_rate, want_mask=True, record_len=None, max_cav=None):
     """x: (B, L, H, W, C) contiguous ; tmat (B, L, 4, 4) fp32 -> warped (B,L,H,W,C), com_mask (B,H,W,1,L)|None.
     With record_len (int32 device (B,)) x is the un-grouped agent batch (N, H, W, C): regroup + warp in one launch,

@@ -889,6 +889,50 @@ int cobevt_nms_rotated(const float* box_corners, const float* box_scores, long N
 int cobevt_delta_to_boxes3d(const float* rm, const float* anchors, float* boxes3d, int N, int H, int W, int A, hipStream_t stream);
 int cobevt_rotated_iou(const float* a, const float* b, double* iou, long N, long M, hipStream_t stream);
 
+/*
+ * LiDAR detection targets and loss (csrc/detect_targets.hpp, compiled into detect_post): OpenCOOD's
+ * VoxelPostprocessor.generate_label with the box_overlaps.bbox_overlaps it needs, and the PointPillar detection loss with its
+ * gradient.  fp32 / int32 data, fp64 only in the loss sums; identical in every library.
+ *
+ * cobevt_boxes_standup: boxes (n, 7) fp32 in 'hwl' order -> standup (n, 4) fp32 [x1, y1, x2, y2], the axis-aligned hull of the four
+ *   rotated footprint corners (boxes_to_corners_3d + corner2d_to_standup_box; length = column 5, width = column 4), every product
+ *   and sum a separately rounded fp32 operation.  standup 16-byte aligned.  One launch; n = 0 launches nothing.
+ *
+ * cobevt_detect_targets: anchors (H, W, A, 7) fp32 and their standup boxes (H W A, 4); gt_boxes (B, G, 7), gt_standup (B, G, 4),
+ *   mask (B, G) fp32, G <= 128 (more: code 2; G = 0 or a mask without a 1 is valid: everything negative).  A slot is valid when its
+ *   mask == 1; column k of the IoU matrix is the k-th VALID box and targets are taken from that same box (the reference indexes the
+ *   unfiltered array with the filtered index: the same thing for a prefix mask).  IoU = bbox_overlaps on the standup boxes with the
+ *   `+1` convention, bit-identical to the compiled reference: float coordinate differences, the `+ 1.0` sums, both areas and the
+ *   union in double (Cython emits the literal as a double), rounded to float once, then a float division - no fused multiply-add,
+ *   correctly rounded division.  Per valid gt the
+ *   highest anchor = the lowest anchor index of maximal IoU, kept when that IoU > 0.  Positive: any IoU > pos_threshold, or a kept
+ *   highest anchor; matched gt = the lowest k with IoU > pos_threshold if there is one, else the lowest k it is the kept highest
+ *   of.  Negative: every IoU < neg_threshold, cleared for kept highest anchors.  Outputs, all elements written: pos_equal_one and
+ *   neg_equal_one (B, H, W, A) fp32 0 / 1, targets (B, H, W, 7A) fp32 [(gx - ax) / d, (gy - ay) / d, (gz - az) / a3, log(g3 / a3),
+ *   log(g4 / a4), log(g5 / a5), g6 - a6] with d = sqrt(a4^2 + a5^2) for positives and 0 elsewhere, num_pos (B) int32.
+ *   Two memset nodes and two launches (one when G = 0); the per-gt maximum crosses workgroups by atomicMax on 64-bit integer keys
+ *   (IoU bits, inverted anchor index): integer atomics only, bitwise reproducible, no host read, no allocation.
+ *   workspace: 8 * B * max(G, 1) bytes, 8-byte aligned, contents irrelevant on entry; the standup boxes 16-byte aligned.
+ *
+ * cobevt_pointpillar_loss: psm (B, A, H, W) and rm (B, 7A, H, W) NCHW fp32 (channel a * 7 + k of rm = component k of anchor a),
+ *   pos_equal_one (B, H, W, A), targets (B, H, W, 7A), num_pos (B) int32 or NULL (then counted as pos_equal_one > 0, one more
+ *   launch with integer atomics) -> loss (3) fp32 = [total, conf_loss, reg_loss] and, when dpsm and drm are given (both or
+ *   neither), d total / d psm and d total / d rm in the maps' own layouts, from the same launch.  With p_b = max(1, num_pos[b]) and
+ *   t = pos_equal_one: conf_loss = cls_weight / B * sum [0.25 t + 0.75 (1 - t)] pt^2 bce / p_b, bce = max(x, 0) - x t +
+ *   log1p(exp(-|x|)), pt = t (1 - sigmoid(x)) + (1 - t) sigmoid(x); reg_loss = reg / B * sum over t > 0 of smooth_l1(d_k) / p_b with
+ *   beta = 1 / 9, d_k = rm_k - tgt_k (k < 6), d_6 = sin(rm_6) cos(tgt_6) - cos(rm_6) sin(tgt_6), a NaN target counting as d = 0;
+ *   total = conf_loss + reg_loss.  Per-element arithmetic fp32, sums fp64 in a fixed order (one partial pair per workgroup, then
+ *   one finishing workgroup): no floating-point atomics, bitwise reproducible.
+ *   workspace: 16 * ceil(H W / 256) * A * B + 4 * B bytes, 8-byte aligned.
+ */
+int cobevt_boxes_standup(const float* boxes, float* standup, long n, hipStream_t stream);
+int cobevt_detect_targets(const float* anchors, const float* anchor_standup, const float* gt_boxes, const float* gt_standup,
+                          const float* mask, float pos_threshold, float neg_threshold, float* pos_equal_one, float* neg_equal_one,
+                          float* targets, int* num_pos, void* workspace, int B, int H, int W, int A, int G, hipStream_t stream);
+int cobevt_pointpillar_loss(const float* psm, const float* rm, const float* pos_equal_one, const float* targets, const int* num_pos,
+                            float* loss, float* dpsm, float* drm, void* workspace, int B, int H, int W, int A, float cls_weight,
+                            float reg, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
