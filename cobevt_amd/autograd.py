@@ -401,11 +401,13 @@ class LayerNormFn(torch.autograd.Function):
         dx = torch.empty_like(x)
         dg = _zeros(C, x.device, torch.float32)
         db = _zeros(C, x.device, torch.float32)
+        # one {dgamma, dbeta} record per workgroup, summed in fp64 by the entry point's second launch
+        scratch = torch.empty(_L.load("").cobevt_layernorm_bwd_scratch(rows, C), device=x.device, dtype=torch.float32)
         if x.dtype == torch.float32 and dy.dtype == torch.float32:
-            _call("cobevt_layernorm_bwd", _p(x), _p(dy), _p(g), _p(dx), _p(dg), _p(db), rows, C, ctypes.c_float(ctx.eps), _stream())
+            _call("cobevt_layernorm_bwd", _p(x), _p(dy), _p(g), _p(dx), _p(dg), _p(db), rows, C, ctypes.c_float(ctx.eps), _p(scratch), _stream())
         else:
             _call("cobevt_layernorm_bwd_t", _p(x), _p(dy), _p(g), _p(dx), _p(dg), _p(db), rows, C, ctypes.c_float(ctx.eps),
-                  _ints([ops.dcode(x.dtype), ops.dcode(dy.dtype), ops.dcode(dx.dtype)]), _stream())
+                  _ints([ops.dcode(x.dtype), ops.dcode(dy.dtype), ops.dcode(dx.dtype)]), _p(scratch), _stream())
         return dx, dg, db, None, None
 
 

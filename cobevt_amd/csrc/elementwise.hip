@@ -38,7 +38,14 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const T* in, const float
 #pragma unroll
     for (int e = 0; e < 8; ++e) s += v[e];
     s = wave_sum_xor(s, G);
-    const float mean = s / (float)C;
+    // shift by the first mean, then centre by the mean of the shifted row: one rounding of the first mean is u |mean|, which rstd turns into
+    // u |mean| / sigma on every output of a mean-dominated row; the shift is exact there and the second mean rounds at the size of sigma
+    // (csrc/train_rows.hip takes the mean the same way: the backward recomputes what this forward used)
+    const float mean0 = s / (float)C;
+    float sd = 0.f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { v[e] -= mean0; sd += v[e]; }
+    const float mean = wave_sum_xor(sd, G) / (float)C;
     float q = 0.f;
 #pragma unroll
     for (int e = 0; e < 8; ++e) { const float d = v[e] - mean; q += d * d; }
@@ -402,7 +409,9 @@ __global__ __launch_bounds__(256) void resize_kernel(const T* in, T* out, int N,
         const float fy = oh * sh, fx = ow * sw;
         const int y0 = (int)fy, x0 = (int)fx;
         const int y1 = min(y0 + 1, H - 1), x1 = min(x0 + 1, W - 1);
-        const float ly = fy - (float)y0, lx = fx - (float)x0, hy = 1.f - ly, hx = 1.f - lx;
+        // index from the rounded product, fraction from the unrounded one (what the contraction of `fy - y0` gave, written out so that it does
+        // not depend on a compiler default: train_nusc.hip resize_bilinear_bwd_kernel takes the same weights)
+        const float ly = __fmaf_rn((float)oh, sh, -(float)y0), lx = __fmaf_rn((float)ow, sw, -(float)x0), hy = 1.f - ly, hx = 1.f - lx;
         float a[8], b[8], c[8], d[8];
         load8<T>(src + ((size_t)y0 * W + x0) * C, a);
         load8<T>(src + ((size_t)y0 * W + x1) * C, b);

@@ -154,7 +154,7 @@ __global__ __launch_bounds__(256) void wce_partial_kernel(const T* logits, const
 #pragma unroll
         for (int c = 0; c < C; ++c)
             if (y == c) { xy = x[c]; wy = weight[c]; }
-        num += wy * (m + logf(s) - xy);
+        num += wy * (logf(s) - (xy - m));           // not m + log s - x_y: that rounds at the size of m (half an ulp of m on a loss of log C)
         den += wy;
         // -100 = nn.CrossEntropyLoss's ignore_index: out of numerator and denominator.  Any other label outside [0, C) is an
         // error in the reference (it raises); counted here and refused by the host (ops.weighted_cross_entropy)

@@ -31,20 +31,23 @@ __global__ __launch_bounds__(kThreads) void swish_kernel(const T* __restrict__ x
 
 // ---- depthwise weight gradient: dw[(a * k + b)][c] = sum over (n, oy, ox) of dy[n][oy][ox][c] * x[n][oy s - pt + a][ox s - pl + b][c] ----
 // grid = (pixel blocks, k tap rows); a thread owns one 8-channel group and walks its share of the block's output pixels with the k taps
-// of the row as k x 8 accumulators; the threads of a group meet in LDS, one fp32 atomic per (workgroup, tap, channel) (dw zero-initialised)
+// of the row as k x 8 accumulators; the threads of a group meet in LDS, one fp32 atomic per (workgroup, tap, channel) (dw zero-initialised).
+// A thread's accumulators and the sum over the group's threads are fp64, rounded once per workgroup: at G = 256 one thread walks all of a
+// workgroup's pixels (513 of 1025 left an fp32 serial sum 30 x less accurate than torch's weight gradient), and the 256 LDS partials of
+// G = 1 are another serial chain.  dw then carries one fp32 rounding per workgroup (at most 256).
 template <typename T, int K>
 __global__ __launch_bounds__(kThreads) void depthwise_wgrad_kernel(const T* __restrict__ x, const T* __restrict__ dy, float* __restrict__ dw,
                                                                    int N, int H, int W, int C, int stride, int pt, int pl, int Ho, int Wo,
                                                                    long pixels, int per_block) {
     const int G = C >> 3;                                          // <= 256 (entry point)
     const int a = blockIdx.y;
-    __shared__ float red[kThreads][9];
+    __shared__ double red[kThreads][9];
     const int gl = threadIdx.x % G, r0 = threadIdx.x / G, rstep = kThreads / G;       // threads with r0 >= rstep idle
-    float acc[K][8];
+    double acc[K][8];
 #pragma unroll
     for (int b = 0; b < K; ++b)
 #pragma unroll
-        for (int e = 0; e < 8; ++e) acc[b][e] = 0.f;
+        for (int e = 0; e < 8; ++e) acc[b][e] = 0.0;
     const long lo = (long)blockIdx.x * per_block, hi = lo + per_block < pixels ? lo + per_block : pixels;
     if (r0 < rstep) {
         for (long p = lo + r0; p < hi; p += rstep) {
@@ -63,7 +66,7 @@ __global__ __launch_bounds__(kThreads) void depthwise_wgrad_kernel(const T* __re
                 float v[8];
                 load8<T>(x + ((n * H + iy) * W + ix) * C + gl * 8, v);
 #pragma unroll
-                for (int e = 0; e < 8; ++e) acc[b][e] += g[e] * v[e];
+                for (int e = 0; e < 8; ++e) acc[b][e] += (double)g[e] * (double)v[e];
             }
         }
     }
@@ -74,15 +77,15 @@ __global__ __launch_bounds__(kThreads) void depthwise_wgrad_kernel(const T* __re
         for (int e = 0; e < 8; ++e) red[threadIdx.x][e] = acc[b][e];
         __syncthreads();
         if (threadIdx.x < G) {
-            float s[8];
+            double s[8];
 #pragma unroll
-            for (int e = 0; e < 8; ++e) s[e] = 0.f;
+            for (int e = 0; e < 8; ++e) s[e] = 0.0;
             for (int r = 0; r < rstep; ++r)
 #pragma unroll
                 for (int e = 0; e < 8; ++e) s[e] += red[r * G + threadIdx.x][e];
 #pragma unroll
             for (int e = 0; e < 8; ++e)
-                if (s[e] != 0.f) atomicAdd(dw + (size_t)(a * K + b) * C + threadIdx.x * 8 + e, s[e]);
+                if (s[e] != 0.0) atomicAdd(dw + (size_t)(a * K + b) * C + threadIdx.x * 8 + e, (float)s[e]);
         }
     }
 }
@@ -103,7 +106,9 @@ __global__ __launch_bounds__(kThreads) void resize_bilinear_bwd_kernel(const T* 
     const float fy = oh * sh, fx = ow * sw;
     const int y0 = (int)fy, x0 = (int)fx;
     const int y1 = min(y0 + 1, H - 1), x1 = min(x0 + 1, W - 1);
-    const float ly = fy - (float)y0, lx = fx - (float)x0, hy = 1.f - ly, hx = 1.f - lx;
+    // index from the rounded product, fraction from the UNROUNDED one, written out as in the forward (elementwise.hip resize_kernel) so that
+    // neither depends on the compiler's contraction; tests/test_train_rows_gpu.py holds both kernels to this rule
+    const float ly = __fmaf_rn((float)oh, sh, -(float)y0), lx = __fmaf_rn((float)ow, sw, -(float)x0), hy = 1.f - ly, hx = 1.f - lx;
     float g[8];
     load8<T>(dy + pix * C + gl * 8, g);
     float* base = dx + n * H * W * C + gl * 8;

@@ -1,8 +1,8 @@
 // Row-local backward kernels of the training slice (fp32): LayerNorm backward and exact-erf GELU forward / backward.
 // The reference gets these from torch autograd (nn.LayerNorm / nn.GELU of base_transformer.py:102-124,
 // swap_fusion_modules.py:275-279, fax_modules.py:189-191,309-313) under train_camera.py:143-179.  HBM-bound elementwise work:
-// one wave per row, 16-byte accesses, the per-channel sums (dgamma, dbeta) accumulated in registers over a workgroup's rows
-// and added to the global fp32 vectors once per workgroup.
+// one wave per row, 16-byte accesses, the per-channel sums (dgamma, dbeta) accumulated in registers over a workgroup's rows,
+// written as one record per workgroup and added in fp64 by a second launch (ln_bwd_finish_kernel).
 #include "wave_ops.hpp"
 
 namespace cobevt {
@@ -11,11 +11,16 @@ namespace {
 constexpr int kLnMaxPerLane = 4;                         // float4 groups per lane: C <= 64 * 4 * 4 = 1024
 
 // y = LN(x) gamma + beta.  dx = rstd (g - mean(g) - xhat mean(g xhat)), g = dy gamma; dgamma += dy xhat; dbeta += dy.
+// The mean is sum / C, a correctly rounded division, in every kernel of this file: sum * (1 / C) is an ulp off for a constant row at
+// C = 1020 (1 / C is inexact), which rstd = 1 / sqrt(eps) turns into y = beta + 7.5e-5 gamma where nn.LayerNorm gives beta.
+// And it is taken twice: the row is shifted by the first mean (x - mean0 is exact where the row is mean-dominated) and centred by the
+// mean of the shifted row.  One rounding of the first mean is u |mean|, which rstd turns into u |mean| / sigma on every xhat of the row
+// (6e-6 for N(100, 1) rows, as in torch's layer_norm); the second mean is rounded at the size of sigma.
 // x / dy / dx are fp32 or bf16 each (xb / db / ob: 1 = bf16) - inside a bf16 autocast region the residual stream is fp32 while the
 // gradient arriving from a projection's input gradient is bf16 (train_camera.py:157-160); the arithmetic is fp32 either way.
 __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const void* __restrict__ x, const void* __restrict__ dy,
                                                             const float* __restrict__ gamma, void* __restrict__ dx,
-                                                            float* __restrict__ dgamma, float* __restrict__ dbeta, int rows, int C,
+                                                            float* __restrict__ partial, int rows, int C,
                                                             float eps, int rows_per_block, int xb, int db_, int ob) {
     __shared__ float red[2][4][1024];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -42,7 +47,16 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const void* __restri
             dv[i] = ok ? ld4q(dy, (size_t)row * C + 4 * g, db_) : make_float4(0.f, 0.f, 0.f, 0.f);
             s += xv[i].x + xv[i].y + xv[i].z + xv[i].w;
         }
-        const float mean = wave_sum_xor(s, 64) * invC;
+        const float mean0 = wave_sum_xor(s, 64) / (float)C;
+        float sd = 0.f;
+#pragma unroll
+        for (int i = 0; i < kLnMaxPerLane; ++i) {
+            if (lane + 64 * i < groups) {
+                xv[i].x -= mean0; xv[i].y -= mean0; xv[i].z -= mean0; xv[i].w -= mean0;
+                sd += xv[i].x + xv[i].y + xv[i].z + xv[i].w;
+            }
+        }
+        const float mean = wave_sum_xor(sd, 64) / (float)C;         // of the shifted row: see the head of the file
         float v = 0.f;
 #pragma unroll
         for (int i = 0; i < kLnMaxPerLane; ++i) {
@@ -78,8 +92,8 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const void* __restri
             }
         }
     }
-    if (!dgamma) return;
-    // workgroup reduction of the per-channel sums, then one atomic per channel
+    if (!partial) return;
+    // workgroup reduction of the per-channel sums into this workgroup's record {dgamma[C], dbeta[C]} (ln_bwd_finish_kernel adds the records)
 #pragma unroll
     for (int i = 0; i < kLnMaxPerLane; ++i) {
         const int g = lane + 64 * i;
@@ -89,20 +103,49 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const void* __restri
         }
     }
     __syncthreads();
+    float* rec = partial + (size_t)blockIdx.x * 2 * C;
     for (int c = threadIdx.x; c < C; c += 256) {
-        atomicAdd(dgamma + c, red[0][0][c] + red[0][1][c] + red[0][2][c] + red[0][3][c]);
-        atomicAdd(dbeta + c, red[1][0][c] + red[1][1][c] + red[1][2][c] + red[1][3][c]);
+        rec[c] = red[0][0][c] + red[0][1][c] + red[0][2][c] + red[0][3][c];
+        rec[C + c] = red[1][0][c] + red[1][1][c] + red[1][2][c] + red[1][3][c];
+    }
+}
+
+// dgamma[c] += sum over the workgroups' records, dbeta the same: the sum and the addition in fp64, ONE fp32 rounding per word.  (The
+// records used to be added with one fp32 atomic per workgroup and word: a chain of B additions onto a growing sum leaves about
+// sqrt(B / 12) ulps of it where torch's two-stage column sums leave one - 4 to 7 x torch's error against float64 at B = 64 .. 256, in an
+// order that changed from run to run; tests/golden/README_train_rows.md.)
+// One workgroup = 32 consecutive words x 32 slices of the records (a serial walk over 256 - 1024 records by one thread per word cost 60 - 250 us
+// in dependent round trips); a thread's slice, then the 32 slices, are added in a fixed order.
+__global__ __launch_bounds__(1024) void ln_bwd_finish_kernel(const float* __restrict__ partial, float* __restrict__ dgamma,
+                                                             float* __restrict__ dbeta, int C, int blocks) {
+    __shared__ double red[32][33];
+    const int w = threadIdx.x & 31, sl = threadIdx.x >> 5;
+    const int t = blockIdx.x * 32 + w;
+    double s = 0.0;
+    if (t < 2 * C) {
+#pragma unroll 8
+        for (int b = sl; b < blocks; b += 32) s += (double)partial[(size_t)b * 2 * C + t];
+    }
+    red[sl][w] = s;
+    __syncthreads();
+    if (sl == 0 && t < 2 * C) {
+        double a = 0.0;
+#pragma unroll
+        for (int k = 0; k < 32; ++k) a += red[k][w];
+        float* dst = t < C ? dgamma + t : dbeta + (t - C);
+        *dst = (float)((double)*dst + a);
     }
 }
 
 // C <= 128 (the FAX / fusion width): a row is 32 float4 groups, so a whole wave per row leaves half of it idle and a row per HALF-wave
 // doubles the rows in flight (the 81,920 x 128 level-0 rows took 57 us per launch, 1.9 TB/s).  One float4 per lane, reductions inside 32 lanes.
-// NW waves per workgroup: 16 on big inputs - every workgroup ends in 2 C atomics on the SAME words, and 1,024 four-wave workgroups made the
-// 81,920-row launches 49 us for 105 MB (a serialised tail of ~1,000 atomics per word); the same waves in a quarter of the workgroups
+// NW waves per workgroup: 16 from 16,384 rows on.  The form dates from the time when every workgroup ended in 2 C atomics on the SAME words
+// (1,024 four-wave workgroups made the 81,920-row launches 49 us for 105 MB); with one record per workgroup that tail is gone, and what the
+// sixteen waves still buy is measured in DESIGN.md 3n
 template <int NW>
 __global__ __launch_bounds__(NW * 64) void layernorm_bwd_narrow_kernel(const void* __restrict__ x, const void* __restrict__ dy,
                                                                    const float* __restrict__ gamma, void* __restrict__ dx,
-                                                                   float* __restrict__ dgamma, float* __restrict__ dbeta, int rows, int C,
+                                                                   float* __restrict__ partial, int rows, int C,
                                                                    float eps, int rows_per_block, int xb, int db_, int ob) {
     constexpr int HW = NW * 2;                        // half-waves = rows in flight per round
     __shared__ float red[2][HW][128];
@@ -126,8 +169,10 @@ __global__ __launch_bounds__(NW * 64) void layernorm_bwd_narrow_kernel(const voi
         dv[1] = (ok && okb) ? ld4q(dy, (size_t)rowb * C + 4 * g, db_) : make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
-            const float mean = half_wave_sum(xv[u].x + xv[u].y + xv[u].z + xv[u].w) * invC;
-            const float a = xv[u].x - mean, b = xv[u].y - mean, c = xv[u].z - mean, d = xv[u].w - mean;
+            const float mean0 = half_wave_sum(xv[u].x + xv[u].y + xv[u].z + xv[u].w) / (float)C;
+            float a = xv[u].x - mean0, b = xv[u].y - mean0, c = xv[u].z - mean0, d = xv[u].w - mean0;
+            const float mean1 = half_wave_sum(ok ? a + b + c + d : 0.f) / (float)C;      // of the shifted row: see the head of the file
+            a -= mean1; b -= mean1; c -= mean1; d -= mean1;
             const float rstd = 1.f / sqrtf(half_wave_sum(ok ? a * a + b * b + c * c + d * d : 0.f) * invC + eps);
             const float4 xh = make_float4(a * rstd, b * rstd, c * rstd, d * rstd);
             float4 gv = dv[u];
@@ -145,7 +190,7 @@ __global__ __launch_bounds__(NW * 64) void layernorm_bwd_narrow_kernel(const voi
             }
         }
     }
-    if (!dgamma) return;
+    if (!partial) return;
     if (ok) {
         *(float4*)&red[0][wave * 2 + sub][4 * g] = dg;
         *(float4*)&red[1][wave * 2 + sub][4 * g] = db;
@@ -155,8 +200,8 @@ __global__ __launch_bounds__(NW * 64) void layernorm_bwd_narrow_kernel(const voi
         float a = 0.f, b = 0.f;
 #pragma unroll
         for (int k = 0; k < HW; ++k) { a += red[0][k][c]; b += red[1][k][c]; }
-        atomicAdd(dgamma + c, a);
-        atomicAdd(dbeta + c, b);
+        partial[(size_t)blockIdx.x * 2 * C + c] = a;
+        partial[(size_t)blockIdx.x * 2 * C + C + c] = b;
     }
 }
 
@@ -208,8 +253,10 @@ __global__ __launch_bounds__(256) void layernorm_fwd_mixed_narrow_kernel(const v
     const bool ok = g < (C >> 2) && row < rows;
     const float4 xv = ok ? ld4q(x, (size_t)row * C + 4 * g, xb) : make_float4(0.f, 0.f, 0.f, 0.f);
     const float invC = 1.f / (float)C;
-    const float mean = half_wave_sum(xv.x + xv.y + xv.z + xv.w) * invC;
-    const float a = xv.x - mean, b = xv.y - mean, c = xv.z - mean, d = xv.w - mean;
+    const float mean0 = half_wave_sum(xv.x + xv.y + xv.z + xv.w) / (float)C;
+    float a = xv.x - mean0, b = xv.y - mean0, c = xv.z - mean0, d = xv.w - mean0;
+    const float mean1 = half_wave_sum(ok ? a + b + c + d : 0.f) / (float)C;              // of the shifted row: see the head of the file
+    a -= mean1; b -= mean1; c -= mean1; d -= mean1;
     const float rstd = 1.f / sqrtf(half_wave_sum(ok ? a * a + b * b + c * c + d * d : 0.f) * invC + eps);
     if (!ok) return;
     const float4 ga = gamma ? *(const float4*)(gamma + 4 * g) : make_float4(1.f, 1.f, 1.f, 1.f);
@@ -236,7 +283,16 @@ __global__ __launch_bounds__(256) void layernorm_fwd_mixed_kernel(const void* __
         s += xv[i].x + xv[i].y + xv[i].z + xv[i].w;
     }
     const float invC = 1.f / (float)C;
-    const float mean = wave_sum_xor(s, 64) * invC;
+    const float mean0 = wave_sum_xor(s, 64) / (float)C;
+    float sd = 0.f;
+#pragma unroll
+    for (int i = 0; i < kLnMaxPerLane; ++i) {
+        if (lane + 64 * i < groups) {
+            xv[i].x -= mean0; xv[i].y -= mean0; xv[i].z -= mean0; xv[i].w -= mean0;
+            sd += xv[i].x + xv[i].y + xv[i].z + xv[i].w;
+        }
+    }
+    const float mean = wave_sum_xor(sd, 64) / (float)C;             // of the shifted row: see the head of the file
     float v = 0.f;
 #pragma unroll
     for (int i = 0; i < kLnMaxPerLane; ++i) {
@@ -515,56 +571,42 @@ __global__ __launch_bounds__(256) void conv_wgrad16_cols_kernel(Wgrad16Params p)
 
 using namespace cobevt;
 
+// Rows per workgroup of the LayerNorm backward: enough workgroups to fill the chip; from 16,384 narrow rows on, sixteen waves each
+static int ln_bwd_rows_per_block(int rows, int C) {
+    const int rpb = ((rows + 1023) / 1024 + 3) / 4 * 4;
+    if (C > 128) return rpb;
+    if (rows >= 16384) return ((rows + 255) / 256 + 63) / 64 * 64;
+    return (rpb + 15) / 16 * 16;
+}
+
 // C-ABI entry points, see include/cobevt_hip.h
-extern "C" int cobevt_layernorm_bwd(const float* x, const float* dy, const float* gamma, float* dx, float* dgamma, float* dbeta,
-                                    int rows, int C, float eps, hipStream_t stream) {
-    if (!x || !dy || !dx || ((dgamma == nullptr) != (dbeta == nullptr))) return COBEVT_ERR_ARG;
-    if (rows < 1 || C < 4 || C % 4 || C > 1024) return COBEVT_ERR_SHAPE;
-    // enough workgroups to fill the chip, few enough that the per-channel atomics stay cheap
-    int rpb = (rows + 1023) / 1024;
-    rpb = ((rpb + 3) / 4) * 4;
-    const int blocks = (rows + rpb - 1) / rpb;
-    if (C <= 128) {
-        if (rows >= 16384) {
-            rpb = ((rows + 255) / 256 + 63) / 64 * 64;
-            hipLaunchKernelGGL(layernorm_bwd_narrow_kernel<16>, dim3((rows + rpb - 1) / rpb), dim3(1024), 0, stream, (const void*)x, (const void*)dy,
-                               gamma, (void*)dx, dgamma, dbeta, rows, C, eps, rpb, 0, 0, 0);
-        } else {
-            rpb = ((rpb + 15) / 16) * 16;
-            hipLaunchKernelGGL(layernorm_bwd_narrow_kernel<4>, dim3((rows + rpb - 1) / rpb), dim3(256), 0, stream, (const void*)x, (const void*)dy,
-                               gamma, (void*)dx, dgamma, dbeta, rows, C, eps, rpb, 0, 0, 0);
-        }
-        return cobevt::launch_status();
-    }
-    hipLaunchKernelGGL(layernorm_bwd_kernel, dim3(blocks), dim3(256), 0, stream, (const void*)x, (const void*)dy, gamma, (void*)dx, dgamma, dbeta, rows, C,
-                       eps, rpb, 0, 0, 0);
-    return cobevt::launch_status();
+extern "C" long cobevt_layernorm_bwd_scratch(int rows, int C) {
+    if (rows < 1 || C < 4 || C % 4 || C > 1024) return 0;
+    const int rpb = ln_bwd_rows_per_block(rows, C);
+    return (long)((rows + rpb - 1) / rpb) * 2 * C;
 }
 
 // dtypes: [x, dy, dx], 0 = bf16, 1 = fp32 each
 extern "C" int cobevt_layernorm_bwd_t(const void* x, const void* dy, const float* gamma, void* dx, float* dgamma, float* dbeta,
-                                      int rows, int C, float eps, const int* dtypes, hipStream_t stream) {
-    if (!x || !dy || !dx || !dtypes || ((dgamma == nullptr) != (dbeta == nullptr))) return COBEVT_ERR_ARG;
+                                      int rows, int C, float eps, const int* dtypes, float* scratch, hipStream_t stream) {
+    if (!x || !dy || !dx || !dtypes || ((dgamma == nullptr) != (dbeta == nullptr)) || (dgamma && !scratch)) return COBEVT_ERR_ARG;
     for (int i = 0; i < 3; ++i) if (dtypes[i] != 0 && dtypes[i] != 1) return COBEVT_ERR_ARG;
     if (rows < 1 || C < 4 || C % 4 || C > 1024) return COBEVT_ERR_SHAPE;
-    int rpb = (rows + 1023) / 1024;
-    rpb = ((rpb + 3) / 4) * 4;
+    const int rpb = ln_bwd_rows_per_block(rows, C);
     const int blocks = (rows + rpb - 1) / rpb;
-    if (C <= 128) {
-        if (rows >= 16384) {
-            rpb = ((rows + 255) / 256 + 63) / 64 * 64;
-            hipLaunchKernelGGL(layernorm_bwd_narrow_kernel<16>, dim3((rows + rpb - 1) / rpb), dim3(1024), 0, stream, x, dy, gamma, dx, dgamma, dbeta, rows,
-                               C, eps, rpb, dtypes[0] == 0, dtypes[1] == 0, dtypes[2] == 0);
-        } else {
-            rpb = ((rpb + 15) / 16) * 16;
-            hipLaunchKernelGGL(layernorm_bwd_narrow_kernel<4>, dim3((rows + rpb - 1) / rpb), dim3(256), 0, stream, x, dy, gamma, dx, dgamma, dbeta, rows,
-                               C, eps, rpb, dtypes[0] == 0, dtypes[1] == 0, dtypes[2] == 0);
-        }
-        return cobevt::launch_status();
-    }
-    hipLaunchKernelGGL(layernorm_bwd_kernel, dim3(blocks), dim3(256), 0, stream, x, dy, gamma, dx, dgamma, dbeta, rows, C, eps, rpb,
-                       dtypes[0] == 0, dtypes[1] == 0, dtypes[2] == 0);
+    float* partial = dgamma ? scratch : nullptr;
+    const int xb = dtypes[0] == 0, db = dtypes[1] == 0, ob = dtypes[2] == 0;
+    if (C > 128) hipLaunchKernelGGL(layernorm_bwd_kernel, dim3(blocks), dim3(256), 0, stream, x, dy, gamma, dx, partial, rows, C, eps, rpb, xb, db, ob);
+    else if (rows >= 16384) hipLaunchKernelGGL(layernorm_bwd_narrow_kernel<16>, dim3(blocks), dim3(1024), 0, stream, x, dy, gamma, dx, partial, rows, C, eps, rpb, xb, db, ob);
+    else hipLaunchKernelGGL(layernorm_bwd_narrow_kernel<4>, dim3(blocks), dim3(256), 0, stream, x, dy, gamma, dx, partial, rows, C, eps, rpb, xb, db, ob);
+    if (partial) hipLaunchKernelGGL(ln_bwd_finish_kernel, dim3((2 * C + 31) / 32), dim3(1024), 0, stream, (const float*)partial, dgamma, dbeta, C, blocks);
     return cobevt::launch_status();
+}
+
+extern "C" int cobevt_layernorm_bwd(const float* x, const float* dy, const float* gamma, float* dx, float* dgamma, float* dbeta,
+                                    int rows, int C, float eps, float* scratch, hipStream_t stream) {
+    const int fp32[3] = {1, 1, 1};
+    return cobevt_layernorm_bwd_t(x, dy, gamma, dx, dgamma, dbeta, rows, C, eps, fp32, scratch, stream);
 }
 
 // dtypes: [x, y], 0 = bf16, 1 = fp32 each

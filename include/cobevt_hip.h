@@ -260,22 +260,28 @@ int cobevt_window_attention_bwd(const void* q, const void* k, const void* v, con
 int cobevt_attention_dropout_mask(int B, int L, int heads, int Nq, int Nk, float drop_p, unsigned drop_seed, unsigned char* keep,
                                   hipStream_t stream);
 
-/* Row-local backward kernels of the training slice (fp32).  cobevt_layernorm_bwd: x, dy (rows, C) -> dx; ADDS dy * xhat / dy
- * column sums into zero-initialised dgamma[C] / dbeta[C] (both nullable together); gamma nullable (= 1).  C % 4 == 0, C <= 1024.
+/* Row-local backward kernels of the training slice (fp32).  cobevt_layernorm_bwd: x, dy (rows, C) -> dx; ADDS the dy * xhat / dy
+ * column sums into dgamma[C] / dbeta[C] (both nullable together; whatever they hold is kept: zero them for a plain gradient); gamma
+ * nullable (= 1).  C % 4 == 0, 4 <= C <= 1024.  scratch: exactly cobevt_layernorm_bwd_scratch(rows, C) floats (one {dgamma, dbeta} record per
+ * workgroup; 0 for a shape the entry points refuse), needed when dgamma / dbeta are given, not read or written otherwise: the records
+ * are summed in fp64 and each word of dgamma / dbeta takes one fp32 rounding, in a fixed order (bit-reproducible).
  * cobevt_gelu: out = GELU(x) (dy null) or dy * GELU'(x) (exact erf form, nn.GELU()); n % 4 == 0.
  * (nn.LayerNorm / nn.GELU under autograd: base_transformer.py:102-124, swap_fusion_modules.py:275-279, fax_modules.py:189-191.) */
+long cobevt_layernorm_bwd_scratch(int rows, int C);
 int cobevt_layernorm_bwd(const float* x, const float* dy, const float* gamma, float* dx, float* dgamma, float* dbeta, int rows,
-                         int C, float eps, hipStream_t stream);
+                         int C, float eps, float* scratch, hipStream_t stream);
 int cobevt_gelu(const float* x, const float* dy, float* out, long n, hipStream_t stream);
 /*
  * The same inside a bf16 autocast region (train_camera.py:157-160: torch's autocast runs layer_norm in fp32 and hands its result to the
  * bf16 projection that follows; nn.GELU runs in its input's bf16): every tensor fp32 or bf16 (dtype codes 0 = bf16, 1 = fp32), fp32
  * arithmetic.  cobevt_layernorm_fwd_t dtypes = [x, y]; cobevt_layernorm_bwd_t dtypes = [x, dy, dx]; cobevt_gelu_bf16: all bf16, n % 8 == 0.
+ * The row mean is sum / C (a division), taken twice - of the row, then of the row shifted by it: a constant row has xhat = 0 and y = beta
+ * exactly at every C, and a mean-dominated row loses nothing to the rounding of its mean.  cobevt_layernorm takes it the same way.
  */
 int cobevt_layernorm_fwd_t(const void* x, const float* gamma, const float* beta, void* y, int rows, int C, float eps, const int* dtypes,
                            hipStream_t stream);
 int cobevt_layernorm_bwd_t(const void* x, const void* dy, const float* gamma, void* dx, float* dgamma, float* dbeta, int rows, int C,
-                           float eps, const int* dtypes, hipStream_t stream);
+                           float eps, const int* dtypes, float* scratch, hipStream_t stream);
 int cobevt_gelu_bf16(const void* x, const void* dy, void* out, long n, hipStream_t stream);
 /* Weight gradient of a k x k convolution, channels-last: dw fp32 (Cout, Cin, k, k) += sum over output pixels of dy (N, Ho, Wo, Cout)
  * x the tap-shifted x (N, H, W, Cin); dw must be zero-initialised (fp32 atomics).  dims (int32[11]): N, H, W, Cin, Ho, Wo, Cout, k,
@@ -454,11 +460,14 @@ int cobevt_seg_class_counts(const long long* pred, const long long* gt, unsigned
  * / sum_i w[y_i], out[1] / out[2] = numerator / denominator, out[3] = number of labels outside [0, C) other than -100 (the
  * ignore_index of nn.CrossEntropyLoss, which contributes to neither sum); the reference raises for such labels, so the caller
  * must refuse a result with out[3] != 0.  logits (N, C, hw) planar (dtype 0 bf16 / 1 fp32, 2 <= C <= 8), target (N, hw) int64,
- * weight [C] fp32, out >= 4 floats, scratch >= 3 * N * ceil(hw / 4096) floats, fixed summation order. */
+ * weight [C] fp32, out >= 4 floats, scratch >= 3 * N * ceil(hw / 4096) floats (one {numerator, denominator, count} record per 4096 pixels
+ * of an image; exactly that many are written), fixed summation order.  The sums are fp32: out[3] is exact below 2^24 bad labels.  With
+ * every label -100 out[1] = out[2] = out[3] = 0 and out[0] = 0 / 0 = NaN, as nn.CrossEntropyLoss. */
 int cobevt_weighted_cross_entropy(const void* logits, const long long* target, const float* weight, float* scratch, float* out,
                                   int dtype, int N, int C, int hw, hipStream_t stream);
 /* Backward of the loss above for fp32 logits: dlogits (N, C, hw) = upstream[0] * w[y] (softmax_c - [c == y]) / sum w[y]; stats = the
- * forward's out[4]; upstream = the incoming gradient of the scalar loss (device fp32[1]).  train_camera.py:166-173 loss.backward(). */
+ * forward's out[4]; upstream = the incoming gradient of the scalar loss (device fp32[1]).  train_camera.py:166-173 loss.backward().
+ * A pixel labelled -100 gets exactly 0 in every class.  With stats[2] == 0 (every label ignored) every element is NaN (0 / 0, as torch). */
 int cobevt_weighted_cross_entropy_bwd(const float* logits, const long long* target, const float* weight, const float* stats,
                                       const float* upstream, float* dlogits, int N, int C, int hw, hipStream_t stream);
 
@@ -490,7 +499,9 @@ int cobevt_bev_embed_linear_rows_small_k(const float* E_inv, const float* world,
 /* Forward of BinarySegmentationLoss / CenterLoss, nuscenes/cross_view_transformer/losses.py:27-84: sigmoid focal loss (fvcore's
  * published definition) of pred (N, C, hw) fp32 logits against label_c = max over the label channels in label_mask[c]
  * (soft_label: label channel c itself, NL == C), over the pixels with visibility >= min_visibility (< 0: all), mean.
- * out[0] = mean, out[1] = sum, out[2] = count; scratch >= 2 * N * ceil(hw / 2048) floats; fixed summation order. */
+ * out[0] = mean, out[1] = sum, out[2] = count; scratch >= 2 * N * ceil(hw / 2048) floats (one {sum, count} record per 2048 pixels of an
+ * image; exactly that many are written); fixed summation order.  The count is an fp32 sum of ones: exact below 2^24 kept elements.
+ * With no pixel kept out[1] = out[2] = 0 and out[0] = 0 / 0 = NaN. */
 int cobevt_sigmoid_focal_loss(const float* pred, const float* label, const unsigned char* visibility, const unsigned int* label_mask,
                               float* scratch, float* out, int N, int C, int NL, int hw, int min_visibility, float alpha,
                               float gamma, int soft_label, hipStream_t stream);
@@ -716,14 +727,17 @@ int cobevt_wgrad_block_operand(const void* src, void* dst, const int* dims, hipS
  * dtype 0 bf16 / 1 fp32. */
 int cobevt_swish(const void* x, const void* dy, void* out, int dtype, long n, hipStream_t stream);
 /* Weight gradient of the depthwise k x k convolution (k = 3 / 5): dw fp32 [k * k][C] += sum over output pixels of dy (N, Ho, Wo, C) x the
- * tap-shifted x (N, H, W, C); dw zero-initialised.  dims (int32[11]): dtype, N, H, W, C, k, stride, pad_top, pad_left, Ho, Wo.  (The input
+ * tap-shifted x (N, H, W, C); ADDED to what dw holds (zero it for a plain gradient): a workgroup's share is summed in fp64 and added with one
+ * fp32 atomic per entry, at most 256 per entry.  dims (int32[11]): dtype, N, H, W, C, k, stride, pad_top, pad_left, Ho, Wo.  (The input
  * gradient is cobevt_depthwise_conv_nhwc on the flipped taps, on the zero-stuffed gradient when strided.) */
 int cobevt_depthwise_wgrad(const void* x, const void* dy, float* dw, const int* dims, hipStream_t stream);
 /* Adjoint of cobevt_resize_nhwc mode 1 (align_corners bilinear; nn.Upsample of decoder.py:12): dy (N, Ho, Wo, C) -> dx fp32 (N, H, W, C),
- * zero-initialised. */
+ * ADDED with fp32 atomics to what dx holds (zero it first).  Both kernels take source row floor(fp32(oh * scale)), scale = fp32((H - 1) / (Ho - 1))
+ * (0 when Ho == 1), clamp the next row to H - 1 and weigh it by fma(oh, scale, -floor), the fraction of the unrounded product; columns alike. */
 int cobevt_resize_bilinear_bwd(const void* dy, float* dx, int dtype, int N, int H, int W, int C, int Ho, int Wo, hipStream_t stream);
 /* Gradient of cobevt_sigmoid_focal_loss's mean w.r.t. the logits: dpred (N, C, hw) fp32 = gscale[0] / count x d loss / d logit on the kept
- * elements, 0 elsewhere.  stats = the forward's out[3] (mean, sum, count) and gscale (the upstream gradient) are DEVICE words: no host sync. */
+ * elements, 0 elsewhere.  stats = the forward's out[3] (mean, sum, count) and gscale (the upstream gradient) are DEVICE words: no host sync.
+ * With count == 0 (no pixel kept) every element is 0. */
 int cobevt_sigmoid_focal_loss_bwd(const float* pred, const float* label, const unsigned char* visibility, const unsigned int* label_mask,
                                   const float* stats, const float* gscale, float* dpred, int N, int C, int NL, int hw, int min_visibility,
                                   float alpha, float gamma, int soft_label, hipStream_t stream);

@@ -9,45 +9,10 @@ import torch
 
 from cobevt_amd import autograd as ag
 from cobevt_amd import ops
+from carved import BF16, DTYPES, ERR_ARG, ERR_SHAPE, ERR_UNSUPPORTED, F32, U, UB, Carved, _dev, _int_map, _lib, _ok
 from util import assert_close
 
 pytestmark = pytest.mark.gpu
-
-F32, BF16 = torch.float32, torch.bfloat16
-DTYPES = [F32, BF16]
-U = 2.0 ** -24                       # fp32 unit roundoff
-UB = 2.0 ** -8                       # bf16 unit roundoff (8 significant bits): one output rounding
-ERR_ARG, ERR_SHAPE, ERR_UNSUPPORTED = 1, 2, 4          # csrc/common.hpp
-GUARD = 256                          # elements: every carved tensor stays 16-byte aligned
-_INT_VIEW = {torch.float64: torch.int64, torch.float32: torch.int32, torch.bfloat16: torch.int16, torch.int64: torch.int64}
-_INT_SENTINEL = 0x5A5A5A5A5A5A5A5A
-
-
-class Carved(object):
-    """n elements in the middle of a sentinel-filled allocation (NaN for float types; the carved region starts as the sentinel too)"""
-
-    def __init__(self, n, dtype, dev, guard=GUARD, behind=0):
-        self.n, self.guard = n, guard
-        fill = _INT_SENTINEL if dtype == torch.int64 else float("nan")
-        self.big = torch.full((guard + n + guard + behind,), fill, dtype=dtype, device=dev)
-        self.t = self.big[guard:guard + n]
-        self.sentinel = torch.full((1,), fill, dtype=dtype).view(_INT_VIEW[dtype]).item()
-
-    def check(self, what, written=True):
-        """both guard bands bit-identical to the sentinel; the carved region finite (written = True), still the sentinel (False) or
-        free (None: scratch)"""
-        bits = self.big.view(_INT_VIEW[self.big.dtype])
-        g, n = self.guard, self.n
-        assert bool((bits[:g] == self.sentinel).all()), what + ": wrote in front of the buffer"
-        assert bool((bits[g + n:] == self.sentinel).all()), what + ": wrote behind the buffer"
-        if written is None:
-            return self.t
-        if written:
-            if self.big.dtype.is_floating_point:
-                assert bool(torch.isfinite(self.t).all()), what + ": an element that the contract says is written is not finite"
-        else:
-            assert bool((bits[g:g + n] == self.sentinel).all()), what + ": wrote a buffer it must leave alone"
-        return self.t
 
 
 def _scratch(scratch_blocks, rows, c, dev):
@@ -55,19 +20,6 @@ def _scratch(scratch_blocks, rows, c, dev):
     (the library wants one per 8 rows of a thread before the cap)"""
     rstep = max(1, 256 // max(1, c // 8))
     return Carved(scratch_blocks * 2 * c, torch.float64, dev, behind=(rows + rstep - 1) // rstep * 2 * c)
-
-
-def _lib():
-    return ag._L.load()
-
-
-def _dev(dev, *ts):
-    """device copies, to be held by the caller until its launch is enqueued (a temporary's block could be handed out again before)"""
-    return [None if t is None else t.to(dev) for t in ts]
-
-
-def _ok(rc, what):
-    ag._L.check(rc, what)
 
 
 def _group_path(c):
@@ -81,13 +33,6 @@ def _rows_list(c):
         return [1, 255, 1000, 4001]
     rstep = 256 // (c // 8)
     return sorted({1, max(1, rstep - 1), 2 * rstep + 1, min(24 * rstep - 5, 4001), 4001})
-
-
-def _int_map(rows, c, dtype, seed):
-    """integer-valued (rows, C) in [-8, 8] with a distinct offset per channel (neighbouring 8-channel groups differ)"""
-    g = torch.Generator().manual_seed(seed)
-    off = (torch.arange(c) * 7) % 9 - 4
-    return (torch.randint(-4, 5, (rows, c), generator=g) + off).to(dtype)
 
 
 def _channel_sums(dev, x, shift, want_sq, want_f, scratch_blocks):

@@ -12,7 +12,7 @@ from cobevt_amd.lib import CobevtHipError
 from cobevt_amd.synth import fill_module_
 import oracle.fax as o_fax
 import oracle.swap_fusion as o_swap
-from util import assert_close, golden
+from util import assert_close, focal_reference, golden
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-3
@@ -1414,23 +1414,6 @@ def test_swish_depthwise_resize_vs_torch(cuda):
         assert_close(got[1], ref[1], 1e-5, "bilinear resize backward (adjoint)")
 
 
-def _focal_reference(pred, label, vis, label_indices, min_visibility, alpha, gamma):
-    """torch restatement of BinarySegmentationLoss / CenterLoss (nuscenes losses.py:27-84) over fvcore's published sigmoid_focal_loss"""
-    F = torch.nn.functional
-    if label_indices is not None:
-        label = torch.stack([label[:, idx].max(1)[0] for idx in label_indices], 1)
-    p = torch.sigmoid(pred)
-    ce = F.binary_cross_entropy_with_logits(pred, label, reduction="none")
-    pt = p * label + (1 - p) * (1 - label)
-    loss = ce * (1 - pt) ** gamma
-    if alpha >= 0:
-        loss = (alpha * label + (1 - alpha) * (1 - label)) * loss
-    if min_visibility is not None:
-        mask = (vis >= min_visibility)[:, None].expand_as(loss)
-        loss = loss[mask]
-    return loss.mean()
-
-
 def test_sigmoid_focal_losses_backward(cuda):
     """BinarySegmentationLoss (grouped labels, visibility mask, alpha) and CenterLoss (soft labels) of the nuScenes experiments: value and
     gradient w.r.t. the logits against the torch restatement; MultipleLoss sums them and back-propagates"""
@@ -1449,8 +1432,8 @@ def test_sigmoid_focal_losses_backward(cuda):
         total, parts = losses({"bev": pb, "center": pc}, batch)
         total.backward()
         rb, rc = _leaf(pred_bev), _leaf(pred_ctr)
-        ref_b = _focal_reference(rb, label, vis, [[4, 5, 6, 7, 8, 10, 11]], 2, 0.25, 2.0)
-        ref_c = _focal_reference(rc, center, vis, None, 2, -1.0, 2.0)
+        ref_b = focal_reference(rb, label, vis, [[4, 5, 6, 7, 8, 10, 11]], 2, 0.25, 2.0)
+        ref_c = focal_reference(rc, center, vis, None, 2, -1.0, 2.0)
         (ref_b + 0.1 * ref_c).backward()
     assert abs(float(parts["bev"]) - float(ref_b)) <= 1e-5 * max(1.0, abs(float(ref_b)))
     assert abs(float(parts["center"]) - float(ref_c)) <= 1e-5 * max(1.0, abs(float(ref_c)))

@@ -114,3 +114,22 @@ def assert_close(got, ref, tol, what, case=None):
 
 def cfg_copy(cfg):
     return copy.deepcopy(cfg)
+
+
+def focal_reference(pred, label, vis, label_indices, min_visibility, alpha, gamma, reduction="mean"):
+    """torch restatement of BinarySegmentationLoss / CenterLoss (nuscenes losses.py:27-84) over fvcore's published sigmoid_focal_loss,
+    in the type of `pred` (fp32 on the device: torch's own arithmetic; float64 on the CPU: the reference of the kernel-level tests).
+    reduction "sum": the sum over the kept elements instead of their mean."""
+    F = torch.nn.functional
+    if label_indices is not None:
+        label = torch.stack([label[:, idx].max(1)[0] for idx in label_indices], 1)
+    p = torch.sigmoid(pred)
+    ce = F.binary_cross_entropy_with_logits(pred, label, reduction="none")
+    pt = p * label + (1 - p) * (1 - label)
+    loss = ce * (1 - pt) ** gamma
+    if alpha >= 0:
+        loss = (alpha * label + (1 - alpha) * (1 - label)) * loss
+    if min_visibility is not None:
+        mask = (vis >= min_visibility)[:, None].expand_as(loss)
+        loss = loss[mask]
+    return loss.sum() if reduction == "sum" else loss.mean()
