@@ -29,7 +29,8 @@
 //                words of its picked rows into the set in LDS by a butterfly over the lanes; then the range mask, a scan over the
 //                picked flags and the ordered write, zeros past count
 // No floating-point atomics, no workgroup waits on another, no host read-back, no allocation: the workspace comes from the caller
-// (cobevt_detect_scratch).  The same select / mask / greedy launches serve cobevt_nms_rotated (boxes and scores given, no filters).
+// (cobevt_detect_scratch).  The same select / mask / greedy launches serve cobevt_nms_rotated (boxes and scores given, no filters)
+// and cobevt_bev_post (bev_detect.hpp: per-pixel cls / reg maps, its own decode launch, (1000, 4, 2) quads out).
 #include "common.hpp"
 #include "detect_targets.hpp"          // the training side: targets and loss (its entry points are at the end of this file)
 
@@ -53,6 +54,10 @@ struct DetSrc {
     const float* boxes;
     const float* scores;
     int box_floats, n_boxes;
+    // bev mode (bev != 0, bev_detect.hpp): psm = cls (1, 1, H, W), rm = reg (1, 6, H, W), A = 1; the map geometry and the
+    // regression statistics of LidarBevPostprocessor
+    int bev;
+    double bev_x0, bev_y0, bev_res, bev_rate, bev_mean[6], bev_std[6];
 };
 
 // the workspace: the candidate keys (one slot per anchor), the sorted top candidates' corners / scores / indices, the mask, and two
@@ -137,7 +142,17 @@ __device__ __forceinline__ int det_cav_of(const DetSrc& s, int g) {
     return c;
 }
 
+}  // namespace cobevt
+
+#include "bev_detect.hpp"              // the per-pixel (PIXOR) maps: label generation and the bev decode (entry points at the end of this file)
+
+namespace cobevt {
+
 __device__ __forceinline__ void det_decode(const DetSrc& s, int g, float* corners) {
+    if (s.bev) {                                     // uniform: the same bits as the bev decode launch (same function)
+        bev_decode(s, g, corners);
+        return;
+    }
     const int c = det_cav_of(s, g);
     float b[7];
     det_box(s.rm[c], s.anchors[c], s.H[c], s.W[c], s.A[c], g - s.start[c], b);
@@ -374,7 +389,8 @@ __global__ __launch_bounds__(256) void det_mask_kernel(DetWs ws, float thresh) {
 
 // 1024 threads; thread t owns sorted candidate t for the load and for the write
 __global__ __launch_bounds__(1024) void det_greedy_kernel(DetWs ws, float* __restrict__ boxes, float* __restrict__ scores,
-                                                          int* __restrict__ index, int* __restrict__ count, int apply_range) {
+                                                          int* __restrict__ index, int* __restrict__ count, int apply_range,
+                                                          int quad) {
     __shared__ unsigned long long removed[kDetWords];
     __shared__ unsigned long long picked[kDetWords];
     __shared__ int wsum[16];
@@ -448,15 +464,26 @@ __global__ __launch_bounds__(1024) void det_greedy_kernel(DetWs ws, float* __res
         all += v;
     }
     const int pos = before + __popcll(bal & ((1ull << lane) - 1ull));
+    // quad (uniform): boxes is (1000, 4, 2), corners 0 .. 3 in xy; otherwise (1000, 8, 3)
     if (keep) {
+        if (quad) {
 #pragma unroll
-        for (int q = 0; q < 24; ++q) boxes[pos * 24 + q] = co[q];
+            for (int k = 0; k < 4; ++k) { boxes[pos * 8 + 2 * k] = co[k * 3]; boxes[pos * 8 + 2 * k + 1] = co[k * 3 + 1]; }
+        } else {
+#pragma unroll
+            for (int q = 0; q < 24; ++q) boxes[pos * 24 + q] = co[q];
+        }
         scores[pos] = ws.sscore[t];
         index[pos] = ws.sidx[t];
     }
     if (t >= all && t < kDetTop) {                   // rows at and past count: zero
+        if (quad) {
 #pragma unroll
-        for (int q = 0; q < 24; ++q) boxes[t * 24 + q] = 0.f;
+            for (int q = 0; q < 8; ++q) boxes[t * 8 + q] = 0.f;
+        } else {
+#pragma unroll
+            for (int q = 0; q < 24; ++q) boxes[t * 24 + q] = 0.f;
+        }
         scores[t] = 0.f;
         index[t] = 0;
     }
@@ -484,13 +511,16 @@ __global__ __launch_bounds__(256) void det_pair_iou_kernel(const float* __restri
 }
 
 static int det_launch_nms(const DetSrc& s, const DetWs& ws, int total, float nms_thresh, float* boxes, float* scores, int* index,
-                          int* count, int apply_range, hipStream_t stream) {
+                          int* count, int apply_range, int quad, hipStream_t stream) {
     if (hipMemsetAsync(ws.counters, 0, 8, stream) != hipSuccess) return COBEVT_ERR_LAUNCH;
-    if (total > 0)
+    if (total > 0 && s.bev)
+        hipLaunchKernelGGL(bev_decode_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, s, ws, total);
+    else if (total > 0)
         hipLaunchKernelGGL(det_decode_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, s, ws, total);
     hipLaunchKernelGGL(det_select_kernel, dim3(1), dim3(1024), 0, stream, s, ws, total);
     hipLaunchKernelGGL(det_mask_kernel, dim3(kDetWords, (kDetTop + 3) / 4), dim3(256), 0, stream, ws, nms_thresh);
-    hipLaunchKernelGGL(det_greedy_kernel, dim3(1), dim3(1024), 0, stream, ws, boxes, scores, index, count, apply_range);
+    hipLaunchKernelGGL(det_greedy_kernel, dim3(1), dim3(1024), 0, stream, ws, boxes, scores, index, count, apply_range,
+                       quad);
     return cobevt::launch_status();
 }
 
@@ -526,7 +556,7 @@ extern "C" int cobevt_detect_post(const float* const* psm, const float* const* r
     }
     for (int c = ncav; c <= kDetMaxCav; ++c) s.start[c] = (int)total;
     s.matrices = matrices; s.ncav = ncav; s.hwl = hwl != 0; s.score_threshold = score_threshold;
-    return det_launch_nms(s, det_ws(workspace, total), (int)total, nms_thresh, boxes, scores, index, count, 1, stream);
+    return det_launch_nms(s, det_ws(workspace, total), (int)total, nms_thresh, boxes, scores, index, count, 1, 0, stream);
 }
 
 extern "C" int cobevt_nms_rotated(const float* box_corners, const float* box_scores, long N, int corner_floats, float nms_thresh,
@@ -539,7 +569,7 @@ extern "C" int cobevt_nms_rotated(const float* box_corners, const float* box_sco
     // N = 0: the decode launch is skipped and nothing reads the pointer; it only has to select box mode
     s.boxes = box_corners ? box_corners : (const float*)workspace;
     s.scores = box_scores; s.box_floats = corner_floats; s.n_boxes = (int)N;
-    return det_launch_nms(s, det_ws(workspace, N), (int)N, nms_thresh, boxes, scores, index, count, 0, stream);
+    return det_launch_nms(s, det_ws(workspace, N), (int)N, nms_thresh, boxes, scores, index, count, 0, 0, stream);
 }
 
 extern "C" int cobevt_delta_to_boxes3d(const float* rm, const float* anchors, float* boxes3d, int N, int H, int W, int A,
@@ -615,4 +645,48 @@ extern "C" int cobevt_pointpillar_loss(const float* psm, const float* rm, const 
     hipLaunchKernelGGL(ppl_finish_kernel, dim3(1), dim3(256), 0, stream, (const double*)partial, nblk, loss,
                        (double)cls_weight / B, (double)reg / B);
     return cobevt::launch_status();
+}
+
+// ---------------------------------------------------------------------------------------------- per-pixel maps (bev_detect.hpp)
+extern "C" int cobevt_bev_labels(const float* gt_boxes, const float* mask, float* label_map, float* bev_corners, int* num_valid,
+                                 const int* dims, const double* params, hipStream_t stream) {
+    if (!dims || !params || !label_map || !num_valid) return COBEVT_ERR_ARG;
+    const long B = dims[0], G = dims[1], lx = dims[2], ly = dims[3];
+    if (G < 0 || G > kTgtMaxGt) return COBEVT_ERR_SHAPE;
+    if (G > 0 && (!gt_boxes || !mask || !bev_corners)) return COBEVT_ERR_ARG;
+    if (B < 1 || B > 65535 || lx < 1 || ly < 1 || lx > 0x7fffffffL / ly || lx * ly > (0x7fffffffL / 8) / B) return COBEVT_ERR_SHAPE;
+    if (!bev_params_ok(params)) return COBEVT_ERR_SHAPE;
+    BevLabelArgs a;
+    a.B = (int)B; a.G = (int)G; a.lx = (int)lx; a.ly = (int)ly;
+    a.x0 = params[0]; a.y0 = params[1]; a.res = params[2]; a.rate = params[3];
+    for (int k = 0; k < 6; ++k) { a.mean[k] = params[4 + k]; a.std[k] = params[10 + k]; }
+    hipLaunchKernelGGL(bev_labels_kernel, dim3((unsigned)((lx * ly + 255) / 256), (unsigned)B), dim3(256), 0, stream, gt_boxes, mask,
+                       label_map, bev_corners, num_valid, a);
+    return cobevt::launch_status();
+}
+
+extern "C" int cobevt_bev_post(const float* const* cls, const float* const* reg, const float* matrices, const int* cav_dims, int ncav,
+                               const double* params, float score_threshold, float nms_thresh, float* boxes, float* scores, int* index,
+                               int* count, void* workspace, hipStream_t stream) {
+    if (!cls || !reg || !matrices || !cav_dims || !params || !boxes || !scores || !index || !count || !workspace) return COBEVT_ERR_ARG;
+    if (ncav < 1 || ncav > kDetMaxCav) return COBEVT_ERR_SHAPE;
+    if ((uintptr_t)workspace & 7) return COBEVT_ERR_SHAPE;
+    if (!bev_params_ok(params)) return COBEVT_ERR_SHAPE;
+    DetSrc s = {};
+    long total = 0;
+    for (int c = 0; c < ncav; ++c) {
+        const long H = cav_dims[2 * c], W = cav_dims[2 * c + 1];
+        if (!cls[c] || !reg[c]) return COBEVT_ERR_ARG;
+        if (H < 1 || W < 1 || H > 0x7fffffffL / W || H * W > 0x7fffffffL / 8) return COBEVT_ERR_SHAPE;
+        s.psm[c] = cls[c]; s.rm[c] = reg[c];
+        s.H[c] = (int)H; s.W[c] = (int)W; s.A[c] = 1;
+        s.start[c] = (int)total;
+        total += H * W;
+        if (total > 0x7fffffffL / 8) return COBEVT_ERR_SHAPE;
+    }
+    for (int c = ncav; c <= kDetMaxCav; ++c) s.start[c] = (int)total;
+    s.matrices = matrices; s.ncav = ncav; s.score_threshold = score_threshold;
+    s.bev = 1; s.bev_x0 = params[0]; s.bev_y0 = params[1]; s.bev_res = params[2]; s.bev_rate = params[3];
+    for (int k = 0; k < 6; ++k) { s.bev_mean[k] = params[4 + k]; s.bev_std[k] = params[10 + k]; }
+    return det_launch_nms(s, det_ws(workspace, total), (int)total, nms_thresh, boxes, scores, index, count, 1, 1, stream);
 }

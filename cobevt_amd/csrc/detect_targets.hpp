@@ -33,21 +33,30 @@ namespace cobevt {
 constexpr int kTgtMaxGt = 128;
 
 // ---------------------------------------------------------------------------------------------- standup boxes
+// footprint corner k = 0 .. 3 of boxes_to_corners_3d: half sizes (sx, sy) along the box axes, the template [1,-1] [1,1] [-1,1] [-1,-1] / 2,
+// rotate_points_along_z: [x y] [[cos, sin], [-sin, cos]], then the centre - every product and sum a separately rounded fp32 operation.
+// The caller gives cos / sin of the yaw (tgt_standup_kernel: cosf / sinf; bev_detect.hpp: the fp64 functions rounded to fp32).
+__device__ __forceinline__ void box_footprint_corner(int k, float cx, float cy, float sx, float sy, float cs, float sn, float& X,
+                                                     float& Y) {
+#pragma clang fp contract(off)
+    const float x = k < 2 ? sx : -sx, y = (k == 1 || k == 2) ? sy : -sy;
+    X = (x * cs + y * -sn) + cx;
+    Y = (x * sn + y * cs) + cy;
+}
+
 __global__ __launch_bounds__(256) void tgt_standup_kernel(const float* __restrict__ boxes, float* __restrict__ out, long n) {
 #pragma clang fp contract(off)
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const float* b = boxes + i * 7;
-    // boxes_to_corners_3d with order 'hwl': the size columns read as [5, 4, 3]; template corners 0 .. 3 [1,-1] [1,1] [-1,1] [-1,-1] / 2
+    // boxes_to_corners_3d with order 'hwl': the size columns read as [5, 4, 3]
     const float sx = b[5] * 0.5f, sy = b[4] * 0.5f;
     const float cs = cosf(b[6]), sn = sinf(b[6]);
     float x1 = 0.f, y1 = 0.f, x2 = 0.f, y2 = 0.f;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        const float x = k < 2 ? sx : -sx, y = (k == 1 || k == 2) ? sy : -sy;
-        // rotate_points_along_z: [x y] [[cos, sin], [-sin, cos]], then the centre
-        const float X = (x * cs + y * -sn) + b[0];
-        const float Y = (x * sn + y * cs) + b[1];
+        float X, Y;
+        box_footprint_corner(k, b[0], b[1], sx, sy, cs, sn, X, Y);
         x1 = k ? fminf(x1, X) : X; x2 = k ? fmaxf(x2, X) : X;
         y1 = k ? fminf(y1, Y) : Y; y2 = k ? fmaxf(y2, Y) : Y;
     }

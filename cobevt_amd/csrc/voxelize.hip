@@ -23,6 +23,7 @@
 //                NOT written.
 // No floating-point atomics, no host read-back, no allocation: the workspace comes from the caller (cobevt_voxelize_scratch).
 #include "common.hpp"
+#include "bev_points.hpp"              // the offsets / mask device functions, and points -> bev_input (its entry points are at the end of this file)
 
 namespace cobevt {
 
@@ -56,8 +57,6 @@ static VoxelWs voxel_ws(int* w, const VoxelArgs& a) {
     s.part = s.bucket + a.M; s.agent_part = s.part + 2 * (scan_blocks(a.M) + 1);
     return s;
 }
-
-__device__ __forceinline__ long clamp_offset(int o, long M) { return o < 0 ? 0 : (o > M ? M : (long)o); }
 
 // value of lane (lane ^ X) of the same 32-lane group (ds_swizzle bit mode: and 0x1f, or 0, xor X)
 template <int X> __device__ __forceinline__ int swz_xor_i(int v) { return __builtin_amdgcn_ds_swizzle(v, (X << 10) | 0x1f); }
@@ -120,16 +119,11 @@ __global__ __launch_bounds__(256) void voxel_classify_kernel(const float4* __res
                                                              VoxelArgs a) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= a.M) return;
-    int agent = -1;
-    for (int k = 0; k < a.N; ++k)
-        if (agent < 0 && i >= clamp_offset(offsets[k], a.M) && i < clamp_offset(offsets[k + 1], a.M)) agent = k;
+    const int agent = point_agent(offsets, a.N, i, a.M);
     int cell = -1;
     if (agent >= 0) {
         const float4 p = points[i];
-        bool keep = isfinite(p.x) && isfinite(p.y) && isfinite(p.z);
-        if (a.range_mask)
-            keep = keep && p.x > a.lo[0] && p.x < a.hi[0] && p.y > a.lo[1] && p.y < a.hi[1] && p.z > a.lo[2] && p.z < a.hi[2];
-        if (a.ego_mask) keep = keep && !(p.x >= -1.95f && p.x <= 2.95f && p.y >= -1.1f && p.y <= 1.1f);
+        bool keep = isfinite(p.x) && isfinite(p.y) && isfinite(p.z) && point_masks_keep(p, a.lo, a.hi, a.range_mask, a.ego_mask);
         // floor((p - lo) / v) with the rounded subtract and divide, compared as floats (a quotient past the int range drops the point)
         const float cx = floorf(__fdiv_rn(__fsub_rn(p.x, a.lo[0]), a.v[0]));
         const float cy = floorf(__fdiv_rn(__fsub_rn(p.y, a.lo[1]), a.v[1]));
@@ -331,5 +325,39 @@ extern "C" int cobevt_voxelize_points(const float* points, const int* point_offs
     if (pb) hipLaunchKernelGGL(voxel_fill_kernel, dim3(pb), dim3(256), 0, stream, s, a.M);
     hipLaunchKernelGGL(voxel_select_kernel, dim3((unsigned)((a.Pcap + 7) / 8)), dim3(256), 0, stream, (const uint4*)points, s,
                        (uint4*)voxel_features, (int4*)voxel_coords, voxel_num_points, a);
+    return cobevt::launch_status();
+}
+
+// ---------------------------------------------------------------------------------------------- points -> bev_input (bev_points.hpp)
+extern "C" int cobevt_bev_points_scratch(const long* dims, long* workspace_ints) {
+    BevPointArgs a;
+    if (!workspace_ints) return COBEVT_ERR_ARG;
+    const int rc = bev_points_args(dims, nullptr, a);
+    if (rc != COBEVT_OK) return rc;
+    *workspace_ints = bev_points_ws_ints(a);
+    return COBEVT_OK;
+}
+
+extern "C" int cobevt_bev_points(const float* points, const int* point_offsets, float* bev, int* workspace, const long* dims,
+                                 const double* geom, hipStream_t stream) {
+    if (!dims || !geom || !point_offsets || !bev || !workspace) return COBEVT_ERR_ARG;
+    BevPointArgs a;
+    const int rc = bev_points_args(dims, geom, a);
+    if (rc != COBEVT_OK) return rc;
+    if (a.M > 0 && !points) return COBEVT_ERR_ARG;
+    if (((uintptr_t)points & 15) || ((uintptr_t)workspace & 7) || ((uintptr_t)bev & 3)) return COBEVT_ERR_SHAPE;
+    if (!(a.res > 0.0) || a.res - a.res != 0.0) return COBEVT_ERR_SHAPE;              // positive and finite
+    for (int j = 0; j < 3; ++j)
+        if (a.origin[j] - a.origin[j] != 0.0) return COBEVT_ERR_SHAPE;
+    const long cells = (long)a.N * a.nx * a.ny;
+    unsigned long long* sum = (unsigned long long*)workspace;
+    int* count = workspace + 2 * cells;
+    if (hipMemsetAsync(bev, 0, 4 * (size_t)cells * a.C, stream) != hipSuccess) return COBEVT_ERR_LAUNCH;
+    if (hipMemsetAsync(workspace, 0, 12 * (size_t)cells, stream) != hipSuccess) return COBEVT_ERR_LAUNCH;
+    const unsigned pb = (unsigned)((a.M + 255) / 256);         // one thread per point
+    if (pb)
+        hipLaunchKernelGGL(bev_points_kernel, dim3(pb), dim3(256), 0, stream, (const float4*)points, point_offsets, bev, sum, count, a);
+    hipLaunchKernelGGL(bev_points_finalise_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, stream, bev,
+                       (const unsigned long long*)sum, (const int*)count, a);
     return cobevt::launch_status();
 }

@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get("COBEVT_HIP_LIB") or LIB_PATH
 _c_int_p = ctypes.POINTER(ctypes.c_int)
 _c_long_p = ctypes.POINTER(ctypes.c_long)
 _c_float_p = ctypes.POINTER(ctypes.c_float)
+_c_double_p = ctypes.POINTER(ctypes.c_double)
 _vp = ctypes.c_void_p
 
 # name -> (restype, argtypes); must list every symbol of include/cobevt_hip.h
@@ -158,6 +159,11 @@ SIGNATURES = {
     "cobevt_boxes_standup": (ctypes.c_int, [_vp, _vp, ctypes.c_long, _vp]),
     "cobevt_detect_targets": (ctypes.c_int, [_vp] * 5 + [ctypes.c_float, ctypes.c_float] + [_vp] * 5 + [ctypes.c_int] * 5 + [_vp]),
     "cobevt_pointpillar_loss": (ctypes.c_int, [_vp] * 9 + [ctypes.c_int] * 4 + [ctypes.c_float, ctypes.c_float, _vp]),
+    "cobevt_bev_points_scratch": (ctypes.c_int, [_c_long_p, _c_long_p]),
+    "cobevt_bev_points": (ctypes.c_int, [_vp] * 4 + [_c_long_p, _c_double_p, _vp]),
+    "cobevt_bev_labels": (ctypes.c_int, [_vp] * 5 + [_c_int_p, _c_double_p, _vp]),
+    "cobevt_bev_post": (ctypes.c_int, [ctypes.POINTER(_vp)] * 2 + [_vp, _c_int_p, ctypes.c_int, _c_double_p, ctypes.c_float,
+                                       ctypes.c_float] + [_vp] * 5 + [_vp]),
 }
 
 _libs = {}

@@ -1492,6 +1492,175 @@ def detect_post_process(cavs, score_threshold, nms_thresh, order, out=None, work
 
 DETECT_MAX_GT = 128        # ground-truth slots per sample cobevt_detect_targets takes (the reference's max_num is 100)
 
+# ----------------------------------------------------------------------------------------------
+# LiDAR BEV maps, the PIXOR formulation (csrc/bev_points.hpp, csrc/bev_detect.hpp)
+# ----------------------------------------------------------------------------------------------
+BEV_TARGET_MEAN = (0.008, 0.001, 0.202, 0.2, 0.43, 1.368)          # lidar_bev_postprocessor.py :24-25
+BEV_TARGET_STD_DEV = (0.866, 0.5, 0.954, 0.668, 0.09, 0.111)
+_BEV_WS = {}               # (device, dims) -> bev_points' int32 workspace, one per shape as for voxelize_points
+
+
+def _bev_shape(shape, last, what):
+    s = tuple(int(v) for v in shape) if np.ndim(shape) == 1 else ()
+    if len(s) != 3 or s[0] < 1 or s[1] < 1 or (last is not None and s[2] != last) or s[2] < 2:
+        raise CobevtHipError("%s must be (nx, ny, %s) with nx, ny >= 1, got %r" % (what, "C >= 2" if last is None else last, shape))
+    return s
+
+
+def _bev_params(origin_xy, res, downsample_rate, target_mean, target_std_dev, what):
+    """the 16 doubles [L1, W1, res, downsample_rate, target_mean (6), target_std_dev (6)] of cobevt_bev_labels / cobevt_bev_post"""
+    vals = [float(origin_xy[0]), float(origin_xy[1]), float(res), float(downsample_rate)]
+    mean, std = [float(v) for v in np.asarray(target_mean).reshape(-1)], [float(v) for v in np.asarray(target_std_dev).reshape(-1)]
+    if len(mean) != 6 or len(std) != 6 or not all(np.isfinite(vals + mean + std)) or any(v == 0.0 for v in std):
+        raise CobevtHipError("%s: target_mean and target_std_dev are 6 finite values each, no zero deviation" % what)
+    if not (vals[2] > 0.0 and vals[3] > 0.0):
+        raise CobevtHipError("%s: res and downsample_rate must be positive, got %r and %r" % (what, res, downsample_rate))
+    return (ctypes.c_double * 16)(*(vals + mean + std))
+
+
+def bev_points_workspace_ints(num_points, num_agents, input_shape):
+    """int32 elements of bev_points' workspace for M points of N agents on an (nx, ny, C) map (cobevt_bev_points_scratch)"""
+    dims = (ctypes.c_long * 8)(int(num_points), int(num_agents), int(input_shape[0]), int(input_shape[1]), int(input_shape[2]), 0, 0, 0)
+    need = ctypes.c_long(0)
+    _L.call("cobevt_bev_points_scratch", dims, ctypes.byref(need))
+    return need.value
+
+
+def bev_points(points, point_offsets, lidar_range, origin, res, input_shape, range_mask=False, ego_mask=False, channels_last=False,
+               out=None, workspace=None):
+    """BevPreprocessor.preprocess for N agents, on the device and without a host synchronisation (csrc/bev_points.hpp).
+    points (M, 4) contiguous fp32 [x, y, z, intensity] and point_offsets (N + 1,) int32 / int64 on the device, as voxelize_points
+    takes them; lidar_range = cav_lidar_range (used by range_mask only), origin = (L1, W1, H1), res the cell size, input_shape =
+    (nx, ny, C).  -> bev_input (N, C, nx, ny) fp32, or (N, nx, ny, C) with channels_last: channels 0 .. C - 2 the binary occupancy of
+    the height slices at trunc(((double)p - origin) / res), channel C - 1 the mean intensity of the cell's points.  Dropped: points
+    with a non-finite value, |intensity| >= 256, removed by a mask, or outside [0, nx) x [0, ny) x [0, C - 1) (the reference wraps or
+    misplaces those).  Integer atomics only: bitwise identical under any permutation of the points; |mean error| <= 2^-33 + 2^-24 |mean|.
+    out = the tensor to write into (the call clears it); workspace = an int32 tensor of at least bev_points_workspace_ints(...)
+    elements whose storage is 8-byte aligned (default: one cached per shape and device)."""
+    _need_cuda(points, point_offsets, out, workspace)
+    if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 4 or not points.is_contiguous():
+        raise CobevtHipError("bev_points: points must be contiguous fp32 (M, 4) as [x, y, z, intensity], got %s %s"
+                             % (points.dtype, tuple(points.shape)))
+    offs = _index_i32(point_offsets, "bev_points: point_offsets")
+    if offs.dim() != 1 or offs.shape[0] < 2:
+        raise CobevtHipError("bev_points: point_offsets must be (N + 1,) with N >= 1 agents, got %s" % (tuple(offs.shape),))
+    nx, ny, c = _bev_shape(input_shape, None, "bev_points: input_shape")
+    rng, org = [float(v) for v in lidar_range], [float(v) for v in origin]
+    if len(rng) != 6 or len(org) != 3 or not all(np.isfinite(rng + org)) or not (float(res) > 0.0 and np.isfinite(float(res))):
+        raise CobevtHipError("bev_points: lidar_range = [x0, y0, z0, x1, y1, z1], origin = (L1, W1, H1) and res > 0, got %r / %r / %r"
+                             % (list(lidar_range), list(origin), res))
+    n, m, dev = offs.shape[0] - 1, points.shape[0], points.device
+    if n * nx * ny * c > 0x7fffffff // 4:
+        raise CobevtHipError("bev_points: %d agents of %d x %d x %d cells are more than the operator indexes" % (n, nx, ny, c))
+    dims = (ctypes.c_long * 8)(m, n, nx, ny, c, int(bool(range_mask)), int(bool(ego_mask)), int(bool(channels_last)))
+    geom = (ctypes.c_double * 10)(*(rng + org + [float(res)]))
+    need = bev_points_workspace_ints(m, n, (nx, ny, c))
+    if workspace is None:
+        key = (dev, n, nx, ny)
+        workspace = _BEV_WS.get(key)
+        if workspace is None:
+            workspace = _BEV_WS[key] = torch.empty((need + 1) // 2, device=dev, dtype=torch.int64).view(torch.int32)
+    elif workspace.dtype != torch.int32 or not workspace.is_contiguous() or workspace.numel() < need or workspace.device != dev \
+            or workspace.data_ptr() % 8:
+        raise CobevtHipError("bev_points: workspace= must be a contiguous, 8-byte aligned int32 tensor of at least %d elements on %s"
+                             % (need, dev))
+    bev = _canvas(out, (n, nx, ny, c) if channels_last else (n, c, nx, ny), torch.float32, dev, "bev_points")
+    with _timed("bev_points|M%d N%d %dx%dx%d" % (m, n, nx, ny, c), lambda: (0.0, 16.0 * m + 12.0 * m + 4.0 * n * nx * ny * (c + 6))):
+        _L.call("cobevt_bev_points", _p(points) if m else None, _p(offs), _p(bev), _p(workspace), dims, geom, _stream())
+    return bev
+
+
+def bev_labels(gt_box_center, mask, origin_xy, res, downsample_rate, label_shape, target_mean=BEV_TARGET_MEAN,
+               target_std_dev=BEV_TARGET_STD_DEV, out=None):
+    """LidarBevPostprocessor.generate_label for a batch, on the device and without a synchronisation (csrc/bev_detect.hpp).
+    gt_box_center (B, max_num, 7) in 'lwh' order and mask (B, max_num), contiguous fp32 on the device, max_num <= 128; origin_xy =
+    (L1, W1); label_shape = (lx, ly, 7).  -> label_map (B, 7, lx, ly) fp32, bev_corners (B, max_num, 4, 2) fp32 (valid boxes compacted
+    to the front in order, zero rows behind them) and num_valid (B,) int32.  Where boxes overlap the last valid one wins; channels
+    1 .. 6 of every pixel are normalised; a box with an edge of squared norm <= 1e-6 marks no pixel - see cobevt_hip.h.  One launch;
+    it needs no workspace.  out = the three tensors to write into."""
+    lx, ly, _ = _bev_shape(label_shape, 7, "bev_labels: label_shape")
+    if gt_box_center.dim() != 3 or gt_box_center.shape[2] != 7:
+        raise CobevtHipError("bev_labels: gt_box_center must be (B, max_num, 7), got %s" % (tuple(gt_box_center.shape),))
+    b, g = gt_box_center.shape[:2]
+    if g > DETECT_MAX_GT:
+        raise CobevtHipError("bev_labels: at most %d ground-truth slots per sample are supported, got %d" % (DETECT_MAX_GT, g))
+    if b < 1 or b > 65535 or b * lx * ly > 0x7fffffff // 8:
+        raise CobevtHipError("bev_labels: %d samples of %d x %d pixels are outside what the operator indexes" % (b, lx, ly))
+    _dev_f32(gt_box_center, "bev_labels: gt_box_center")
+    _dev_f32(mask, "bev_labels: mask", (b, g))
+    params = _bev_params(origin_xy, res, downsample_rate, target_mean, target_std_dev, "bev_labels")
+    dev = gt_box_center.device
+    shapes = [((b, 7, lx, ly), torch.float32), ((b, g, 4, 2), torch.float32), ((b,), torch.int32)]
+    if out is None:
+        out = [None] * 3
+    elif len(out) != 3:
+        raise CobevtHipError("bev_labels: out= is (label_map, bev_corners, num_valid)")
+    _need_cuda(*out)
+    label_map, corners, num_valid = [_canvas(o, s, d, dev, "bev_labels") for o, (s, d) in zip(out, shapes)]
+    gp = (lambda t: _p(t) if g else None)
+    with _timed("bev_labels|B%d G%d %dx%d" % (b, g, lx, ly), lambda: (0.0, 28.0 * b * lx * ly + 60.0 * b * g)):
+        _L.call("cobevt_bev_labels", gp(gt_box_center), gp(mask), _p(label_map), gp(corners), _p(num_valid), _ints([b, g, lx, ly]), params,
+                _stream())
+    return label_map, corners, num_valid
+
+
+def _bev_post_out(out, dev):
+    shapes = [((DETECT_TOP, 4, 2), torch.float32), ((DETECT_TOP,), torch.float32), ((DETECT_TOP,), torch.int32), ((1,), torch.int32)]
+    if out is None:
+        out = [None] * 4
+    elif len(out) != 4:
+        raise CobevtHipError("bev_post_process: out= is (boxes, scores, index, count)")
+    return [_canvas(o, sh, d, dev, "bev_post_process") for o, (sh, d) in zip(out, shapes)]
+
+
+def bev_post_process(cavs, origin_xy, res, downsample_rate, score_threshold, nms_thresh, target_mean=BEV_TARGET_MEAN,
+                     target_std_dev=BEV_TARGET_STD_DEV, out=None, workspace=None):
+    """LidarBevPostprocessor.post_process on the device, without a synchronisation (csrc/bev_detect.hpp + csrc/detect_post.hip).
+    cavs: a sequence of 1 .. 16 (cls, reg, transformation_matrix): cls (1, 1, lx, ly) and reg (1, 6, lx, ly) contiguous fp32 on the
+    device, the 4 x 4 matrix a tensor or array (converted to fp32 on the device; give device tensors to capture the call in a graph).
+    -> boxes (1000, 4, 2) fp32, scores (1000) fp32, index (1000) int32 (global pixel index: cav 0's pixels in (i, j) order, then cav
+    1's, ...), count (1) int32, in pick order; rows at and past count are zero.  Candidates are the pixels with sigmoid(cls) >
+    score_threshold and finite decoded values; the 1000 best of all cavs, rotated NMS (iou > nms_thresh), then the GT_RANGE mask on
+    the four corners - see cobevt_hip.h.  out = the four tensors to write into; workspace = an int64 tensor of
+    detect_workspace_bytes(total pixels) bytes."""
+    cavs = list(cavs)
+    if not 1 <= len(cavs) <= DETECT_MAX_CAV:
+        raise CobevtHipError("bev_post_process: 1 .. %d cavs are supported, got %d" % (DETECT_MAX_CAV, len(cavs)))
+    params = _bev_params(origin_xy, res, downsample_rate, target_mean, target_std_dev, "bev_post_process")
+    keep, dims, mats, total = [], [], [], 0
+    dev = None
+    for c, cav in enumerate(cavs):
+        if len(cav) != 3:
+            raise CobevtHipError("bev_post_process: cav %d must be (cls, reg, transformation_matrix)" % c)
+        cls, reg, mat = cav
+        _need_cuda(cls, reg)
+        dev = cls.device if dev is None else dev
+        if cls.device != dev or reg.device != dev:
+            raise CobevtHipError("bev_post_process: cav %d is on another device" % c)
+        if reg.dtype != torch.float32 or reg.dim() != 4 or reg.shape[0] != 1 or reg.shape[1] != 6 or not reg.is_contiguous() \
+                or reg.shape[2] < 1 or reg.shape[3] < 1:
+            raise CobevtHipError("bev_post_process: reg of cav %d must be contiguous fp32 (1, 6, lx, ly), got %s %s"
+                                 % (c, reg.dtype, tuple(reg.shape)))
+        lx, ly = reg.shape[2:]
+        if cls.dtype != torch.float32 or tuple(cls.shape) != (1, 1, lx, ly) or not cls.is_contiguous():
+            raise CobevtHipError("bev_post_process: cls of cav %d must be contiguous fp32 %s, got %s %s"
+                                 % (c, (1, 1, lx, ly), cls.dtype, tuple(cls.shape)))
+        mats.append(_f32_dev(mat, dev, "bev_post_process: transformation_matrix of cav %d" % c, (4, 4)))
+        keep.append((cls, reg))
+        dims += [lx, ly]
+        total += lx * ly
+    if total > 0x7fffffff // 8:
+        raise CobevtHipError("bev_post_process: %d pixels are more than the operator indexes" % total)
+    matrices = mats[0].reshape(1, 4, 4) if len(mats) == 1 else torch.stack(mats)
+    ws = _detect_workspace(workspace, total, dev, "bev_post_process")
+    ob, osc, oi, oc = _bev_post_out(out, dev)
+    ptrs = [(ctypes.c_void_p * len(cavs))(*[k[j].data_ptr() for k in keep]) for j in range(2)]
+    cost = lambda: (0.0, 36.0 * total + 8.0 * DETECT_TOP * 16 + 100.0 * DETECT_TOP)         # noqa: E731
+    with _timed("bev_post|cavs%d N%d" % (len(cavs), total), cost):
+        _L.call("cobevt_bev_post", ptrs[0], ptrs[1], _p(matrices), _ints(dims), len(cavs), params, float(score_threshold),
+                float(nms_thresh), _p(ob), _p(osc), _p(oi), _p(oc), _p(ws), _stream())
+    return ob, osc, oi, oc
+
 
 def _dev_f32(t, what, shape=None, dims=None):
     """a contiguous fp32 device tensor as it stands, or an error: the target / loss operators convert nothing"""

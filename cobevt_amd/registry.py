@@ -1,6 +1,9 @@
 """create_model / create_loss — the reference's registry contracts (opv2v/opencood/tools/train_utils.py:102-135 and
 :138-170): hypes['model' | 'loss']['core_method'] names a module, the class whose lower-cased name equals the name without
-underscores is instantiated with hypes[...]['args']."""
+underscores is instantiated with hypes[...]['args'].
+
+build_preprocessor / build_postprocessor — the registries of opv2v/opencood/data_utils/pre_processor/__init__.py and
+post_processor/__init__.py: cfg['core_method'] names the class under the reference's own names."""
 import importlib
 
 
@@ -48,3 +51,30 @@ def create_model(hypes):
                          "required (FAX hot path models: corpbevt, fax_fused_transformer)"
                          % (backbone_name, target_model_name))
     return model(backbone_config)
+
+
+_PREPROCESSORS = {"BevPreprocessor": ("bev_preprocessor", "BevPreprocessor"),
+                  "SpVoxelPreprocessor": ("sp_voxel_preprocessor", "SpVoxelPreprocessor"),
+                  "RgbPreprocessor": ("rgb_preprocessor", "RgbPreProcessor")}
+_POSTPROCESSORS = {"BevPostprocessor": ("lidar_bev_postprocessor", "LidarBevPostprocessor"),
+                   "VoxelPostprocessor": ("voxel_postprocessor", "VoxelPostprocessor"),
+                   "CameraBevPostprocessor": ("camera_bev_postprocessor", "CameraBevPostprocessor")}
+
+
+def _build(table, name, what):
+    if name not in table:
+        # the reference asserts; an unknown name is an error here
+        raise ValueError("%s %r is not found: known are %s" % (what, name, ", ".join(sorted(table))))
+    module, cls = table[name]
+    return getattr(importlib.import_module("cobevt_amd.host." + module), cls)
+
+
+def build_preprocessor(preprocess_cfg, train):
+    """preprocess_cfg['core_method'] in BevPreprocessor / SpVoxelPreprocessor / RgbPreprocessor -> the instance"""
+    return _build(_PREPROCESSORS, preprocess_cfg["core_method"], "preprocessor")(preprocess_params=preprocess_cfg, train=train)
+
+
+def build_postprocessor(anchor_cfg, train):
+    """anchor_cfg['core_method'] in BevPostprocessor (LidarBevPostprocessor) / VoxelPostprocessor / CameraBevPostprocessor -> the
+    instance"""
+    return _build(_POSTPROCESSORS, anchor_cfg["core_method"], "postprocessor")(anchor_params=anchor_cfg, train=train)

@@ -947,6 +947,60 @@ int cobevt_pointpillar_loss(const float* psm, const float* rm, const float* pos_
                             float* loss, float* dpsm, float* drm, void* workspace, int B, int H, int W, int A, float cls_weight,
                             float reg, hipStream_t stream);
 
+/*
+ * LiDAR BEV maps, the PIXOR formulation: OpenCOOD's BevPreprocessor (csrc/bev_points.hpp, compiled into voxelize) and
+ * LidarBevPostprocessor (csrc/bev_detect.hpp, compiled into detect_post).  Identical in every library.  No timing of these entry
+ * points has been measured yet.
+ *
+ * cobevt_bev_points: points (M, 4) fp32 [x, y, z, intensity] of N agents and point_offsets (N + 1) int32 ON THE DEVICE, with the
+ *   conventions of cobevt_voxelize_points (rows at or past offsets[N] are ignored) -> bev (N, C, nx, ny) fp32, or (N, nx, ny, C) when
+ *   channels_last is set: channels 0 .. C - 2 the binary occupancy of the height slices, channel C - 1 the mean intensity.
+ *   dims = [M, N, nx, ny, C, range_mask, ego_mask, channels_last] (host), C >= 2;
+ *   geom = [x0, y0, z0, x1, y1, z1 (cav_lidar_range, for range_mask), L1, W1, H1, res] (host, DOUBLES).
+ *   Index per axis: trunc(((double)p - origin) / res) - fp64 on the fp32 point, truncation toward zero, not floor: a point in
+ *   (origin - res, origin) falls into cell 0.  Skip rules: a point is dropped when a coordinate or its intensity is not finite, when
+ *   |intensity| >= 2^8, when a mask removes it (same rules as cobevt_voxelize_points) or when its index is outside [0, nx) x [0, ny)
+ *   x [0, C - 1) - a deliberate deviation: the reference wraps negative indices and writes iz = C - 1 into the intensity channel.
+ *   Every kept point sets bev[ix, iy, iz] = 1; the intensity channel is the mean intensity of the cell's kept points, 0 without one.
+ *   Order independence: per cell a 32-bit count and a 64-bit fixed-point sum (quantum 2^-32) in separate arrays, integer atomics
+ *   only, then a finalise pass that divides in fp64 and rounds to fp32 once.  Intensities with 2^-9 <= |i| < 2^8 are summed exactly,
+ *   smaller ones with a per-point error <= 2^-33: |out - mean| <= 2^-33 + 2^-24 |mean| (1 + 2^-20).  Bitwise identical under any
+ *   permutation of the points and from run to run.  Two memset nodes (bev, workspace) and two launches (points, finalise; M = 0: one);
+ *   no host read, no allocation.  workspace: cobevt_bev_points_scratch(dims) ints, 8-byte aligned, contents irrelevant on entry;
+ *   points 16-byte aligned.
+ *
+ * cobevt_bev_labels: LidarBevPostprocessor.generate_label for a batch.  gt_boxes (B, G, 7) fp32 in 'lwh' order, mask (B, G) fp32
+ *   (valid when == 1), G <= 128 (more: code 2; G = 0 is valid) -> label_map (B, 7, lx, ly) fp32, bev_corners (B, G, 4, 2) fp32 (valid
+ *   boxes compacted to the front in slot order, zero rows behind them) and num_valid (B) int32.  dims = [B, G, lx, ly] (host);
+ *   params = [L1, W1, res, downsample_rate, target_mean (6), target_std_dev (6)] (host, doubles; res, rate > 0, std != 0).
+ *   Corners 0 .. 3 of boxes_to_corners_3d in separately rounded fp32 (cos / sin: the fp64 functions rounded to fp32); everything
+ *   after that in fp64 in the reference's operation order: pixel (i, j) belongs to a box when (p_rel . e) / (e . e) is in [0, 1]
+ *   inclusive for both edges c1 - c0 and c3 - c0 of the corners in label-pixel units; targets [1, cos yaw, sin yaw, x - px, y - py,
+ *   log dx, log dy] with (px, py) from dist_to_continuous.  Tie rule: where boxes overlap the LAST valid box wins.  Channels 1 .. 6 of
+ *   every pixel, background included, are (v - mean) / std; one cast to fp32.  Skip rule: a box with an edge of squared norm <= 1e-6
+ *   (the reference asserts) marks no pixel.  One launch, no atomics, no host read, no allocation.
+ *
+ * cobevt_bev_post: LidarBevPostprocessor.post_process.  cls, reg: HOST arrays of ncav (1 .. 16) DEVICE pointers - cav c's cls
+ *   (1, 1, lx, ly) and reg (1, 6, lx, ly) fp32; matrices (ncav, 4, 4) fp32 ON THE DEVICE; cav_dims = [lx, ly] per cav (host); params as
+ *   for cobevt_bev_labels.  prob = sigmoid(cls) in fp32; a pixel is a candidate when prob > score_threshold and every decoded value
+ *   is finite.  reg * std + mean, atan2, exp, the cell centre (float)(L1 + i res rate) + x and the corner template are fp64; the
+ *   rotation, the `+= centre` (one fp64 add rounded to fp32) and the projection by the cav's matrix are rounded to fp32 where the
+ *   reference rounds.  Then cobevt_detect_post's own select + sort, mask and greedy launches: the 1000 best of all cavs (equal
+ *   scores: lower global pixel index first), suppression when (float)iou > nms_thresh, and the GT_RANGE test on the four corners, x
+ *   in [-140, 140] and y in [-40, 40], after suppression.  Outputs in pick order: boxes (1000, 4, 2), scores (1000), index (1000) =
+ *   the global pixel index (cav 0's pixels in (i, j) order, then cav 1's), count (1); rows at and past count are zero.  One 8-byte
+ *   memset node and four launches (bev decode, select + sort, mask, greedy); integer atomics only, no host read, no allocation,
+ *   bitwise reproducible.  workspace: cobevt_detect_scratch(total pixels) BYTES, 8-byte aligned.  Skip rules: none.
+ */
+int cobevt_bev_points_scratch(const long* dims, long* workspace_ints);
+int cobevt_bev_points(const float* points, const int* point_offsets, float* bev, int* workspace, const long* dims, const double* geom,
+                      hipStream_t stream);
+int cobevt_bev_labels(const float* gt_boxes, const float* mask, float* label_map, float* bev_corners, int* num_valid, const int* dims,
+                      const double* params, hipStream_t stream);
+int cobevt_bev_post(const float* const* cls, const float* const* reg, const float* matrices, const int* cav_dims, int ncav,
+                    const double* params, float score_threshold, float nms_thresh, float* boxes, float* scores, int* index, int* count,
+                    void* workspace, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
