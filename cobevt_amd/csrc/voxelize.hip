@@ -24,6 +24,7 @@
 // No floating-point atomics, no host read-back, no allocation: the workspace comes from the caller (cobevt_voxelize_scratch).
 #include "common.hpp"
 #include "bev_points.hpp"              // the offsets / mask device functions, and points -> bev_input (its entry points are at the end of this file)
+#include "cloud_prep.hpp"              // sensor-frame clouds -> one compact ego-frame cloud, in front of both (entry points at the end)
 
 namespace cobevt {
 
@@ -359,5 +360,43 @@ extern "C" int cobevt_bev_points(const float* points, const int* point_offsets, 
         hipLaunchKernelGGL(bev_points_kernel, dim3(pb), dim3(256), 0, stream, (const float4*)points, point_offsets, bev, sum, count, a);
     hipLaunchKernelGGL(bev_points_finalise_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, stream, bev,
                        (const unsigned long long*)sum, (const int*)count, a);
+    return cobevt::launch_status();
+}
+
+// ---------------------------------------------------------------------------------------------- raw clouds -> ego-frame cloud (cloud_prep.hpp)
+extern "C" int cobevt_prepare_points_scratch(const long* dims, long* workspace_ints) {
+    CloudArgs a;
+    if (!workspace_ints) return COBEVT_ERR_ARG;
+    const int rc = cloud_args(dims, nullptr, a);
+    if (rc != COBEVT_OK) return rc;
+    *workspace_ints = cloud_ws_ints(a.M);
+    return COBEVT_OK;
+}
+
+extern "C" int cobevt_prepare_points(const float* points, const int* point_offsets, const double* transforms, const int* order, float* out,
+                                     int* out_offsets, void* boxes, const void* box_mask, int* workspace, const long* dims,
+                                     const double* geom, hipStream_t stream) {
+    if (!dims || !geom || !point_offsets || !out_offsets || !workspace) return COBEVT_ERR_ARG;
+    CloudArgs a;
+    const int rc = cloud_args(dims, geom, a);
+    if (rc != COBEVT_OK) return rc;
+    if (a.M > 0 && (!points || !out)) return COBEVT_ERR_ARG;
+    if (a.G > 0 && (!boxes || !box_mask)) return COBEVT_ERR_ARG;
+    if ((((uintptr_t)points | (uintptr_t)out) & 15) || (((uintptr_t)workspace | (uintptr_t)transforms | (uintptr_t)boxes | (uintptr_t)box_mask) & 7))
+        return COBEVT_ERR_SHAPE;
+    if (((uintptr_t)order | (uintptr_t)point_offsets | (uintptr_t)out_offsets) & 3) return COBEVT_ERR_SHAPE;
+    a.project = transforms != nullptr;
+    a.ordered = order != nullptr;
+    const long nb = cloud_blocks(a.M);
+    unsigned long long* flags = (unsigned long long*)workspace;
+    int* part = workspace + 2 * ((a.M + 63) / 64);
+    if (nb)
+        hipLaunchKernelGGL(cloud_classify_kernel, dim3((unsigned)nb), dim3(256), 0, stream, (const float4*)points, point_offsets, transforms,
+                           order, flags, part, a);
+    hipLaunchKernelGGL(cloud_scan_kernel, dim3(a.G > 0 ? 2u : 1u), dim3(1024), 0, stream, point_offsets, (const unsigned long long*)flags,
+                       part, out_offsets, boxes, box_mask, nb, a);
+    if (nb)
+        hipLaunchKernelGGL(cloud_scatter_kernel, dim3((unsigned)nb), dim3(256), 0, stream, (const float4*)points, point_offsets, transforms,
+                           order, (const unsigned long long*)flags, (const int*)part, (float4*)out, a);
     return cobevt::launch_status();
 }

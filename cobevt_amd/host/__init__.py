@@ -35,6 +35,8 @@ from .camera_bev_postprocessor import CameraBevPostprocessor  # noqa: F401
 from .voxel_postprocessor import VoxelPostprocessor  # noqa: F401
 from .bev_preprocessor import BevPreprocessor  # noqa: F401
 from .lidar_bev_postprocessor import LidarBevPostprocessor  # noqa: F401
+from .data_augmentor import DataAugmentor  # noqa: F401
+from .pcd_utils import shuffle_order  # noqa: F401
 from . import eval_utils  # noqa: F401
 from .eval_utils import calculate_ap, caluclate_tp_fp, eval_final_results, voc_ap  # noqa: F401
 from .rgb_preprocessor import RgbPreProcessor  # noqa: F401

@@ -43,7 +43,8 @@ class BevPreprocessor(object):
 
     def preprocess_batch(self, points, point_offsets, out=None, channels_last=False):
         """points (M, 4) fp32 [x, y, z, intensity], the agents' clouds concatenated; point_offsets (N + 1,) int32 / int64 on the device
-        -> {'bev_input': (N, C, nx, ny) fp32} (ops.bev_points); channels_last: (N, nx, ny, C)"""
+        -> {'bev_input': (N, C, nx, ny) fp32} (ops.bev_points); channels_last: (N, nx, ny, C).  ops.prepare_points makes such a cloud
+        from per-agent sensor-frame clouds and their matrices."""
         bev = ops.bev_points(points, point_offsets, self.lidar_range, self.origin, self.res, self.input_shape, self.range_mask,
                              self.ego_mask, channels_last=channels_last, out=out)
         return {"bev_input": bev}

@@ -34,7 +34,8 @@ class SpVoxelPreprocessor(object):
 
     def preprocess_batch(self, points, point_offsets, out=None):
         """points (M, 4) fp32 [x, y, z, intensity], the agents' clouds concatenated in the ego frame; point_offsets (N + 1,) int32 /
-        int64 on the device -> {'voxel_features', 'voxel_coords', 'voxel_num_points', 'num_voxels'} (ops.voxelize_points)"""
+        int64 on the device -> {'voxel_features', 'voxel_coords', 'voxel_num_points', 'num_voxels'} (ops.voxelize_points).
+        ops.prepare_points makes such a cloud from per-agent sensor-frame clouds and their matrices."""
         vf, coords, npts, nvox = ops.voxelize_points(points, point_offsets, self.lidar_range, self.voxel_size, self.max_points_per_voxel,
                                                      self.max_voxels, self.range_mask, self.ego_mask, out=out)
         return {"voxel_features": vf, "voxel_coords": coords, "voxel_num_points": npts, "num_voxels": nvox}

@@ -161,6 +161,8 @@ SIGNATURES = {
     "cobevt_pointpillar_loss": (ctypes.c_int, [_vp] * 9 + [ctypes.c_int] * 4 + [ctypes.c_float, ctypes.c_float, _vp]),
     "cobevt_bev_points_scratch": (ctypes.c_int, [_c_long_p, _c_long_p]),
     "cobevt_bev_points": (ctypes.c_int, [_vp] * 4 + [_c_long_p, _c_double_p, _vp]),
+    "cobevt_prepare_points_scratch": (ctypes.c_int, [_c_long_p, _c_long_p]),
+    "cobevt_prepare_points": (ctypes.c_int, [_vp] * 9 + [_c_long_p, _c_double_p, _vp]),
     "cobevt_bev_labels": (ctypes.c_int, [_vp] * 5 + [_c_int_p, _c_double_p, _vp]),
     "cobevt_bev_post": (ctypes.c_int, [ctypes.POINTER(_vp)] * 2 + [_vp, _c_int_p, ctypes.c_int, _c_double_p, ctypes.c_float,
                                        ctypes.c_float] + [_vp] * 5 + [_vp]),

@@ -1331,6 +1331,126 @@ def voxelize_points(points, point_offsets, lidar_range, voxel_size, max_points=3
     return vf, coords, npts, nvox
 
 
+CLOUD_MAX_BOXES = 128      # ground-truth rows cobevt_prepare_points augments (one thread each of one workgroup)
+_CLOUD_WS = {}             # (device, M) -> prepare_points' int32 workspace, one per shape as for voxelize_points
+_WORLD_KEYS = ("flip_x", "flip_y", "rot", "scale")
+
+
+def prepare_points_workspace_ints(num_points, num_agents=1):
+    """int32 elements of prepare_points' workspace for M points of N agents (cobevt_prepare_points_scratch)"""
+    dims = (ctypes.c_long * 10)(int(num_points), int(num_agents), 0, 0, 0, 0, 0, 0, 0, 0)
+    need = ctypes.c_long(0)
+    _L.call("cobevt_prepare_points_scratch", dims, ctypes.byref(need))
+    return need.value
+
+
+def rotation_cos_sin(angle):
+    """(cos, sin) as common_utils.rotate_points_along_z makes them: torch.cos / torch.sin of the fp32 angle on the CPU"""
+    a = torch.tensor([float(angle)], dtype=torch.float64).float()
+    return float(torch.cos(a)[0]), float(torch.sin(a)[0])
+
+
+def prepare_points(points, point_offsets, transforms=None, *, order=None, ego_mask=False, lidar_range=None, world=None, boxes=None,
+                   box_mask=None, out=None, workspace=None):
+    """Per-agent sensor-frame clouds -> one compact ego-frame cloud (csrc/cloud_prep.hpp), without a host synchronisation: what the
+    reference's datasets do in NumPy in front of the pre-processors.
+    points (M, 4) contiguous fp32 [x, y, z, intensity] and point_offsets (N + 1,) int32 / int64 on the device, as voxelize_points
+    takes them (rows at or past offsets[N] are ignored).  Per agent, in input order - with order (M,) int32 / int64 on the device in
+    the order points[order[i]]; order must map each agent's row range onto itself, which is not checked (host.shuffle_order makes one):
+      1 ego_mask: pcd_utils.mask_ego_points on the sensor-frame point (limits rounded to fp32, voxelize_points' rule);
+      2 transforms (N, 4, 4) fp64 on the device (fp32: converted on the device): pcd_utils.lidar_project in fp64 as
+        ((T[r][0] x + T[r][1] y) + T[r][2] z) + T[r][3]; None skips the stage;
+      3 world = dict(flip_x=bool, flip_y=bool, rot=float | None, scale=float | None), always in this order:
+        augment_utils.random_flip_along_x (y negated), random_flip_along_y (x negated), global_rotation (x, y, z rounded to fp32,
+        x c - y s and x s + y c in fp64 from fp32 values, rounded to fp32), global_scaling (fl32(v * fl32(scale)));
+      4 the point is rounded to fp32;
+      5 lidar_range = [x0, y0, z0, x1, y1, z1]: pcd_utils.mask_points_by_range on the fp32 OUTPUT point with the limits rounded to
+        fp32 (where the reference still holds fp64 points it compares in fp64: a point within half an fp32 ulp of a limit can differ);
+      6 the kept points are written densely, in order.
+    -> points_out (M, 4) fp32, out_offsets (N + 1,) int32: agent a's points are rows out_offsets[a] .. out_offsets[a + 1]; rows at or
+    past out_offsets[N] are NOT written (they keep what `out=` held).  Non-finite values get no rule of their own: a NaN survives the
+    ego mask and fails the range mask.
+    boxes (G <= 128, 7) and box_mask (G,), both fp32 or both fp64, contiguous, on the device: rows with mask == 1 get stage 3 IN PLACE
+    as augment_utils applies it to boxes (flip_x: y and heading negated; flip_y: x negated, heading <- -(h + pi); rot: x, y, z rounded
+    to fp32 and rotated, heading += rot; scale: columns 0 .. 5), in fp64 with one rounding to the dtype; other rows are untouched.
+    The reference compacts the valid rows to the front and leaves the mask alone, which is the same thing whenever the mask is a
+    prefix - and generate_object_center always produces a prefix.
+    Every call augments the boxes again: a captured graph that holds the call does so on each replay, so refresh the boxes' buffer
+    before a replay (as pipeline.CapturedCall does with its arguments) or keep the boxes out of the captured call.
+    out = (points_out, out_offsets) to write into, points_out not overlapping points; workspace = an int32 tensor of at least prepare_points_workspace_ints(M) elements
+    whose storage is 8-byte aligned (default: one cached per shape and device).  Bitwise reproducible."""
+    _need_cuda(points, point_offsets, transforms, order, boxes, box_mask, workspace, *(out or ()))
+    if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 4 or not points.is_contiguous():
+        raise CobevtHipError("prepare_points: points must be contiguous fp32 (M, 4) as [x, y, z, intensity], got %s %s"
+                             % (points.dtype, tuple(points.shape)))
+    offs = _index_i32(point_offsets, "prepare_points: point_offsets")
+    if offs.dim() != 1 or offs.shape[0] < 2:
+        raise CobevtHipError("prepare_points: point_offsets must be (N + 1,) with N >= 1 agents, got %s" % (tuple(offs.shape),))
+    n, m, dev = offs.shape[0] - 1, points.shape[0], points.device
+    if transforms is not None:
+        if transforms.dtype not in (torch.float64, torch.float32) or tuple(transforms.shape) != (n, 4, 4):
+            raise CobevtHipError("prepare_points: transforms must be fp64 (or fp32) (N, 4, 4) with N = %d agents, got %s %s"
+                                 % (n, transforms.dtype, tuple(transforms.shape)))
+        transforms = transforms.to(torch.float64).contiguous()
+    if order is not None:
+        order = _index_i32(order, "prepare_points: order")
+        if tuple(order.shape) != (m,):
+            raise CobevtHipError("prepare_points: order must be (M,) with M = %d rows, got %s" % (m, tuple(order.shape)))
+    rng = [0.0] * 6
+    if lidar_range is not None:
+        rng = [float(v) for v in lidar_range]
+        if len(rng) != 6 or not all(np.isfinite(rng)):
+            raise CobevtHipError("prepare_points: lidar_range = [x0, y0, z0, x1, y1, z1], got %r" % (list(lidar_range),))
+    world = dict(world or {})
+    if any(k not in _WORLD_KEYS for k in world):
+        raise CobevtHipError("prepare_points: world = dict(flip_x, flip_y, rot, scale), got the keys %r" % (sorted(world),))
+    rot, scale = world.get("rot"), world.get("scale")
+    if (rot is not None and not np.isfinite(float(rot))) or (scale is not None and not np.isfinite(float(scale))):
+        raise CobevtHipError("prepare_points: world['rot'] and world['scale'] are finite numbers or None, got %r / %r" % (rot, scale))
+    cos, sin = rotation_cos_sin(rot) if rot is not None else (1.0, 0.0)
+    g = 0
+    if boxes is not None or box_mask is not None:
+        if boxes is None or box_mask is None or boxes.dtype not in (torch.float32, torch.float64) or boxes.dim() != 2 \
+                or boxes.shape[1] != 7 or not boxes.is_contiguous():
+            raise CobevtHipError("prepare_points: boxes must be contiguous fp32 or fp64 (G, 7), with box_mask (G,)")
+        g = boxes.shape[0]
+        if box_mask.dtype != boxes.dtype:
+            raise CobevtHipError("prepare_points: boxes and box_mask must have the same dtype, got %s and %s" % (boxes.dtype, box_mask.dtype))
+        if tuple(box_mask.shape) != (g,) or not box_mask.is_contiguous():
+            raise CobevtHipError("prepare_points: box_mask must be contiguous (G,) with G = %d, got %s" % (g, tuple(box_mask.shape)))
+        if g > CLOUD_MAX_BOXES:
+            raise CobevtHipError("prepare_points: at most G = %d boxes are supported, got %d" % (CLOUD_MAX_BOXES, g))
+    if workspace is None:
+        key = (dev, m)
+        workspace = _CLOUD_WS.get(key)
+        if workspace is None:
+            need = prepare_points_workspace_ints(m, n)
+            workspace = _CLOUD_WS[key] = torch.empty((need + 1) // 2, device=dev, dtype=torch.int64).view(torch.int32)
+    else:
+        need = prepare_points_workspace_ints(m, n)
+        if workspace.dtype != torch.int32 or not workspace.is_contiguous() or workspace.numel() < need or workspace.device != dev \
+                or workspace.data_ptr() % 8:
+            raise CobevtHipError("prepare_points: workspace= must be a contiguous, 8-byte aligned int32 tensor of at least %d elements on %s"
+                                 % (need, dev))
+    if out is None:
+        out = (None, None)
+    elif len(out) != 2:
+        raise CobevtHipError("prepare_points: out= is (points_out, out_offsets)")
+    pts_out = _canvas(out[0], (m, 4), torch.float32, dev, "prepare_points")
+    if m and pts_out.data_ptr() < points.data_ptr() + 16 * m and points.data_ptr() < pts_out.data_ptr() + 16 * m:
+        raise CobevtHipError("prepare_points: out= must not overlap points (the scatter launch reads points while it writes out)")
+    out_offs = _canvas(out[1], (n + 1,), torch.int32, dev, "prepare_points")
+    dims = (ctypes.c_long * 10)(m, n, g, int(bool(ego_mask)), int(lidar_range is not None), int(bool(world.get("flip_x"))),
+                                int(bool(world.get("flip_y"))), int(rot is not None), int(scale is not None),
+                                int(g > 0 and boxes.dtype == torch.float64))
+    geom = (ctypes.c_double * 10)(*(rng + [cos, sin, float(rot or 0.0), float(1.0 if scale is None else scale)]))
+    with _timed("prepare_points|M%d N%d G%d" % (m, n, g), lambda: (0.0, 16.0 * m + 16.0 * m + 16.0 * m)):
+        _L.call("cobevt_prepare_points", _p(points) if m else None, _p(offs), _p(transforms), _p(order) if m else None,
+                _p(pts_out) if m else None, _p(out_offs), _p(boxes) if g else None, _p(box_mask) if g else None, _p(workspace), dims, geom,
+                _stream())
+    return pts_out, out_offs
+
+
 DETECT_TOP = 1000          # box_utils.nms_rotated's `top`: the fixed capacity of the detection outputs
 DETECT_MAX_CAV = 16
 _DETECT_WS = {}            # (device, total anchors) -> the workspace: one buffer per size, so a captured graph replays on the buffer it saw

@@ -992,6 +992,42 @@ int cobevt_pointpillar_loss(const float* psm, const float* rm, const float* pos_
  *   memset node and four launches (bev decode, select + sort, mask, greedy); integer atomics only, no host read, no allocation,
  *   bitwise reproducible.  workspace: cobevt_detect_scratch(total pixels) BYTES, 8-byte aligned.  Skip rules: none.
  */
+/*
+ * cobevt_prepare_points (csrc/cloud_prep.hpp, compiled into voxelize; identical in every library): per-agent SENSOR-frame clouds and
+ *   their matrices -> one compact ego-frame cloud, the input of cobevt_voxelize_points / cobevt_bev_points.  What the reference's
+ *   datasets do in NumPy: pcd_utils.mask_ego_points, lidar_project, DataAugmentor (world flip / rotation / scaling),
+ *   mask_points_by_range and the vstack.
+ *   points (M, 4) fp32 and point_offsets (N + 1) int32 ON THE DEVICE with the conventions of cobevt_voxelize_points (rows at or past
+ *   offsets[N] are ignored); transforms (N, 4, 4) fp64 on the device or null (no projection); order (M) int32 on the device or null:
+ *   row i reads points[order[i]] - it must map each agent's row range onto itself, which is NOT checked (an entry outside [0, M)
+ *   drops the row); out (M, 4) fp32, not overlapping points; out_offsets (N + 1) int32: each agent's start in out.
+ *   dims = [M, N, G, ego_mask, range_mask, flip_x, flip_y, rotate, scale, boxes are fp64] (host), G <= 128 (more: code 2);
+ *   geom = [x0, y0, z0, x1, y1, z1 (for range_mask), cos, sin (fp32 values of the fp32 angle), angle, scale] (host, DOUBLES).
+ *   Per agent, in input (or `order`) order:
+ *     1 ego mask (ego_mask) on the sensor-frame fp32 point, the rule of cobevt_voxelize_points;
+ *     2 projection (transforms): ((T[r][0] x + T[r][1] y) + T[r][2] z) + T[r][3] in fp64, this association, no contraction;
+ *     3 augmentation: flip_x negates y, flip_y negates x; rotate rounds x, y, z to fp32, forms x c - y s and x s + y c in fp64 from
+ *       the fp32 values and rounds each to fp32; scale is fl32(v * fl32(scale)) - the reference where its points are fp32 at that
+ *       step; after a projection without a rotation it multiplies its fp64 array by the fp64 scale, up to one fp32 ulp away; the
+ *       intensity is copied bitwise;
+ *     4 the point is rounded to fp32;
+ *     5 range mask (range_mask): strict inequalities against the limits rounded to fp32, on the fp32 OUTPUT point - a deliberate
+ *       deviation where the reference still holds fp64 points (140.7999999 against 140.8 is kept there and dropped here);
+ *     6 stable compaction.  Rows of out at or past out_offsets[N] are NOT written.
+ *   Skip rules: none for non-finite values, IEEE comparisons decide (a NaN survives the ego mask and fails the range mask).
+ *   boxes (G, 7) and box_mask (G), both fp32 or both fp64, or null with G = 0: rows with mask == 1 get stage 3 in place as
+ *   augment_utils applies it to boxes, in fp64 - flip_x: y, heading negated; flip_y: x negated, heading <- -(h + pi); rotate: x, y, z
+ *   rounded to fp32 and rotated as the points, heading += angle; scale: columns 0 .. 5 times the fp64 scale - and are rounded to
+ *   their dtype once; other rows are untouched.
+ *   Three launches (classify: a flag bit per point and a count per 1024 points; scan: one workgroup, and one more for the boxes;
+ *   scatter: one 16-byte store per kept point), M = 0: the scan launch alone.  No atomics, no workgroup waits on another, no host
+ *   read, no allocation, bitwise reproducible.  workspace: cobevt_prepare_points_scratch(dims) ints, 8-byte aligned, contents
+ *   irrelevant on entry; points and out 16-byte aligned.  Measured: 38.8 us per eager call for 5 x 65,536 points with every stage on.
+ */
+int cobevt_prepare_points_scratch(const long* dims, long* workspace_ints);
+int cobevt_prepare_points(const float* points, const int* point_offsets, const double* transforms, const int* order, float* out,
+                          int* out_offsets, void* boxes, const void* box_mask, int* workspace, const long* dims, const double* geom,
+                          hipStream_t stream);
 int cobevt_bev_points_scratch(const long* dims, long* workspace_ints);
 int cobevt_bev_points(const float* points, const int* point_offsets, float* bev, int* workspace, const long* dims, const double* geom,
                       hipStream_t stream);
