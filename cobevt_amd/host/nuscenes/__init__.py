@@ -7,4 +7,5 @@ from .decoder import Decoder, DecoderBlock  # noqa: F401
 from .cvt import CrossViewTransformer  # noqa: F401
 from .efficientnet import EfficientNetExtractor  # noqa: F401
 from .metrics import BaseIoUMetric, IoUMetric  # noqa: F401
+from .transforms import LoadDataTransform, Sample  # noqa: F401
 from .losses import BinarySegmentationLoss, CenterLoss, MultipleLoss, SigmoidFocalLoss  # noqa: F401

@@ -88,7 +88,9 @@ SIGNATURES = {
                                                  ctypes.c_int, ctypes.c_float, ctypes.c_float, ctypes.c_int, _vp]),
     "cobevt_iou_counts": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                          ctypes.c_int, ctypes.c_int, _vp]),
-    "cobevt_agent_max": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_long, _vp]),
+    "cobevt_resize_pil_u8": (ctypes.c_int, [_vp] * 7 + [_c_int_p, _vp]),
+    "cobevt_decode_bev": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]),
+    "cobevt_agent_max":(ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_long, _vp]),
     "cobevt_bottleneck_nhwc": (ctypes.c_int, [_vp] * 8 + [_c_int_p, _vp]),
     "cobevt_bottleneck_f32_nhwc": (ctypes.c_int, [_vp] * 9 + [_c_int_p, _vp]),
     "cobevt_attention_index_map": (ctypes.c_int, [_c_int_p, ctypes.c_int, _vp, _vp]),

@@ -1451,6 +1451,147 @@ def prepare_points(points, point_offsets, transforms=None, *, order=None, ego_ma
     return pts_out, out_offs
 
 
+PIL_PRECISION_BITS = 22    # Pillow's 8-bit resample: 32 - 8 - 2 bits of coefficient
+PIL_MAX_TAPS = 17          # taps per output index cobevt_resize_pil_u8 takes: a down-scale of at most 8
+BEV_MAX_CLASSES = 16       # label bits cobevt_decode_bev unpacks
+_PIL_TAPS = {}             # (n_in, n_out) -> (bounds, coeffs), host, read-only
+_PIL_TAPS_DEV = {}         # (device, n_in, n_out) -> the same on the device
+_PIL_LUT = {}              # device -> ToTensor's byte -> fp32 table
+
+
+def pil_ksize(n_in, n_out):
+    """taps per output index of Pillow's BILINEAR resample from n_in to n_out samples"""
+    return 2 * int(math.ceil(1.0 * max(n_in / n_out, 1.0))) + 1
+
+
+def pil_resize_taps(n_in, n_out):
+    """Pillow's tap tables for resampling one axis from n_in to n_out samples with BILINEAR on 8-bit data (Resample.c:
+    precompute_coeffs, then normalize_coeffs_8bpc), evaluated in float64 in Pillow's own order of operations.
+    -> bounds int32 (n_out, 2) = [first source index, tap count], coeffs int32 (n_out, ksize) in 22-bit fixed point (zero past
+    the tap count).  Pure host function; the arrays are cached and read-only."""
+    n_in, n_out = int(n_in), int(n_out)
+    if n_in < 1 or n_out < 1:
+        raise CobevtHipError("pil_resize_taps: n_in and n_out must be positive, got %d -> %d" % (n_in, n_out))
+    hit = _PIL_TAPS.get((n_in, n_out))
+    if hit is not None:
+        return hit
+    scale = n_in / n_out
+    filterscale = max(scale, 1.0)
+    support = 1.0 * filterscale
+    ksize = 2 * int(math.ceil(support)) + 1
+    ss = 1.0 / filterscale
+    bounds = np.zeros((n_out, 2), dtype=np.int32)
+    coeffs = np.zeros((n_out, ksize), dtype=np.int32)
+    for xx in range(n_out):
+        center = (xx + 0.5) * scale
+        xmin = max(int(center - support + 0.5), 0)
+        xmax = min(int(center + support + 0.5), n_in) - xmin
+        k, ww = [], 0.0
+        for x in range(xmax):
+            a = abs((x + xmin - center + 0.5) * ss)
+            w = 1.0 - a if a < 1.0 else 0.0
+            k.append(w)
+            ww += w
+        for x in range(xmax):
+            v = k[x] / ww if ww != 0.0 else k[x]
+            coeffs[xx, x] = int(-0.5 + v * (1 << PIL_PRECISION_BITS)) if v < 0 else int(0.5 + v * (1 << PIL_PRECISION_BITS))
+        bounds[xx] = (xmin, xmax)
+    bounds.setflags(write=False)
+    coeffs.setflags(write=False)
+    _PIL_TAPS[(n_in, n_out)] = (bounds, coeffs)
+    return bounds, coeffs
+
+
+def _pil_taps_device(device, n_in, n_out, what):
+    key = (device, n_in, n_out)
+    hit = _PIL_TAPS_DEV.get(key)
+    if hit is None:
+        if device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+            raise CobevtHipError("%s: the tap tables for %d -> %d are not on %s yet and cannot be uploaded while a graph is being "
+                                 "captured; call once outside the capture" % (what, n_in, n_out, device))
+        b, c = pil_resize_taps(n_in, n_out)
+        hit = _PIL_TAPS_DEV[key] = (torch.from_numpy(b.copy()).to(device), torch.from_numpy(c.copy()).to(device))
+    return hit
+
+
+def _pil_lut(device, what):
+    lut = _PIL_LUT.get(device)
+    if lut is None:
+        if device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+            raise CobevtHipError("%s: the byte -> fp32 table is not on %s yet and cannot be uploaded while a graph is being captured; "
+                                 "call once outside the capture" % (what, device))
+        # the very expression torchvision's ToTensor evaluates per byte (img.to(float32).div(255)), on the host: no device division
+        lut = _PIL_LUT[device] = torch.arange(256, dtype=torch.float32).div(255).to(device)
+    return lut
+
+
+def resize_pil_bilinear(images_u8, size, top_crop=0, *, dtype=torch.float32, out=None):
+    """Image.resize(size, resample=Image.BILINEAR) of Pillow's 8-bit path, the crop of the top rows and ToTensor, for a stack of
+    decoded frames in one launch (csrc/image_ingest.hpp): the camera side of the nuScenes LoadDataTransform.
+    images_u8 (n, H, W, 3) contiguous uint8 on the device (any storage offset); size = (w_resize, h_resize), Pillow's order;
+    top_crop rows of the RESIZED image are cut (and never computed).  With h = h_resize - top_crop, w = w_resize:
+      dtype=torch.float32 -> (n, 3, h, w) fp32, each byte through the table arange(256) / 255: ToTensor's result, bit for bit;
+      dtype=torch.uint8   -> (n, h, w, 3) uint8, the resized bytes themselves.
+    Bit-exact with Pillow: integer tap tables from pil_resize_taps (cached on the device per (n_in, n_out), uploaded on first use -
+    outside a graph capture), 22-bit fixed-point passes, the horizontal result rounded to a byte before the vertical pass, an axis
+    that keeps its size skipped.  A down-scale above 8 on either axis is refused.  No host synchronisation."""
+    what = "resize_pil_bilinear"
+    _need_cuda(images_u8, out)
+    if images_u8.dtype != torch.uint8 or images_u8.dim() != 4 or not images_u8.is_contiguous():
+        raise CobevtHipError("%s: images_u8 must be contiguous uint8 (n, H, W, 3), got %s %s"
+                             % (what, images_u8.dtype, tuple(images_u8.shape)))
+    n, hs, ws, ch = images_u8.shape
+    if ch != 3:
+        raise CobevtHipError("%s: images_u8 must have 3 channels last, got %d" % (what, ch))
+    if n < 1 or hs < 1 or ws < 1:
+        raise CobevtHipError("%s: images_u8 must not be empty, got %s" % (what, tuple(images_u8.shape)))
+    try:
+        wr, hr = (int(v) for v in size)
+    except (TypeError, ValueError):
+        raise CobevtHipError("%s: size = (w_resize, h_resize), got %r" % (what, size))
+    if wr < 1 or hr < 1:
+        raise CobevtHipError("%s: size = (w_resize, h_resize) must be positive, got %r" % (what, (wr, hr)))
+    top = int(top_crop)
+    if top < 0 or top >= hr:
+        raise CobevtHipError("%s: top_crop must lie in [0, h_resize = %d), got %d" % (what, hr, top))
+    if pil_ksize(ws, wr) > PIL_MAX_TAPS or pil_ksize(hs, hr) > PIL_MAX_TAPS:
+        raise CobevtHipError("%s: size: a down-scale above 8 on either axis is not supported, got (%d, %d) -> (%d, %d)"
+                             % (what, hs, ws, hr, wr))
+    if dtype not in (torch.float32, torch.uint8):
+        raise CobevtHipError("%s: dtype must be torch.float32 or torch.uint8, got %s" % (what, dtype))
+    dev = images_u8.device
+    as_u8 = dtype == torch.uint8
+    res = _canvas(out, (n, hr - top, wr, 3) if as_u8 else (n, 3, hr - top, wr), dtype, dev, what)
+    hb, hc = _pil_taps_device(dev, ws, wr, what) if ws != wr else (None, None)
+    vb, vc = _pil_taps_device(dev, hs, hr, what) if hs != hr else (None, None)
+    lut = None if as_u8 else _pil_lut(dev, what)
+    dims = _ints([n, hs, ws, ch, hr, wr, top, int(as_u8)])
+    with _timed("resize_pil|%dx%d>%dx%d" % (hs, ws, hr, wr), lambda: (0.0, 3.0 * n * hs * ws + res.numel() * res.element_size())):
+        _L.call("cobevt_resize_pil_u8", _p(images_u8), _p(res), _p(hb), _p(hc), _p(vb), _p(vc), _p(lut), dims, _stream())
+    return res
+
+
+def decode_bev(labels_i32, num_classes, out=None):
+    """The bit-packed nuScenes BEV label -> class planes: labels_i32 (n, h, w) contiguous int32 on the device ->
+    (n, num_classes <= 16, h, w) fp32 of (x >> c) & 1 - the reference's decode -> * 255 -> uint8 -> ToTensor, exactly 0.0 or 1.0
+    (csrc/image_ingest.hpp).  One streaming launch, no host synchronisation."""
+    what = "decode_bev"
+    _need_cuda(labels_i32, out)
+    if labels_i32.dtype != torch.int32 or labels_i32.dim() != 3 or not labels_i32.is_contiguous():
+        raise CobevtHipError("%s: labels_i32 must be contiguous int32 (n, h, w), got %s %s"
+                             % (what, labels_i32.dtype, tuple(labels_i32.shape)))
+    if labels_i32.numel() < 1:
+        raise CobevtHipError("%s: labels_i32 must not be empty, got %s" % (what, tuple(labels_i32.shape)))
+    c = int(num_classes)
+    if c < 1 or c > BEV_MAX_CLASSES:
+        raise CobevtHipError("%s: num_classes must lie in 1 .. %d, got %d" % (what, BEV_MAX_CLASSES, c))
+    n, h, w = labels_i32.shape
+    res = _canvas(out, (n, c, h, w), torch.float32, labels_i32.device, what)
+    with _timed("decode_bev|C%d" % c, lambda: (0.0, 4.0 * n * h * w * (1 + c))):
+        _L.call("cobevt_decode_bev", _p(labels_i32), _p(res), n, h * w, c, _stream())
+    return res
+
+
 DETECT_TOP = 1000          # box_utils.nms_rotated's `top`: the fixed capacity of the detection outputs
 DETECT_MAX_CAV = 16
 _DETECT_WS = {}            # (device, total anchors) -> the workspace: one buffer per size, so a captured graph replays on the buffer it saw

@@ -514,6 +514,29 @@ int cobevt_iou_counts(const float* pred, const float* label, const unsigned char
                       const float* thresholds, unsigned long long* counts, int N, int C, int NL, int hw, int T,
                       int min_visibility, hipStream_t stream);
 
+/*
+ * cobevt_resize_pil_u8 (csrc/image_ingest.hpp, compiled into postprocess; identical in every library): the camera side of the
+ *   nuScenes LoadDataTransform (nuscenes/cross_view_transformer/data/transforms.py:118-149) on decoded frames in device memory -
+ *   Image.resize((w_resize, h_resize), resample=BILINEAR) of Pillow's 8-bit path, the crop of the top `top_crop` rows, ToTensor.
+ *   src (n, H, W, 3) uint8 contiguous, any alignment.  dims = [n, H, W, channels, h_resize, w_resize, top_crop, out is uint8] (host).
+ *   out: (n, 3, h, w) fp32 = lut[byte] (out is uint8 = 0; lut[256] fp32 on the device, ToTensor's is i / 255), or (n, h, w, 3)
+ *   uint8, the resized bytes themselves (out is uint8 = 1; lut may be null); h = h_resize - top_crop, w = w_resize.
+ *   Per axis with n_in != n_out the caller passes Pillow's tap tables ON THE DEVICE (Resample.c precompute_coeffs +
+ *   normalize_coeffs_8bpc, evaluated in float64 on the host): bounds (n_out, 2) int32 = [first source index, tap count] and coeffs
+ *   (n_out, ksize) int32, 22-bit fixed point (the kernel multiplies in 24 bits: magnitudes below 2^23), ksize = 2 * ceil(max(n_in / n_out, 1)) + 1; hbounds / hcoeffs for W -> w_resize,
+ *   vbounds / vcoeffs for H -> h_resize.  An axis that keeps its size is skipped as Pillow skips it (its tables may be null).
+ *   One pass is clip((sum_t src[first + t] * coeffs[t] + 2^21) >> 22, 0, 255) in int32; the horizontal pass runs first and its
+ *   result is rounded to a byte before the vertical pass reads it, as in Pillow: bit-exact.  Only rows the crop keeps are computed.
+ *   Table entries are clamped to the image, so a wrong table gives wrong pixels and no access outside src.
+ *   Code 2, before any launch: channels != 3, a down-scale above 8 on either axis (ksize > 17), n, a size or an output empty,
+ *   n > 65535, top_crop outside [0, h_resize).  One launch, no atomics, no host read, no allocation.
+ * cobevt_decode_bev: the label side (transforms.py:151-159 with data/common.py:69-78): labels (N, hw) int32 bit-packed ->
+ *   out (N, num_classes <= 16, hw) fp32 of (x >> c) & 1, exactly 0.0 or 1.0.  One streaming launch.
+ */
+int cobevt_resize_pil_u8(const unsigned char* src, void* out, const int* hbounds, const int* hcoeffs, const int* vbounds,
+                         const int* vcoeffs, const float* lut, const int* dims, hipStream_t stream);
+int cobevt_decode_bev(const int* labels, float* out, int N, int hw, int num_classes, hipStream_t stream);
+
 /* ---- upstream of the nuScenes path: MBConv pieces of the EfficientNet image backbone wrapped by
  * nuscenes/cross_view_transformer/model/backbones/efficientnet.py:24-96 (efficientnet-pytorch 0.7.1 MBConvBlock.forward;
  * the 1x1 convolutions of a block go through cobevt_linear_rows / cobevt_conv2d_nhwc with act 3 = swish) -------------- */
