@@ -29,6 +29,9 @@ from .self_attn import AttFusion  # noqa: F401
 from .auto_encoder import AutoEncoder  # noqa: F401
 from .att_bev_backbone import AttBEVBackbone  # noqa: F401
 from .point_pillar_intermediate import PointPillarIntermediate  # noqa: F401
+from .mean_vfe import MeanVFE  # noqa: F401
+from .sparse_backbone_3d import SparseConv3d, SubMConv3d, VoxelBackBone8x  # noqa: F401
+from .height_compression import HeightCompression  # noqa: F401
 from .pipeline import CapturedCall, CapturedCorpBEVT, HostFrameFeeder, PipelinedCorpBEVT  # noqa: F401
 # the data formats either side of the path
 from .camera_bev_postprocessor import CameraBevPostprocessor  # noqa: F401

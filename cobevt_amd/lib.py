@@ -168,6 +168,12 @@ SIGNATURES = {
     "cobevt_bev_labels": (ctypes.c_int, [_vp] * 5 + [_c_int_p, _c_double_p, _vp]),
     "cobevt_bev_post": (ctypes.c_int, [ctypes.POINTER(_vp)] * 2 + [_vp, _c_int_p, ctypes.c_int, _c_double_p, ctypes.c_float,
                                        ctypes.c_float] + [_vp] * 5 + [_vp]),
+    "cobevt_mean_vfe": (ctypes.c_int, [_vp] * 4 + [_c_long_p, _vp]),
+    "cobevt_sparse_scratch": (ctypes.c_int, [_c_long_p, _c_long_p]),
+    "cobevt_sparse_index": (ctypes.c_int, [_vp] * 5 + [_c_long_p, _vp]),
+    "cobevt_sparse_downsample": (ctypes.c_int, [_vp] * 5 + [_c_long_p, _vp]),
+    "cobevt_sparse_conv": (ctypes.c_int, [_vp] * 9 + [_c_long_p, _vp]),
+    "cobevt_sparse_dense": (ctypes.c_int, [_vp] * 4 + [_c_long_p, _vp]),
 }
 
 _libs = {}

@@ -1451,6 +1451,268 @@ def prepare_points(points, point_offsets, transforms=None, *, order=None, ego_ma
     return pts_out, out_offs
 
 
+# ----------------------------------------------------------------------------------------------
+# the sparse 3-D voxel backbone (csrc/sparse_conv.hpp): MeanVFE, active-set indices, SubMConv3d / SparseConv3d, dense()
+# ----------------------------------------------------------------------------------------------
+SPARSE_TILE_ROWS = 32      # output rows of one MFMA tile of cobevt_sparse_conv: the unit that skips absent taps
+SPARSE_BLOCK_ROWS = 128    # ... and of one workgroup (four tiles)
+_SPARSE_WS = {}            # (device, N, D, H, W) -> a level's int32 index workspace, one per shape as for voxelize_points
+
+
+def sparse_row_channels(channels, dtype):
+    """channels of one feature row as cobevt_sparse_conv reads it: a whole number of 32-byte groups (16 bf16 / 8 fp32)"""
+    g = 16 if dcode(dtype) == BF16 else 8
+    return (int(channels) + g - 1) // g * g
+
+
+def mean_vfe(voxel_features, voxel_num_points, voxel_coords=None, dtype=torch.float32, channels=None, out=None):
+    """MeanVFE (csrc/sparse_conv.hpp) in one launch: voxel_features (P, T, C) contiguous fp32, voxel_num_points (P,) int32 / int64 ->
+    (P, channels) in `dtype`: per voxel the sum of its first voxel_num_points point slots, in slot order, divided by
+    max(voxel_num_points, 1) - the reference's sum over all T slots whenever the unused ones are zero, which spconv guarantees.
+    channels (default C, at most 64) >= C pads every row with zeros: sparse_row_channels(C, dtype) is the row cobevt_sparse_conv reads.
+    With voxel_coords (P, 4) the rows with a batch index < 0 (the padding rows of a fixed-size voxel dict) are zero."""
+    _need_cuda(voxel_features, voxel_num_points, voxel_coords, out)
+    if voxel_features.dtype != torch.float32 or voxel_features.dim() != 3 or not voxel_features.is_contiguous():
+        raise CobevtHipError("mean_vfe: voxel_features must be contiguous fp32 (P, T, C), got %s %s" % (voxel_features.dtype, tuple(voxel_features.shape)))
+    p, t, c = voxel_features.shape
+    cpad = c if channels is None else int(channels)
+    if t < 1 or c < 1 or cpad < c or cpad > 64:
+        raise CobevtHipError("mean_vfe: T >= 1 point slots and 1 <= C <= channels <= 64 are supported, got T = %d, C = %d, channels = %d" % (t, c, cpad))
+    npts = _index_i32(voxel_num_points, "mean_vfe: voxel_num_points")
+    if tuple(npts.shape) != (p,):
+        raise CobevtHipError("mean_vfe: voxel_num_points must be (P,) with P = %d, got %s" % (p, tuple(npts.shape)))
+    coords = None
+    if voxel_coords is not None:
+        coords = _index_i32(voxel_coords, "mean_vfe: voxel_coords", (4,))
+        if coords.shape[0] != p:
+            raise CobevtHipError("mean_vfe: voxel_coords must be (P, 4) with P = %d" % p)
+    out = _canvas(out, (p, cpad), dtype, voxel_features.device, "mean_vfe")
+    dims = (ctypes.c_long * 5)(dcode(dtype), p, t, c, cpad)
+    with _timed("mean_vfe|P%d T%d C%d" % (p, t, c), lambda: (float(p * t * c), 4.0 * p * t * c + out.element_size() * p * cpad)):
+        _L.call("cobevt_mean_vfe", _p(voxel_features), _p(npts), _p(coords), _p(out), dims, _stream())
+    return out
+
+
+def _sparse_shape(batch_size, spatial_shape, what):
+    shape = tuple(int(v) for v in spatial_shape)
+    n = int(batch_size)
+    if len(shape) != 3 or n < 1 or min(shape) < 1:
+        raise CobevtHipError("%s: batch_size >= 1 and spatial_shape = (D, H, W) >= 1 are needed, got %r / %r" % (what, batch_size, list(spatial_shape)))
+    return n, shape
+
+
+def sparse_workspace_ints(batch_size, spatial_shape):
+    """int32 elements of one level's index workspace - a bit per cell, a popcount prefix per 32-bit word, the scan's partials - for
+    batch_size samples on the sparse shape (D, H, W) (cobevt_sparse_scratch)"""
+    n, shape = _sparse_shape(batch_size, spatial_shape, "sparse_workspace_ints")
+    need = ctypes.c_long(0)
+    _L.call("cobevt_sparse_scratch", (ctypes.c_long * 4)(n, *shape), ctypes.byref(need))
+    return need.value
+
+
+def _sparse_ws(workspace, dev, n, shape, what):
+    if workspace is None:
+        key = (dev, n) + shape
+        workspace = _SPARSE_WS.get(key)
+        if workspace is None:
+            workspace = _SPARSE_WS[key] = torch.empty(sparse_workspace_ints(n, shape), device=dev, dtype=torch.int32)
+        return workspace
+    need = sparse_workspace_ints(n, shape)
+    if workspace.dtype != torch.int32 or not workspace.is_contiguous() or workspace.numel() < need or workspace.device != dev \
+            or workspace.data_ptr() % 16:
+        raise CobevtHipError("%s: workspace= must be a contiguous, 16-byte aligned int32 tensor of at least %d elements on %s" % (what, need, dev))
+    return workspace
+
+
+def sparse_out_shape(spatial_shape, kernel, stride, padding):
+    """the output shape of SparseConv3d: floor((n + 2 p - k) / s) + 1 per axis"""
+    return tuple((int(n) + 2 * p - k) // s + 1 for n, k, s, p in zip(spatial_shape, kernel, stride, padding))
+
+
+def _triple(v):
+    return (int(v),) * 3 if isinstance(v, (int, np.integer)) else tuple(int(x) for x in v)
+
+
+class SparseConvTensor(object):
+    """A level of the sparse backbone, the holder the reference gets from spconv:
+      features       (capacity, C) in the compute dtype; rows at or past the live count are NOT written
+      indices        (capacity, 4) int32 [b, z, y, x], rows ordered by the cell index ((b D + z) H + y) W + x
+      num            (2,) int32 ON THE DEVICE: [live rows, rows dropped because the capacity was smaller than the active set]
+      spatial_shape  (D, H, W); batch_size
+    dense() -> (N, C, D, H, W), zero off the active set.  `workspace` is the level's index (sparse_workspace_ints), `row_map` - only on
+    what sparse_index returns - the input row each level row reads its features from."""
+
+    def __init__(self, features, indices, num, spatial_shape, batch_size, workspace, row_map=None):
+        self.features, self.indices, self.num = features, indices, num
+        self.spatial_shape, self.batch_size = tuple(int(v) for v in spatial_shape), int(batch_size)
+        self.workspace, self.row_map = workspace, row_map
+
+    @property
+    def capacity(self):
+        return int(self.indices.shape[0])
+
+    def dense(self):
+        return sparse_dense(self)
+
+
+def sparse_index(voxel_coords, batch_size, spatial_shape, features=None, capacity=None, workspace=None):
+    """The active set of level 0 from voxel_coords (P, 4) int32 / int64 [b, z, y, x] on the sparse shape (D, H, W)
+    (cobevt_sparse_index), without a host read and independent of scheduling -> SparseConvTensor whose rows are ordered by cell index.
+    Rows with b < 0 (padding rows) or a coordinate outside the shape are ignored; of duplicate cells the lowest input row wins.
+    capacity (default P: nothing can be dropped) bounds the rows; cells past it are dropped from the high end of the cell order and
+    counted in num[1].  features (P, C) are NOT permuted: the tensor keeps them with row_map (capacity,), and the first convolution
+    reads row r of the level from features[row_map[r]].  workspace = an int32 tensor of at least sparse_workspace_ints(...) elements
+    (default: one cached per shape and device, so a second index of the same shape replaces the first)."""
+    _need_cuda(voxel_coords, features, workspace)
+    n, shape = _sparse_shape(batch_size, spatial_shape, "sparse_index")
+    coords = _index_i32(voxel_coords, "sparse_index: voxel_coords", (4,))
+    p, dev = coords.shape[0], coords.device
+    cap = max(p, 1) if capacity is None else int(capacity)
+    if cap < 1:
+        raise CobevtHipError("sparse_index: capacity must be >= 1, got %d" % cap)
+    if features is not None and (features.dim() != 2 or features.shape[0] != p or not features.is_contiguous()):
+        raise CobevtHipError("sparse_index: features must be contiguous (P, C) with P = %d, got %s" % (p, tuple(features.shape)))
+    workspace = _sparse_ws(workspace, dev, n, shape, "sparse_index")
+    indices = torch.empty((cap, 4), device=dev, dtype=torch.int32)
+    num = torch.empty((2,), device=dev, dtype=torch.int32)
+    source = torch.empty((cap,), device=dev, dtype=torch.int32)
+    dims = (ctypes.c_long * 6)(n, shape[0], shape[1], shape[2], p, cap)
+    cells = n * shape[0] * shape[1] * shape[2]
+    with _timed("sparse_index|P%d N%d %dx%dx%d" % ((p, n) + shape), lambda: (0.0, 32.0 * p + cells / 8.0 * 5 + 20.0 * cap)):
+        _L.call("cobevt_sparse_index", _p(coords) if p else None, _p(workspace), _p(indices), _p(num), _p(source), dims, _stream())
+    return SparseConvTensor(features, indices, num, shape, n, workspace, row_map=source)
+
+
+def sparse_downsample(x, kernel, stride, padding, capacity=None, workspace=None):
+    """The output level of SparseConv3d(kernel, stride, padding) over the level x (cobevt_sparse_downsample): a cell is active when
+    any input of its receptive field is -> SparseConvTensor without features.  capacity: default the provable bound
+    min(cells of the output level, outputs one input can mark x x's capacity) - 8 x for kernel 3 / stride 2, 2 x for (3, 1, 1) /
+    (2, 1, 1) -, with which nothing can be dropped; a smaller one drops the cells past it from the high end of the cell order."""
+    k, s, p = _triple(kernel), _triple(stride), _triple(padding)
+    _need_cuda(x.indices, x.num, workspace)
+    so = sparse_out_shape(x.spatial_shape, k, s, p)
+    if min(so) < 1:
+        raise CobevtHipError("sparse_downsample: a %s level has no output under kernel %s, stride %s, padding %s" % (x.spatial_shape, k, s, p))
+    n, dev = x.batch_size, x.indices.device
+    if capacity is None:
+        fan = 1
+        for kk, ss in zip(k, s):
+            fan *= (kk + ss - 1) // ss
+        capacity = min(n * so[0] * so[1] * so[2], fan * x.capacity)
+    cap = int(capacity)
+    if cap < 1:
+        raise CobevtHipError("sparse_downsample: capacity must be >= 1, got %d" % cap)
+    workspace = _sparse_ws(workspace, dev, n, so, "sparse_downsample")
+    indices = torch.empty((cap, 4), device=dev, dtype=torch.int32)
+    num = torch.empty((2,), device=dev, dtype=torch.int32)
+    dims = (ctypes.c_long * 15)(n, *(x.spatial_shape + (x.capacity, cap) + k + s + p))
+    cells = n * so[0] * so[1] * so[2]
+    with _timed("sparse_downsample|%dx%dx%d" % so, lambda: (0.0, 16.0 * x.capacity + cells / 8.0 * 5 + 16.0 * cap)):
+        _L.call("cobevt_sparse_downsample", _p(x.indices), _p(x.num), _p(workspace), _p(indices), _p(num), dims, _stream())
+    return SparseConvTensor(None, indices, num, so, n, workspace)
+
+
+class SparseConvPlan(object):
+    """spconv's SubMConv3d / SparseConv3d (bias=False) + the eval BatchNorm1d + ReLU that follow it, lowered to cobevt_sparse_conv:
+    `wgt` [taps][Cout padded to 32][Cin padded to the 32-byte row] = weight[co, kz, ky, kx, ci] * bn_scale[co] (folded in float64,
+    then rounded to the compute dtype), tap = (kz KY + ky) KX + kx, and `shift` fp32 [Cout padded].  weight: (Cout, kz, ky, kx, Cin),
+    the spconv 2.x layout; the sum is a cross-correlation (input cell = stride * output cell - padding + tap).  subm: the output set
+    is the input set (kernel 3, stride 1, padding 1).  device="cpu" builds the same tensors without a GPU."""
+
+    PAIRS = ((16, 16), (16, 32), (32, 32), (32, 64), (64, 64), (64, 128))
+
+    def __init__(self, weight, bn=None, stride=1, padding=0, subm=False, dtype=torch.bfloat16, device="cuda"):
+        if weight.dim() != 5:
+            raise CobevtHipError("SparseConvPlan: weight must be (Cout, kz, ky, kx, Cin), got %s" % (tuple(weight.shape),))
+        cout, kz, ky, kx, cin = (int(d) for d in weight.shape)
+        self.kernel, self.stride, self.padding, self.subm = (kz, ky, kx), _triple(stride), _triple(padding), bool(subm)
+        self.dtype, self.code = dtype, dcode(dtype)
+        if self.subm and (self.kernel, self.stride, self.padding) != ((3, 3, 3), (1, 1, 1), (1, 1, 1)):
+            raise CobevtHipError("SparseConvPlan: SubMConv3d is supported with kernel 3, stride 1, padding 1, got %s / %s / %s"
+                                 % (self.kernel, self.stride, self.padding))
+        if self.kernel not in ((3, 3, 3), (3, 1, 1)) or self.stride not in ((1, 1, 1), (2, 2, 2), (2, 1, 1)) \
+                or self.padding not in ((1, 1, 1), (0, 1, 1), (0, 0, 0)) or (self.kernel == (3, 1, 1) and self.padding != (0, 0, 0)):
+            raise CobevtHipError("SparseConvPlan: kernel 3 or (3, 1, 1), stride 1, 2 or (2, 1, 1) and padding 1, (0, 1, 1) or 0 are "
+                                 "supported, got %s / %s / %s" % (self.kernel, self.stride, self.padding))
+        if not ((cin <= 8 and cout == 16) or (cin, cout) in self.PAIRS):
+            raise CobevtHipError("SparseConvPlan: %d -> %d channels; supported are <= 8 -> 16 and %s" % (cin, cout, ", ".join("%d -> %d" % p for p in self.PAIRS)))
+        w = weight.detach().double().cpu()
+        shift = torch.zeros(cout, dtype=torch.float64)
+        if bn is not None:
+            sc, shift = (t.cpu() for t in bn_affine(bn))
+            w = w * sc[:, None, None, None, None]
+        self.cin, self.cout, self.taps = cin, cout, kz * ky * kx
+        self.cin_pad, self.cout_pad = sparse_row_channels(cin, dtype), (cout + 31) // 32 * 32
+        wk = torch.zeros(self.taps, self.cout_pad, self.cin_pad, dtype=torch.float64)
+        wk[:, :cout, :cin] = w.permute(1, 2, 3, 0, 4).reshape(self.taps, cout, cin)
+        sh = torch.zeros(self.cout_pad, dtype=torch.float64)
+        sh[:cout] = shift
+        self.wgt = wk.to(torch.float32).to(dtype).to(device).contiguous()
+        self.shift = sh.to(torch.float32).to(device).contiguous()
+
+
+def sparse_conv3d(x, plan, capacity=None, workspace=None, out_level=None):
+    """One SubMConv3d / SparseConv3d + BatchNorm + ReLU of the plan over the SparseConvTensor x (cobevt_sparse_conv): one launch,
+    output-stationary (no floating-point atomics, bitwise reproducible), taps that no row of a 32-row tile has are skipped.
+    x.features (rows, plan.cin_pad) contiguous in plan.dtype.  SubM: the result shares x's indices / num / workspace.  Strided: the
+    output level comes from sparse_downsample(x, ..., capacity, workspace) first (two calls), or is `out_level` if the caller has it.
+    -> SparseConvTensor with features (capacity, Cout); rows at or past num[0] are not written."""
+    p = plan
+    f = x.features
+    if f is None or f.dim() != 2 or f.shape[1] != p.cin_pad or f.dtype != p.dtype or not f.is_contiguous():
+        raise CobevtHipError("sparse_conv3d: x.features must be contiguous (rows, %d) %s for this plan, got %s"
+                             % (p.cin_pad, p.dtype, None if f is None else "%s %s" % (f.dtype, tuple(f.shape))))
+    _need_cuda(f, x.indices, x.num, x.workspace, x.row_map, p.wgt, p.shift)
+    if x.row_map is None and f.shape[0] != x.capacity:
+        raise CobevtHipError("sparse_conv3d: x.features has %d rows, the level's capacity is %d" % (f.shape[0], x.capacity))
+    if p.subm:
+        level = x
+    elif out_level is not None:
+        level = out_level
+        if level.spatial_shape != sparse_out_shape(x.spatial_shape, p.kernel, p.stride, p.padding) or level.batch_size != x.batch_size:
+            raise CobevtHipError("sparse_conv3d: out_level is %s, the plan's output on %s is %s"
+                                 % (level.spatial_shape, x.spatial_shape, sparse_out_shape(x.spatial_shape, p.kernel, p.stride, p.padding)))
+    else:
+        level = sparse_downsample(x, p.kernel, p.stride, p.padding, capacity, workspace)
+    cap = level.capacity
+    out = torch.empty((cap, p.cout), device=f.device, dtype=p.dtype)
+    dims = (ctypes.c_long * 18)(p.code, x.batch_size, *(x.spatial_shape + (f.shape[0], cap, p.cin_pad, p.cout) + p.kernel + p.stride + p.padding))
+
+    def cost():       # an upper bound: the live rows and the taps present are known on the device only
+        esz = f.element_size()
+        return 2.0 * cap * p.taps * p.cin_pad * p.cout, float(esz * (cap * p.taps * p.cin_pad + p.wgt.numel() + cap * p.cout))
+
+    fam = "sparse_conv|%s k%d%d%d s%d%d%d %d->%d %dx%dx%d" % (("subm" if p.subm else "spconv",) + p.kernel + p.stride + (p.cin, p.cout) + level.spatial_shape)
+    with _timed(fam, cost):
+        _L.call("cobevt_sparse_conv", _p(f), _p(x.workspace), _p(x.num), _p(x.row_map), _p(level.indices), _p(level.num), _p(p.wgt),
+                _p(p.shift), _p(out), dims, _stream())
+    return SparseConvTensor(out, level.indices, level.num, level.spatial_shape, level.batch_size, level.workspace)
+
+
+def sparse_dense_nhwc(x):
+    """SparseConvTensor -> (N, H, W, C D) in the features' dtype, channel index c D + d, zero off the active set: the NHWC form of
+    HeightCompression's dense().view(N, C D, H, W) (cobevt_sparse_dense: a clear launch and a scatter launch)"""
+    f = x.features
+    if f is None or f.dim() != 2 or f.shape[0] != x.capacity or not f.is_contiguous() or x.row_map is not None:
+        raise CobevtHipError("sparse_dense: the tensor needs contiguous features (capacity, C) in the level's row order")
+    _need_cuda(f, x.indices, x.num)
+    n, (d, h, w), c = x.batch_size, x.spatial_shape, int(f.shape[1])
+    out = torch.empty((n, h, w, c * d), device=f.device, dtype=f.dtype)
+    dims = (ctypes.c_long * 7)(dcode(f.dtype), n, d, h, w, x.capacity, c)
+    with _timed("sparse_dense|%dx%dx%d C%d" % (d, h, w, c), lambda: (0.0, float(f.element_size() * (out.numel() + 2 * f.numel())))):
+        _L.call("cobevt_sparse_dense", _p(f), _p(x.indices), _p(x.num), _p(out), dims, _stream())
+    return out
+
+
+def sparse_dense(x):
+    """spconv's SparseConvTensor.dense(): (N, C, D, H, W), zero off the active set - a VIEW of sparse_dense_nhwc's memory, laid out so
+    that .view(N, C * D, H, W) works on it and is channels-last (what BaseBEVBackbone reads without a copy)"""
+    y = sparse_dense_nhwc(x)
+    n, h, w, cd = y.shape
+    d = x.spatial_shape[0]
+    return y.view(n, h, w, cd // d, d).permute(0, 3, 4, 1, 2)
+
+
 PIL_PRECISION_BITS = 22    # Pillow's 8-bit resample: 32 - 8 - 2 bits of coefficient
 PIL_MAX_TAPS = 17          # taps per output index cobevt_resize_pil_u8 takes: a down-scale of at most 8
 BEV_MAX_CLASSES = 16       # label bits cobevt_decode_bev unpacks

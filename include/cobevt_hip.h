@@ -1060,6 +1060,53 @@ int cobevt_bev_post(const float* const* cls, const float* const* reg, const floa
                     const double* params, float score_threshold, float nms_thresh, float* boxes, float* scores, int* index, int* count,
                     void* workspace, hipStream_t stream);
 
+/*
+ * The sparse 3-D voxel backbone (csrc/sparse_conv.hpp, compiled into voxelize; identical in every library): OpenCOOD's MeanVFE,
+ * VoxelBackBone8x (spconv's SubMConv3d / SparseConv3d + BatchNorm1d + ReLU) and HeightCompression (SparseConvTensor.dense).
+ * dtype: 0 = bf16 storage (bf16 MFMA, fp32 accumulation), 1 = fp32 storage (the exact fp32 MFMA, in all three libraries).  Every
+ * `dims` is a host array of longs.  All of them: no host read, no allocation, no floating-point atomics, bitwise reproducible; scalar
+ * arguments are validated before anything is launched (null: code 1; shape, alignment, unsupported layer: code 2).
+ *
+ * A LEVEL is a sparse shape (N, D, H, W), N D H W < 2^31 - 32768, with an active set.  Its index is one int32 workspace of
+ * cobevt_sparse_scratch([N, D, H, W]) ints, 16-byte aligned, contents irrelevant on entry (a bit per cell, a popcount prefix per
+ * 32-bit word, the scan's partials), plus caller-owned indices (capacity, 4) int32 [b, z, y, x] and num (2) int32 = [live rows,
+ * dropped rows].  Rows are ordered by the cell index ((b D + z) H + y) W + x.  Active cells past the capacity are dropped from the
+ * high end of that order - never written, inactive to every later lookup - and counted in num[1]; num[0] = min(active, capacity).
+ * Launches are sized by capacities and read num on the device.
+ *
+ * cobevt_mean_vfe: voxel_features (P, T, C) fp32, voxel_num_points (P) int32, voxel_coords (P, 4) int32 or null -> out (P, Cpad) in
+ *   dtype: the sum of the first n = voxel_num_points point slots in slot order, divided by max(n, 1) (correctly rounded); channels
+ *   C .. Cpad - 1 and rows with voxel_coords[p][0] < 0 (padding rows) are 0.  dims = [dtype, P, T, C, Cpad], C <= Cpad <= 64.  One launch.
+ * cobevt_sparse_index: voxel_coords (P, 4) int32 [b, z, y, x] -> the level's index, and source (capacity) int32: source[row] = the
+ *   LOWEST input row of that cell (rows >= num[0]: not meaningful).  Rows with b < 0 or a coordinate outside the shape are ignored.
+ *   dims = [N, D, H, W, P, capacity].  Six launches (clear, mark, count, scan, emit, source), no memset node.
+ * cobevt_sparse_downsample: the output level of SparseConv3d(kernel, stride, pad) over an input level's (in_indices, in_num):
+ *   output shape floor((n + 2 pad - kernel) / stride) + 1 per axis, a cell active when any input of its receptive field is.
+ *   `workspace`, indices, num are the OUTPUT level's.  dims = [N, D, H, W of the input, input capacity, output capacity, kernel z y x,
+ *   stride z y x, pad z y x]; kernel 3 3 3 or 3 1 1 (pad 0 only), stride 1 1 1 / 2 2 2 / 2 1 1, pad 1 1 1 / 0 1 1 / 0 0 0.
+ * cobevt_sparse_conv: out[r] = relu(bias + sum over taps k of W'[k] in[row(stride o_r - pad + k)]), r < out_num[0], for SubMConv3d
+ *   (the output level IS the input level: pass its indices / num as out_indices / out_num, kernel 3, stride 1, pad 1) and SparseConv3d
+ *   (out_indices / out_num from cobevt_sparse_downsample).  in (input feature rows, input row) in dtype, rows ordered as the input
+ *   level's - or, with row_map (source of cobevt_sparse_index), in the caller's order: row r of the level reads in[row_map[r]].
+ *   in_workspace / in_num: the INPUT level's.  weight [taps][Cout padded to 32][input row] in dtype, tap = (kz KY + ky) KX + kx, with the
+ *   BatchNorm scale folded in; bias (Cout padded to 32) fp32; out (output capacity, Cout) in dtype, rows >= out_num[0] NOT written.
+ *   dims = [dtype, N, D, H, W of the input, input feature rows, output capacity, input row in channels, Cout, kernel, stride, pad].
+ *   Channel pairs (input row -> Cout): bf16 16 -> 16 | 32, 32 -> 32 | 64, 64 -> 64 | 128; fp32 the same and 8 -> 16 | 32 (narrower
+ *   inputs are zero-padded to the 32-byte row by the caller).  One launch: 128 output rows per workgroup, the rows x taps neighbour
+ *   table in LDS, one ballot per tap and 32-row tile skips absent taps.
+ * cobevt_sparse_dense: rows -> out (N, H, W, C D) in dtype, channel index c D + d, zero elsewhere (NHWC of dense().view(N, C D, H, W)).
+ *   dims = [dtype, N, D, H, W, capacity, C]; out 16-byte aligned.  Two launches (clear, scatter), no memset node.
+ */
+int cobevt_mean_vfe(const float* voxel_features, const int* voxel_num_points, const int* voxel_coords, void* out, const long* dims,
+                    hipStream_t stream);
+int cobevt_sparse_scratch(const long* dims, long* workspace_ints);
+int cobevt_sparse_index(const int* voxel_coords, int* workspace, int* indices, int* num, int* source, const long* dims, hipStream_t stream);
+int cobevt_sparse_downsample(const int* in_indices, const int* in_num, int* workspace, int* indices, int* num, const long* dims,
+                             hipStream_t stream);
+int cobevt_sparse_conv(const void* in, const int* in_workspace, const int* in_num, const int* row_map, const int* out_indices,
+                       const int* out_num, const void* weight, const float* bias, void* out, const long* dims, hipStream_t stream);
+int cobevt_sparse_dense(const void* features, const int* indices, const int* num, void* out, const long* dims, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
