@@ -9,8 +9,8 @@ becomes.  csrc/f32_matrix.hpp is the only file that says so, and the include gra
     "fp32_split" compute mode of host.set_compute_dtype) and with the third's into csrc/f32h/ (ONE fp16 MFMA, the weight operand
     as a single fp16 term: the ResNet encoder's library under "fp32_fast");
   * every other source is SHARED: compiled once into csrc/, without any such flag, and that one object is linked into all three.
-Nothing lists the variant sources: variant_sources() derives them from the #include lines (nine of the 36 at present, so a clean
-build is 27 + 3 x 9 = 54 hipcc runs), and tests/test_build_plan.py pins the set.
+Nothing lists the variant sources: variant_sources() derives them from the #include lines (ten of the 44 at present, so a clean
+build is 34 + 3 x 10 = 64 hipcc runs), and tests/test_build_plan.py pins the set.
 
 An object is rebuilt when its source or a header in ITS OWN include closure is newer.  Each library links an explicit object
 list in SOURCES order, never a directory's contents.  plan() returns all of this without running the compiler.
@@ -25,7 +25,7 @@ CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB = os.path.join(CSRC, "libcobevt_hip.so")
 LIB_F32S = os.path.join(CSRC, "libcobevt_hip_f32s.so")
 LIB_F32H = os.path.join(CSRC, "libcobevt_hip_f32h.so")
-SOURCES = ["igemm.hip", "conv3x3.hip", "basicblock.hip", "bottleneck.hip", "bottleneck_f32.hip", "gemm_rows.hip", "gemm_rows3.hip", "gemm_rows3_f32.hip", "bev_query.hip", "row_chain.hip", "row_chain_f32.hip", "row_chain64.hip", "ln_linear64.hip", "proj_chain128.hip", "proj_chain_k.hip", "swap_stage.hip", "stem7x7.hip", "attention.hip", "attention_resident.hip", "attention_bwd.hip", "train_rows.hip", "train_glue.hip", "train_prep.hip", "wgrad3.hip", "train_nusc.hip", "train_fax.hip", "elementwise.hip", "pairwise_fusion.hip", "postprocess.hip", "depthwise.hip", "peer_gather.hip", "calibrate.hip", "pillar_vfe.hip", "train_pillar.hip", "voxelize.hip", "detect_post.hip"]
+SOURCES = ["igemm.hip", "conv3x3.hip", "basicblock.hip", "bottleneck.hip", "bottleneck_f32.hip", "gemm_rows.hip", "gemm_rows3.hip", "gemm_rows3_f32.hip", "bev_query.hip", "row_chain.hip", "row_chain_f32.hip", "row_chain64.hip", "ln_linear64.hip", "proj_chain128.hip", "proj_chain_k.hip", "swap_stage.hip", "stem7x7.hip", "attention.hip", "attention_resident.hip", "attention_bwd.hip", "train_rows.hip", "train_glue.hip", "train_prep.hip", "wgrad3.hip", "train_nusc.hip", "train_fax.hip", "elementwise.hip", "pairwise_fusion.hip", "postprocess.hip", "depthwise.hip", "peer_gather.hip", "calibrate.hip", "pillar_vfe.hip", "train_pillar.hip", "voxelize.hip", "detect_post.hip", "sparse_conv.hip", "cloud_prep.hip", "bev_points.hip", "detect_targets.hip", "bev_labels.hip", "image_ingest.hip", "deconv.hip", "att_fuse.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-pass-failed"]
 MAX_JOBS = 16  # hipcc processes at a time
 
@@ -78,7 +78,7 @@ def _obj(objdir, src):
 
 def plan(force=False):
     """The build without running it: (jobs, links).  jobs = [(source, object path, flags)], one per stale object (every object
-    with `force`); links = [(library, its 36 objects in SOURCES order)] for the three libraries."""
+    with `force`); links = [(library, its objects in SOURCES order)] for the three libraries."""
     variant = set(variant_sources())
     jobs, links = {}, []          # jobs by object path: a shared object is asked for by all three libraries and built once
     for lib, sub, extra in LIBRARIES:

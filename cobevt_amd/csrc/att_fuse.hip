@@ -1,6 +1,6 @@
 // AttFusion (fusion_modules/self_attn.py:36-57) on channels-last maps: per pixel, scaled-dot-product attention over the agents of a
-// sample, of which the reference keeps row 0 (the ego's).  Included by pairwise_fusion.hip only (its sample_rows / group_ok / 8
-// channels per lane); no matrix product, so the one shared object serves all three libraries.
+// sample, of which the reference keeps row 0 (the ego's).  sample_rows / group_ok / 8 channels per lane are warp_common.hpp's, shared
+// with pairwise_fusion.hip; no matrix product, so the one shared object serves all three libraries.
 //
 //   x (N, HW, C), out (B, HW, C);  sample b owns agent rows off .. off + n - 1 (off = sum record_len[:b]):
 //   s_j = <x[off, p], x[off + j, p]> * scale,  w = softmax_j(s),  out[b, p] = sum_j w_j x[off + j, p]
@@ -9,7 +9,6 @@
 // and the xor butterfly below stays inside it.  The ego row stays in registers, every agent row is loaded once (16-byte loads, the
 // next one in flight while this one is folded in), the softmax is online with a running maximum, all arithmetic is fp32 with the
 // accurate expf, and the result is rounded once to the storage type.  The op is memory-bound: n C in, C out per pixel.
-#pragma once
 #include "warp_common.hpp"
 
 namespace cobevt {
@@ -76,3 +75,18 @@ __global__ __launch_bounds__(256) void att_fuse_kernel(const T* x, const int* re
 
 }  // namespace
 }  // namespace cobevt
+
+using namespace cobevt;
+
+extern "C" int cobevt_att_fuse_nhwc(const void* x, const int* record_len, void* out, int dtype, int B, int N, long HW, int C, float scale,
+                                    hipStream_t stream) {
+    if (!x || !record_len || !out) return COBEVT_ERR_ARG;
+    if (dtype != 0 && dtype != 1) return COBEVT_ERR_ARG;
+    if (!group_ok(C) || B < 1 || B > 65535 || N < 1 || HW < 1) return COBEVT_ERR_SHAPE;
+    const long blocks = (HW * (C >> 3) + 255) / 256;
+    if (blocks > 0x7fffffffL) return COBEVT_ERR_SHAPE;
+    const dim3 grid((unsigned)blocks, (unsigned)B);
+    if (dtype == 0) hipLaunchKernelGGL(att_fuse_kernel<bf16_t>, grid, dim3(256), 0, stream, (const bf16_t*)x, record_len, (bf16_t*)out, N, HW, C, scale);
+    else hipLaunchKernelGGL(att_fuse_kernel<float>, grid, dim3(256), 0, stream, (const float*)x, record_len, (float*)out, N, HW, C, scale);
+    return cobevt::launch_status();
+}

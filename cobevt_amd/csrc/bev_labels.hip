@@ -1,12 +1,11 @@
-// PIXOR-style per-pixel detection maps (gfx950), included by detect_post.hip only (after DetSrc / DetWs and the rounded fp32 helpers):
-// OpenCOOD's LidarBevPostprocessor.generate_label for a batch, and the decode launch of its post_process.  The selection of the 1000
-// best, the fp64 quad clip and the greedy NMS behind the decode are detect_post.hip's own launches - nothing of them is copied here.
+// PIXOR-style per-pixel detection label maps (gfx950): OpenCOOD's LidarBevPostprocessor.generate_label for a batch.  The other
+// direction, its post_process, is the bev mode of detect_post.hip (cobevt_bev_post).
 //
 // Labels (lidar_bev_postprocessor.py generate_label / update_label_map / normalize_targets, box_utils.get_points_in_rotated_box),
 // per sample b: gt (G, 7) fp32 [x, y, z, dx, dy, dz, yaw] in 'lwh' order, G <= 128 slots of which the ones with mask == 1 are valid,
 // compacted in slot order as `gt_box_center[mask == 1]` does.
 //   corners     0 .. 3 of boxes_to_corners_3d(order = 'lwh') in separately rounded fp32, as the reference's torch fp32 chain makes
-//               them (box_footprint_corner of detect_targets.hpp, the function cobevt_boxes_standup uses); cos / sin of the yaw are
+//               them (box_footprint_corner of detect_common.hpp, the function cobevt_boxes_standup uses); cos / sin of the yaw are
 //               the fp64 functions rounded to fp32: the correctly rounded values, which is what a good host cosf returns
 //   after that  fp64 in the reference's operation order: corner_dist = (corner - origin) / res / downsample_rate; integer pixel
 //               (i, j) belongs to a box when l = (p_rel . edge) / (edge . edge) lies in [0, 1] INCLUSIVE for the edges c1 - c0 and
@@ -19,80 +18,10 @@
 // One launch, one thread per label pixel, no atomics: the first G threads of each workgroup build the per-box constants (c0, the two
 // edges, their squared norms, the six targets) once into LDS; workgroup 0 of a sample also writes bev_corners (valid boxes
 // compacted to the front, zero rows behind them) and num_valid.
-//
-// Decode (post_process / reg_map_to_bbx_corners / boxes2d_to_corners2d / project_points_by_matrix_torch), one thread per pixel of
-// every cav: prob = sigmoid(cls) in fp32; a pixel is a candidate when prob > score_threshold and all its decoded values are finite.
-//   fp64        reg * std + mean (the reference multiplies an fp32 map by float64 arrays: promoted), atan2, exp, the centre
-//               (float)(L1 + i * res * rate) + x (torch.arange(dtype = float32) rounds the grid to fp32), the template times the sizes
-//   fp32        rotate_points_along_z_2d casts points and rotation matrix to fp32: the half sizes and the fp64 cos / sin are
-//               rounded to fp32 and the rotation is separately rounded fp32 products and sums; `corners2d += centre` adds the fp64
-//               centre to the fp32 tensor in place: one fp64 add rounded to fp32; the projection by the cav's matrix is the fp32
-//               chain of det_corners with z = 0
-//   kept fp64   nothing beyond the reference: cos / sin are evaluated in fp64 and rounded, exactly where the reference's `.float()` is
-// The candidate key is detect_post.hip's: (ordered score bits << 32) | ~global pixel index, cav 0's pixels in (i, j) order first.
-#pragma once
-#include "common.hpp"
+#include "detect_common.hpp"           // kTgtMaxGt and box_footprint_corner (detect_targets.hip), bev_params_ok (detect_post.hip)
 
 namespace cobevt {
 
-// ---------------------------------------------------------------------------------------------- decode
-// corners of global pixel g -> co[k * 3 + {0, 1, 2}] for k = 0 .. 3 (z = 0), zeros for k = 4 .. 7; false when a value is not finite
-__device__ __forceinline__ bool bev_decode(const DetSrc& s, int g, float* co) {
-#pragma clang fp contract(off)
-    const int c = det_cav_of(s, g), p = g - s.start[c];
-    const int ly = s.W[c];
-    const int i = p / ly, j = p - i * ly;
-    const long plane = (long)s.H[c] * ly;
-    const float* __restrict__ r = s.rm[c] + p;
-    double v[6];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) v[k] = (double)r[k * plane] * s.bev_std[k] + s.bev_mean[k];
-    const double yaw = atan2(v[1], v[0]);
-    const double dx = exp(v[4]), dy = exp(v[5]);
-    const double cell = s.bev_res * s.bev_rate;
-    const double cx = (double)(float)(s.bev_x0 + (double)i * cell) + v[2];
-    const double cy = (double)(float)(s.bev_y0 + (double)j * cell) + v[3];
-    const float sx = (float)(dx * 0.5), sy = (float)(dy * 0.5);
-    const float cs = (float)cos(yaw), sn = (float)sin(yaw);
-    const float* __restrict__ T = s.matrices + 16 * c;
-    bool finite = true;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const float x = k < 2 ? sx : -sx, y = (k == 1 || k == 2) ? sy : -sy;
-        const float rx = add(mul(x, cs), mul(y, -sn)), ry = add(mul(x, sn), mul(y, cs));
-        const float X = (float)((double)rx + cx), Y = (float)((double)ry + cy);
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            const float o = add(add(add(mul(T[4 * q], X), mul(T[4 * q + 1], Y)), mul(T[4 * q + 2], 0.f)), T[4 * q + 3]);
-            finite = finite && isfinite(o);
-            co[k * 3 + q] = o;
-        }
-        co[k * 3 + 2] = 0.f;
-    }
-#pragma unroll
-    for (int q = 12; q < 24; ++q) co[q] = 0.f;
-    return finite;
-}
-
-__global__ __launch_bounds__(256) void bev_decode_kernel(DetSrc s, DetWs ws, int total) {
-    const int g = blockIdx.x * 256 + threadIdx.x;
-    if (g >= total) return;
-    const int c = det_cav_of(s, g);
-    const float logit = s.psm[c][g - s.start[c]];
-    const float score = __fdiv_rn(1.f, add(1.f, expf(-logit)));
-    bool keep = score > s.score_threshold;           // false for a NaN score
-    if (keep) {
-        float co[24];
-        keep = bev_decode(s, g, co);
-    }
-    if (keep) {
-        const unsigned long long key = ((unsigned long long)ordered_bits(score) << 32) | (unsigned)~(unsigned)g;
-        const int slot = atomicAdd(&ws.counters[0], 1);
-        if (slot < total) ws.cand[slot] = key;       // slot < total always: one append per pixel at most
-    }
-}
-
-// ---------------------------------------------------------------------------------------------- labels
 struct BevLabelArgs {
     int B, G, lx, ly;
     double x0, y0, res, rate, mean[6], std[6];
@@ -176,14 +105,23 @@ __global__ __launch_bounds__(256) void bev_labels_kernel(const float* __restrict
     for (int k = 1; k < 7; ++k) dst[(long)k * plane] = (float)((out[k] - a.mean[k - 1]) / a.std[k - 1]);
 }
 
-// params: [L1, W1, res, downsample_rate, target_mean (6), target_std_dev (6)]
-static bool bev_params_ok(const double* q) {
-    for (int k = 0; k < 16; ++k)
-        if (!(q[k] == q[k]) || q[k] - q[k] != 0.0) return false;                    // finite
-    if (!(q[2] > 0.0) || !(q[3] > 0.0)) return false;
-    for (int k = 10; k < 16; ++k)
-        if (q[k] == 0.0) return false;
-    return true;
-}
-
 }  // namespace cobevt
+
+using namespace cobevt;
+
+extern "C" int cobevt_bev_labels(const float* gt_boxes, const float* mask, float* label_map, float* bev_corners, int* num_valid,
+                                 const int* dims, const double* params, hipStream_t stream) {
+    if (!dims || !params || !label_map || !num_valid) return COBEVT_ERR_ARG;
+    const long B = dims[0], G = dims[1], lx = dims[2], ly = dims[3];
+    if (G < 0 || G > kTgtMaxGt) return COBEVT_ERR_SHAPE;
+    if (G > 0 && (!gt_boxes || !mask || !bev_corners)) return COBEVT_ERR_ARG;
+    if (B < 1 || B > 65535 || lx < 1 || ly < 1 || lx > 0x7fffffffL / ly || lx * ly > (0x7fffffffL / 8) / B) return COBEVT_ERR_SHAPE;
+    if (!bev_params_ok(params)) return COBEVT_ERR_SHAPE;
+    BevLabelArgs a;
+    a.B = (int)B; a.G = (int)G; a.lx = (int)lx; a.ly = (int)ly;
+    a.x0 = params[0]; a.y0 = params[1]; a.res = params[2]; a.rate = params[3];
+    for (int k = 0; k < 6; ++k) { a.mean[k] = params[4 + k]; a.std[k] = params[10 + k]; }
+    hipLaunchKernelGGL(bev_labels_kernel, dim3((unsigned)((lx * ly + 255) / 256), (unsigned)B), dim3(256), 0, stream, gt_boxes, mask,
+                       label_map, bev_corners, num_valid, a);
+    return cobevt::launch_status();
+}

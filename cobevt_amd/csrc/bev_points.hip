@@ -1,8 +1,8 @@
-// LiDAR points -> PIXOR's `bev_input` (gfx950), included by voxelize.hip only: OpenCOOD's BevPreprocessor.preprocess for N agents.
+// LiDAR points -> PIXOR's `bev_input` (gfx950): OpenCOOD's BevPreprocessor.preprocess for N agents.
 // points (M, 4) fp32 [x, y, z, intensity] (rows offsets[a] .. offsets[a + 1] of agent a, device int32) -> bev (N, C, nx, ny) fp32, or
 // (N, nx, ny, C) with channels_last: channels 0 .. C - 2 are the binary occupancy of the height slices, channel C - 1 the mean
-// intensity of the cell's points.  The point masks and the offsets convention are voxelize.hip's: the device functions below are the
-// ones its classify launch calls.
+// intensity of the cell's points.  The point masks and the offsets convention are voxelize.hip's: the device functions of
+// points_common.hpp are the ones its classify launch calls.
 //
 // Semantics (bev_preprocessor.py :29-47, per agent):
 //   index     trunc(((double)p - origin) / res) per axis: fp64 arithmetic on the fp32 point, as numpy promotes `pcd_raw[:, :3] -
@@ -27,28 +27,9 @@
 // The two words of a cell live in separate arrays (voxelize.hip measured a cell's atomics' words in one record at 166 us against
 // 97 us); this kernel itself has not been timed.
 // No floating-point atomics, no host read-back, no allocation: the workspace comes from the caller (cobevt_bev_points_scratch).
-#pragma once
-#include "common.hpp"
+#include "points_common.hpp"
 
 namespace cobevt {
-
-__device__ __forceinline__ long clamp_offset(int o, long M) { return o < 0 ? 0 : (o > M ? M : (long)o); }
-
-// the agent that owns row i (-1: none): rows offsets[a] .. offsets[a + 1], offsets clamped to [0, M]
-__device__ __forceinline__ int point_agent(const int* __restrict__ offsets, int N, long i, long M) {
-    int agent = -1;
-    for (int k = 0; k < N; ++k)
-        if (agent < 0 && i >= clamp_offset(offsets[k], M) && i < clamp_offset(offsets[k + 1], M)) agent = k;
-    return agent;
-}
-
-// pcd_utils.mask_points_by_range (:54-58, strict inequalities) and mask_ego_points (:79-80), each when its flag is set
-__device__ __forceinline__ bool point_masks_keep(const float4 p, const float* lo, const float* hi, int range_mask, int ego_mask) {
-    bool keep = true;
-    if (range_mask) keep = keep && p.x > lo[0] && p.x < hi[0] && p.y > lo[1] && p.y < hi[1] && p.z > lo[2] && p.z < hi[2];
-    if (ego_mask) keep = keep && !(p.x >= -1.95f && p.x <= 2.95f && p.y >= -1.1f && p.y <= 1.1f);
-    return keep;
-}
 
 struct BevPointArgs {
     long M;
@@ -118,3 +99,38 @@ static int bev_points_args(const long* dims, const double* geom, BevPointArgs& a
 }
 
 }  // namespace cobevt
+
+using namespace cobevt;
+
+extern "C" int cobevt_bev_points_scratch(const long* dims, long* workspace_ints) {
+    BevPointArgs a;
+    if (!workspace_ints) return COBEVT_ERR_ARG;
+    const int rc = bev_points_args(dims, nullptr, a);
+    if (rc != COBEVT_OK) return rc;
+    *workspace_ints = bev_points_ws_ints(a);
+    return COBEVT_OK;
+}
+
+extern "C" int cobevt_bev_points(const float* points, const int* point_offsets, float* bev, int* workspace, const long* dims,
+                                 const double* geom, hipStream_t stream) {
+    if (!dims || !geom || !point_offsets || !bev || !workspace) return COBEVT_ERR_ARG;
+    BevPointArgs a;
+    const int rc = bev_points_args(dims, geom, a);
+    if (rc != COBEVT_OK) return rc;
+    if (a.M > 0 && !points) return COBEVT_ERR_ARG;
+    if (((uintptr_t)points & 15) || ((uintptr_t)workspace & 7) || ((uintptr_t)bev & 3)) return COBEVT_ERR_SHAPE;
+    if (!(a.res > 0.0) || a.res - a.res != 0.0) return COBEVT_ERR_SHAPE;              // positive and finite
+    for (int j = 0; j < 3; ++j)
+        if (a.origin[j] - a.origin[j] != 0.0) return COBEVT_ERR_SHAPE;
+    const long cells = (long)a.N * a.nx * a.ny;
+    unsigned long long* sum = (unsigned long long*)workspace;
+    int* count = workspace + 2 * cells;
+    if (hipMemsetAsync(bev, 0, 4 * (size_t)cells * a.C, stream) != hipSuccess) return COBEVT_ERR_LAUNCH;
+    if (hipMemsetAsync(workspace, 0, 12 * (size_t)cells, stream) != hipSuccess) return COBEVT_ERR_LAUNCH;
+    const unsigned pb = (unsigned)((a.M + 255) / 256);         // one thread per point
+    if (pb)
+        hipLaunchKernelGGL(bev_points_kernel, dim3(pb), dim3(256), 0, stream, (const float4*)points, point_offsets, bev, sum, count, a);
+    hipLaunchKernelGGL(bev_points_finalise_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, stream, bev,
+                       (const unsigned long long*)sum, (const int*)count, a);
+    return cobevt::launch_status();
+}

@@ -1,4 +1,4 @@
-// Assembly of LiDAR clouds (gfx950), included by voxelize.hip only: what OpenCOOD's datasets do on the host in front of the
+// Assembly of LiDAR clouds (gfx950): what OpenCOOD's datasets do on the host in front of the
 // pre-processors - pcd_utils.mask_ego_points, lidar_project, DataAugmentor's world flip / rotation / scaling, mask_points_by_range and
 // the vstack of the agents' clouds - as one operator in front of cobevt_voxelize_points / cobevt_bev_points.
 // points (M, 4) fp32 [x, y, z, intensity] of N agents in their SENSOR frames (rows offsets[a] .. offsets[a + 1] of agent a, device
@@ -47,8 +47,7 @@
 // then agree with the counts by construction, whatever the compiler makes of the arithmetic in two kernels, so no store can leave
 // out.  The coordinates come from the same contraction-free function in launches 1 and 3.
 // No host read, no allocation (workspace: cobevt_prepare_points_scratch), bitwise reproducible.  M = 0: the scan launch only.
-#pragma once
-#include "bev_points.hpp"
+#include "points_common.hpp"
 
 namespace cobevt {
 
@@ -258,3 +257,42 @@ static int cloud_args(const long* dims, const double* geom, CloudArgs& a) {
 }
 
 }  // namespace cobevt
+
+using namespace cobevt;
+
+extern "C" int cobevt_prepare_points_scratch(const long* dims, long* workspace_ints) {
+    CloudArgs a;
+    if (!workspace_ints) return COBEVT_ERR_ARG;
+    const int rc = cloud_args(dims, nullptr, a);
+    if (rc != COBEVT_OK) return rc;
+    *workspace_ints = cloud_ws_ints(a.M);
+    return COBEVT_OK;
+}
+
+extern "C" int cobevt_prepare_points(const float* points, const int* point_offsets, const double* transforms, const int* order, float* out,
+                                     int* out_offsets, void* boxes, const void* box_mask, int* workspace, const long* dims,
+                                     const double* geom, hipStream_t stream) {
+    if (!dims || !geom || !point_offsets || !out_offsets || !workspace) return COBEVT_ERR_ARG;
+    CloudArgs a;
+    const int rc = cloud_args(dims, geom, a);
+    if (rc != COBEVT_OK) return rc;
+    if (a.M > 0 && (!points || !out)) return COBEVT_ERR_ARG;
+    if (a.G > 0 && (!boxes || !box_mask)) return COBEVT_ERR_ARG;
+    if ((((uintptr_t)points | (uintptr_t)out) & 15) || (((uintptr_t)workspace | (uintptr_t)transforms | (uintptr_t)boxes | (uintptr_t)box_mask) & 7))
+        return COBEVT_ERR_SHAPE;
+    if (((uintptr_t)order | (uintptr_t)point_offsets | (uintptr_t)out_offsets) & 3) return COBEVT_ERR_SHAPE;
+    a.project = transforms != nullptr;
+    a.ordered = order != nullptr;
+    const long nb = cloud_blocks(a.M);
+    unsigned long long* flags = (unsigned long long*)workspace;
+    int* part = workspace + 2 * ((a.M + 63) / 64);
+    if (nb)
+        hipLaunchKernelGGL(cloud_classify_kernel, dim3((unsigned)nb), dim3(256), 0, stream, (const float4*)points, point_offsets, transforms,
+                           order, flags, part, a);
+    hipLaunchKernelGGL(cloud_scan_kernel, dim3(a.G > 0 ? 2u : 1u), dim3(1024), 0, stream, point_offsets, (const unsigned long long*)flags,
+                       part, out_offsets, boxes, box_mask, nb, a);
+    if (nb)
+        hipLaunchKernelGGL(cloud_scatter_kernel, dim3((unsigned)nb), dim3(256), 0, stream, (const float4*)points, point_offsets, transforms,
+                           order, (const unsigned long long*)flags, (const int*)part, (float4*)out, a);
+    return cobevt::launch_status();
+}

@@ -3,7 +3,7 @@
 //
 //   out[n, s*y + dy, s*x + dx, c_off + co] = act(shift[co] + sum_ci in[n, y, x, ci] * W'[(dy*s + dx)*Cout + co][ci])
 //
-// Included by igemm.hip only (after common.hpp and f32_matrix.hpp), so it is built once per library like the rest of that source.
+// An fp32-storage matrix kernel: it includes f32_matrix.hpp, so it is built once per library, like igemm.hip.
 //
 // GEMM view: M = N*H*W input pixels (the NHWC input IS the [M][Cin] matrix), K = Cin, columns = s*s*Cout ordered tap-major, weights
 // [s*s*Cout][Kpad] with the BatchNorm scale folded in.  Cout % 32 == 0, so a 32-column MFMA tile is 32 consecutive output channels of
@@ -19,9 +19,14 @@
 // by 16 bytes; it then reads it back as 16-byte pieces in pixel-major order, so that 4 (bf16) / 8 (fp32) consecutive lanes store one
 // destination pixel's whole 64 / 128-byte run with global_store_dwordx4.  Every destination element of the slice is written exactly
 // once (no atomics, no zero-fill), nothing outside [c_off, c_off + Cout) is touched.
-#pragma once
+#include "common.hpp"
+#include "f32_matrix.hpp"
 
 namespace cobevt {
+
+// this kernel's K-tile in LDS (the layout igemm.hip's loop uses too; the two files need not agree)
+constexpr int kDeconvRowBytes = 80;  // 64 data + 16 pad
+constexpr int kDeconvTileBytes = 64;
 
 struct DeconvParams {
     const void* in;
@@ -39,14 +44,14 @@ template <typename T>
 __global__ __launch_bounds__(256) void deconv_kernel(DeconvParams p) {
     constexpr int BM = kDeconvBM, BN = kDeconvBN;
     constexpr int ES = Elem<T>::kBytes;
-    constexpr int BKE = kTileBytes / ES;
+    constexpr int BKE = kDeconvTileBytes / ES;
     constexpr int CH = Elem<T>::kChunk;
     constexpr int CPP = 32 * ES / 16;          // 16-byte pieces of one pixel's 32-channel run
     constexpr int ST_IT = 32 * CPP / 64;       // store instructions per 32 x 32 tile
     constexpr int ROWB = 32 * ES + 16;         // epilogue staging row: 32 channels + 16 bytes of padding
-    static_assert(4 * 32 * ROWB <= 2 * (BM + BN) * kRowBytes, "the epilogue staging fits the K loop's buffers");
+    static_assert(4 * 32 * ROWB <= 2 * (BM + BN) * kDeconvRowBytes, "the epilogue staging fits the K loop's buffers");
 
-    __shared__ __attribute__((aligned(16))) unsigned char smem[2][(BM + BN) * kRowBytes];
+    __shared__ __attribute__((aligned(16))) unsigned char smem[2][(BM + BN) * kDeconvRowBytes];
 
     // consecutive workgroups: all column tiles of one pixel tile, then the next pixel tile (the pixel panel is re-read from L2)
     const int ntn = (p.NC + BN - 1) / BN;
@@ -78,10 +83,10 @@ __global__ __launch_bounds__(256) void deconv_kernel(DeconvParams p) {
     };
     auto store_tile = [&](int buf) {
         unsigned char* As = smem[buf];
-        unsigned char* Bs = smem[buf] + BM * kRowBytes;
-        *(uint4*)(As + rowp * kRowBytes + j * 16) = stage_x_piece<T>(a_reg);
+        unsigned char* Bs = smem[buf] + BM * kDeconvRowBytes;
+        *(uint4*)(As + rowp * kDeconvRowBytes + j * 16) = stage_x_piece<T>(a_reg);
 #pragma unroll
-        for (int it = 0; it < 2; ++it) *(uint4*)(Bs + (rowp + 64 * it) * kRowBytes + j * 16) = stage_w_piece<T>(b_reg[it]);
+        for (int it = 0; it < 2; ++it) *(uint4*)(Bs + (rowp + 64 * it) * kDeconvRowBytes + j * 16) = stage_w_piece<T>(b_reg[it]);
     };
 
     f32x16 acc[2];
@@ -91,7 +96,7 @@ __global__ __launch_bounds__(256) void deconv_kernel(DeconvParams p) {
         for (int r = 0; r < 16; ++r) acc[b][r] = 0.f;
 
     const int wm = wave >> 1, wn = wave & 1;
-    const int frag_off = (lane & 31) * kRowBytes + (lane >> 5) * 16;
+    const int frag_off = (lane & 31) * kDeconvRowBytes + (lane >> 5) * 16;
 
     load_tile(0);
     store_tile(0);
@@ -99,14 +104,14 @@ __global__ __launch_bounds__(256) void deconv_kernel(DeconvParams p) {
     for (int kt = 0; kt < nk; ++kt) {
         const int buf = kt & 1;
         if (kt + 1 < nk) load_tile(kt + 1);
-        const unsigned char* As = smem[buf] + wm * 32 * kRowBytes + frag_off;
-        const unsigned char* Bs = smem[buf] + (BM + wn * 64) * kRowBytes + frag_off;
+        const unsigned char* As = smem[buf] + wm * 32 * kDeconvRowBytes + frag_off;
+        const unsigned char* Bs = smem[buf] + (BM + wn * 64) * kDeconvRowBytes + frag_off;
 #pragma unroll
         for (int g = 0; g < 2; ++g) {
             const uint4 xs = *(const uint4*)(As + g * 32);
 #pragma unroll
             for (int b = 0; b < 2; ++b) {
-                const uint4 ws = *(const uint4*)(Bs + b * 32 * kRowBytes + g * 32);
+                const uint4 ws = *(const uint4*)(Bs + b * 32 * kDeconvRowBytes + g * 32);
                 mfma_kgroup_staged<T>(ws, xs, acc[b]);       // weights first: D row = channel, D column = pixel (f32_matrix.hpp)
             }
         }
@@ -176,3 +181,30 @@ static int launch_deconv(const DeconvParams& p, hipStream_t stream) {
 }
 
 }  // namespace cobevt
+
+using namespace cobevt;
+
+// C-ABI entry point, see include/cobevt_hip.h
+extern "C" int cobevt_deconv_nhwc(const void* in, const void* wgt, const float* shift, void* out, const int* dims, hipStream_t stream) {
+    // dims: [dtype, N, H, W, Cin, Cout, Kpad, s, c_off, ldc, act]
+    if (!in || !wgt || !shift || !out || !dims) return COBEVT_ERR_ARG;
+    const int dtype = dims[0], N = dims[1];
+    if (dtype != 0 && dtype != 1) return COBEVT_ERR_ARG;
+    DeconvParams p;
+    p.in = in; p.wgt = wgt; p.shift = shift; p.out = out;
+    p.H = dims[2]; p.W = dims[3]; p.Cin = dims[4]; p.Cout = dims[5]; p.Kpad = dims[6];
+    p.s = dims[7]; p.c_off = dims[8]; p.ldc = dims[9]; p.act = dims[10];
+    if (p.act < 0 || p.act > 4) return COBEVT_ERR_ARG;
+    if (N <= 0 || p.H <= 0 || p.W <= 0 || p.Cin <= 0 || p.Cout <= 0) return COBEVT_ERR_SHAPE;
+    if (p.s < 1 || p.s > 8) return COBEVT_ERR_SHAPE;
+    const int bke = dtype == 0 ? 32 : 16, ch = dtype == 0 ? 8 : 4;
+    if (p.Cin % ch != 0 || p.Cout % 32 != 0) return COBEVT_ERR_SHAPE;
+    if (p.Kpad % bke != 0 || p.Kpad < p.Cin) return COBEVT_ERR_SHAPE;
+    // 16-byte stores: the slice starts on an 8-channel boundary of a row whose length is a multiple of 8 channels
+    if (p.c_off < 0 || p.c_off % 8 != 0 || p.ldc % 8 != 0 || (long long)p.c_off + p.Cout > p.ldc) return COBEVT_ERR_SHAPE;
+    const long long M = (long long)N * p.H * p.W;
+    if (M > 0x7fffffffLL - kDeconvBM || M * p.s * p.s > 0x7fffffffLL) return COBEVT_ERR_SHAPE;     // pixel indices are ints
+    p.M = (int)M;
+    p.NC = p.s * p.s * p.Cout;
+    return dtype == 0 ? launch_deconv<bf16_t>(p, stream) : launch_deconv<float>(p, stream);
+}

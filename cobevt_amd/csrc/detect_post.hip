@@ -30,9 +30,9 @@
 //                picked flags and the ordered write, zeros past count
 // No floating-point atomics, no workgroup waits on another, no host read-back, no allocation: the workspace comes from the caller
 // (cobevt_detect_scratch).  The same select / mask / greedy launches serve cobevt_nms_rotated (boxes and scores given, no filters)
-// and cobevt_bev_post (bev_detect.hpp: per-pixel cls / reg maps, its own decode launch, (1000, 4, 2) quads out).
+// and cobevt_bev_post (bev mode: per-pixel cls / reg maps, its own decode launch, (1000, 4, 2) quads out).
 #include "common.hpp"
-#include "detect_targets.hpp"          // the training side: targets and loss (its entry points are at the end of this file)
+#include "detect_common.hpp"           // bev_params_ok, shared with bev_labels.hip
 
 namespace cobevt {
 
@@ -54,7 +54,7 @@ struct DetSrc {
     const float* boxes;
     const float* scores;
     int box_floats, n_boxes;
-    // bev mode (bev != 0, bev_detect.hpp): psm = cls (1, 1, H, W), rm = reg (1, 6, H, W), A = 1; the map geometry and the
+    // bev mode (bev != 0, cobevt_bev_post): psm = cls (1, 1, H, W), rm = reg (1, 6, H, W), A = 1; the map geometry and the
     // regression statistics of LidarBevPostprocessor
     int bev;
     double bev_x0, bev_y0, bev_res, bev_rate, bev_mean[6], bev_std[6];
@@ -142,12 +142,75 @@ __device__ __forceinline__ int det_cav_of(const DetSrc& s, int g) {
     return c;
 }
 
-}  // namespace cobevt
+// ---------------------------------------------------------------------------------------------- bev mode: the decode
+// PIXOR-style per-pixel maps (LidarBevPostprocessor.post_process / reg_map_to_bbx_corners / boxes2d_to_corners2d /
+// project_points_by_matrix_torch; the labels of the same maps are bev_labels.hip), one thread per pixel of every cav: prob =
+// sigmoid(cls) in fp32; a pixel is a candidate when prob > score_threshold and all its decoded values are finite.
+//   fp64        reg * std + mean (the reference multiplies an fp32 map by float64 arrays: promoted), atan2, exp, the centre
+//               (float)(L1 + i * res * rate) + x (torch.arange(dtype = float32) rounds the grid to fp32), the template times the sizes
+//   fp32        rotate_points_along_z_2d casts points and rotation matrix to fp32: the half sizes and the fp64 cos / sin are
+//               rounded to fp32 and the rotation is separately rounded fp32 products and sums; `corners2d += centre` adds the fp64
+//               centre to the fp32 tensor in place: one fp64 add rounded to fp32; the projection by the cav's matrix is the fp32
+//               chain of det_corners with z = 0
+//   kept fp64   nothing beyond the reference: cos / sin are evaluated in fp64 and rounded, exactly where the reference's `.float()` is
+// The candidate key is the cav mode's: (ordered score bits << 32) | ~global pixel index, cav 0's pixels in (i, j) order first.
+// corners of global pixel g -> co[k * 3 + {0, 1, 2}] for k = 0 .. 3 (z = 0), zeros for k = 4 .. 7; false when a value is not finite
+__device__ __forceinline__ bool bev_decode(const DetSrc& s, int g, float* co) {
+#pragma clang fp contract(off)
+    const int c = det_cav_of(s, g), p = g - s.start[c];
+    const int ly = s.W[c];
+    const int i = p / ly, j = p - i * ly;
+    const long plane = (long)s.H[c] * ly;
+    const float* __restrict__ r = s.rm[c] + p;
+    double v[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) v[k] = (double)r[k * plane] * s.bev_std[k] + s.bev_mean[k];
+    const double yaw = atan2(v[1], v[0]);
+    const double dx = exp(v[4]), dy = exp(v[5]);
+    const double cell = s.bev_res * s.bev_rate;
+    const double cx = (double)(float)(s.bev_x0 + (double)i * cell) + v[2];
+    const double cy = (double)(float)(s.bev_y0 + (double)j * cell) + v[3];
+    const float sx = (float)(dx * 0.5), sy = (float)(dy * 0.5);
+    const float cs = (float)cos(yaw), sn = (float)sin(yaw);
+    const float* __restrict__ T = s.matrices + 16 * c;
+    bool finite = true;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const float x = k < 2 ? sx : -sx, y = (k == 1 || k == 2) ? sy : -sy;
+        const float rx = add(mul(x, cs), mul(y, -sn)), ry = add(mul(x, sn), mul(y, cs));
+        const float X = (float)((double)rx + cx), Y = (float)((double)ry + cy);
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            const float o = add(add(add(mul(T[4 * q], X), mul(T[4 * q + 1], Y)), mul(T[4 * q + 2], 0.f)), T[4 * q + 3]);
+            finite = finite && isfinite(o);
+            co[k * 3 + q] = o;
+        }
+        co[k * 3 + 2] = 0.f;
+    }
+#pragma unroll
+    for (int q = 12; q < 24; ++q) co[q] = 0.f;
+    return finite;
+}
 
-#include "bev_detect.hpp"              // the per-pixel (PIXOR) maps: label generation and the bev decode (entry points at the end of this file)
+__global__ __launch_bounds__(256) void bev_decode_kernel(DetSrc s, DetWs ws, int total) {
+    const int g = blockIdx.x * 256 + threadIdx.x;
+    if (g >= total) return;
+    const int c = det_cav_of(s, g);
+    const float logit = s.psm[c][g - s.start[c]];
+    const float score = __fdiv_rn(1.f, add(1.f, expf(-logit)));
+    bool keep = score > s.score_threshold;           // false for a NaN score
+    if (keep) {
+        float co[24];
+        keep = bev_decode(s, g, co);
+    }
+    if (keep) {
+        const unsigned long long key = ((unsigned long long)ordered_bits(score) << 32) | (unsigned)~(unsigned)g;
+        const int slot = atomicAdd(&ws.counters[0], 1);
+        if (slot < total) ws.cand[slot] = key;       // slot < total always: one append per pixel at most
+    }
+}
 
-namespace cobevt {
-
+// ---------------------------------------------------------------------------------------------- decode, select
 __device__ __forceinline__ void det_decode(const DetSrc& s, int g, float* corners) {
     if (s.bev) {                                     // uniform: the same bits as the bev decode launch (same function)
         bev_decode(s, g, corners);
@@ -588,80 +651,6 @@ extern "C" int cobevt_rotated_iou(const float* a, const float* b, double* iou, l
     if (N == 0 || M == 0) return COBEVT_OK;
     if (!a || !b || !iou) return COBEVT_ERR_ARG;
     hipLaunchKernelGGL(det_pair_iou_kernel, dim3((unsigned)((N * M + 255) / 256)), dim3(256), 0, stream, a, b, iou, (int)N, (int)M);
-    return cobevt::launch_status();
-}
-
-// ---------------------------------------------------------------------------------------------- targets and loss (detect_targets.hpp)
-extern "C" int cobevt_boxes_standup(const float* boxes, float* standup, long n, hipStream_t stream) {
-    if (n < 0 || n > 0x7fffffffL / 8) return COBEVT_ERR_SHAPE;
-    if (n == 0) return COBEVT_OK;
-    if (!boxes || !standup) return COBEVT_ERR_ARG;
-    if ((uintptr_t)standup & 15) return COBEVT_ERR_SHAPE;
-    hipLaunchKernelGGL(tgt_standup_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, boxes, standup, n);
-    return cobevt::launch_status();
-}
-
-extern "C" int cobevt_detect_targets(const float* anchors, const float* anchor_standup, const float* gt_boxes, const float* gt_standup,
-                                     const float* mask, float pos_threshold, float neg_threshold, float* pos_equal_one,
-                                     float* neg_equal_one, float* targets, int* num_pos, void* workspace, int B, int H, int W, int A,
-                                     int G, hipStream_t stream) {
-    if (!anchors || !anchor_standup || !pos_equal_one || !neg_equal_one || !targets || !num_pos || !workspace) return COBEVT_ERR_ARG;
-    if (G < 0 || G > kTgtMaxGt) return COBEVT_ERR_SHAPE;
-    if (G > 0 && (!gt_boxes || !gt_standup || !mask)) return COBEVT_ERR_ARG;
-    if (B < 1 || B > 65535 || H < 1 || W < 1 || A < 1 || (long)H > 0x7fffffffL / W || (long)H * W > (0x7fffffffL / 8) / A
-        || (long)H * W * A > (0x7fffffffL / 8) / B)
-        return COBEVT_ERR_SHAPE;
-    if (((uintptr_t)anchor_standup & 15) || ((uintptr_t)gt_standup & 15) || ((uintptr_t)workspace & 7)) return COBEVT_ERR_SHAPE;
-    const int M = H * W * A;
-    unsigned long long* best = (unsigned long long*)workspace;           // (B, max(G, 1)) keys
-    if (hipMemsetAsync(best, 0, 8 * (size_t)B * (G > 0 ? G : 1), stream) != hipSuccess) return COBEVT_ERR_LAUNCH;
-    if (hipMemsetAsync(num_pos, 0, 4 * (size_t)B, stream) != hipSuccess) return COBEVT_ERR_LAUNCH;
-    const dim3 grid((unsigned)((M + 255) / 256), (unsigned)B);
-    if (G > 0) hipLaunchKernelGGL(tgt_best_kernel, grid, dim3(256), 0, stream, anchor_standup, gt_standup, mask, best, M, G);
-    hipLaunchKernelGGL(tgt_label_kernel, grid, dim3(256), 0, stream, anchors, anchor_standup, gt_boxes, gt_standup, mask, best,
-                       pos_equal_one, neg_equal_one, targets, num_pos, M, G, pos_threshold, neg_threshold);
-    return cobevt::launch_status();
-}
-
-extern "C" int cobevt_pointpillar_loss(const float* psm, const float* rm, const float* pos_equal_one, const float* targets,
-                                       const int* num_pos, float* loss, float* dpsm, float* drm, void* workspace, int B, int H, int W,
-                                       int A, float cls_weight, float reg, hipStream_t stream) {
-    if (!psm || !rm || !pos_equal_one || !targets || !loss || !workspace || ((dpsm == nullptr) != (drm == nullptr))) return COBEVT_ERR_ARG;
-    if (B < 1 || B > 65535 || A < 1 || A > 65535 || H < 1 || W < 1 || (long)H > 0x7fffffffL / W || (long)H * W > (0x7fffffffL / 8) / A
-        || (long)H * W * A > (0x7fffffffL / 8) / B)
-        return COBEVT_ERR_SHAPE;
-    if ((uintptr_t)workspace & 7) return COBEVT_ERR_SHAPE;
-    const int HW = H * W, M = HW * A;
-    const long nblk = ppl_blocks(B, HW, A);
-    double* partial = (double*)workspace;                                // 2 nblk doubles, then B ints
-    int* counts = (int*)(partial + 2 * nblk);
-    if (!num_pos) {
-        if (hipMemsetAsync(counts, 0, 4 * (size_t)B, stream) != hipSuccess) return COBEVT_ERR_LAUNCH;
-        hipLaunchKernelGGL(ppl_count_kernel, dim3((unsigned)((M + 255) / 256), (unsigned)B), dim3(256), 0, stream, pos_equal_one, counts, M);
-        num_pos = counts;
-    }
-    hipLaunchKernelGGL(ppl_main_kernel, dim3((unsigned)((HW + 255) / 256), (unsigned)A, (unsigned)B), dim3(256), 0, stream, psm, rm,
-                       pos_equal_one, targets, num_pos, partial, dpsm, drm, HW, A, cls_weight / (float)B, reg / (float)B);
-    hipLaunchKernelGGL(ppl_finish_kernel, dim3(1), dim3(256), 0, stream, (const double*)partial, nblk, loss,
-                       (double)cls_weight / B, (double)reg / B);
-    return cobevt::launch_status();
-}
-
-// ---------------------------------------------------------------------------------------------- per-pixel maps (bev_detect.hpp)
-extern "C" int cobevt_bev_labels(const float* gt_boxes, const float* mask, float* label_map, float* bev_corners, int* num_valid,
-                                 const int* dims, const double* params, hipStream_t stream) {
-    if (!dims || !params || !label_map || !num_valid) return COBEVT_ERR_ARG;
-    const long B = dims[0], G = dims[1], lx = dims[2], ly = dims[3];
-    if (G < 0 || G > kTgtMaxGt) return COBEVT_ERR_SHAPE;
-    if (G > 0 && (!gt_boxes || !mask || !bev_corners)) return COBEVT_ERR_ARG;
-    if (B < 1 || B > 65535 || lx < 1 || ly < 1 || lx > 0x7fffffffL / ly || lx * ly > (0x7fffffffL / 8) / B) return COBEVT_ERR_SHAPE;
-    if (!bev_params_ok(params)) return COBEVT_ERR_SHAPE;
-    BevLabelArgs a;
-    a.B = (int)B; a.G = (int)G; a.lx = (int)lx; a.ly = (int)ly;
-    a.x0 = params[0]; a.y0 = params[1]; a.res = params[2]; a.rate = params[3];
-    for (int k = 0; k < 6; ++k) { a.mean[k] = params[4 + k]; a.std[k] = params[10 + k]; }
-    hipLaunchKernelGGL(bev_labels_kernel, dim3((unsigned)((lx * ly + 255) / 256), (unsigned)B), dim3(256), 0, stream, gt_boxes, mask,
-                       label_map, bev_corners, num_valid, a);
     return cobevt::launch_status();
 }
 

@@ -1,4 +1,4 @@
-// LiDAR detection TARGETS and LOSS (gfx950), included by detect_post.hip only: OpenCOOD's VoxelPostprocessor.generate_label - the
+// LiDAR detection TARGETS and LOSS (gfx950), the training side of detect_post.hip: OpenCOOD's VoxelPostprocessor.generate_label - the
 // anchor-to-ground-truth assignment with the `bbox_overlaps` it needs - and the PointPillar detection loss with its gradient.
 //
 // Targets (voxel_postprocessor.py generate_label, box_utils.py, box_overlaps.pyx), per sample b of a batch, M = H W A anchors in
@@ -25,25 +25,11 @@
 //               d_6 = sin(rm_6) cos(tgt_6) - cos(rm_6) sin(tgt_6); a NaN target counts as d = 0
 // Per-element arithmetic fp32; sums fp64 in a fixed order (a wave butterfly, the four waves of a workgroup in order, one partial
 // pair per workgroup, then one finishing workgroup over the partials): no floating-point atomics, bitwise reproducible.
-#pragma once
-#include "common.hpp"
+#include "detect_common.hpp"           // kTgtMaxGt and box_footprint_corner, shared with bev_labels.hip
 
 namespace cobevt {
 
-constexpr int kTgtMaxGt = 128;
-
 // ---------------------------------------------------------------------------------------------- standup boxes
-// footprint corner k = 0 .. 3 of boxes_to_corners_3d: half sizes (sx, sy) along the box axes, the template [1,-1] [1,1] [-1,1] [-1,-1] / 2,
-// rotate_points_along_z: [x y] [[cos, sin], [-sin, cos]], then the centre - every product and sum a separately rounded fp32 operation.
-// The caller gives cos / sin of the yaw (tgt_standup_kernel: cosf / sinf; bev_detect.hpp: the fp64 functions rounded to fp32).
-__device__ __forceinline__ void box_footprint_corner(int k, float cx, float cy, float sx, float sy, float cs, float sn, float& X,
-                                                     float& Y) {
-#pragma clang fp contract(off)
-    const float x = k < 2 ? sx : -sx, y = (k == 1 || k == 2) ? sy : -sy;
-    X = (x * cs + y * -sn) + cx;
-    Y = (x * sn + y * cs) + cy;
-}
-
 __global__ __launch_bounds__(256) void tgt_standup_kernel(const float* __restrict__ boxes, float* __restrict__ out, long n) {
 #pragma clang fp contract(off)
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
@@ -275,3 +261,60 @@ __global__ __launch_bounds__(256) void ppl_finish_kernel(const double* __restric
 static long ppl_blocks(long B, long HW, long A) { return ((HW + 255) / 256) * A * B; }
 
 }  // namespace cobevt
+
+using namespace cobevt;
+
+extern "C" int cobevt_boxes_standup(const float* boxes, float* standup, long n, hipStream_t stream) {
+    if (n < 0 || n > 0x7fffffffL / 8) return COBEVT_ERR_SHAPE;
+    if (n == 0) return COBEVT_OK;
+    if (!boxes || !standup) return COBEVT_ERR_ARG;
+    if ((uintptr_t)standup & 15) return COBEVT_ERR_SHAPE;
+    hipLaunchKernelGGL(tgt_standup_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, boxes, standup, n);
+    return cobevt::launch_status();
+}
+
+extern "C" int cobevt_detect_targets(const float* anchors, const float* anchor_standup, const float* gt_boxes, const float* gt_standup,
+                                     const float* mask, float pos_threshold, float neg_threshold, float* pos_equal_one,
+                                     float* neg_equal_one, float* targets, int* num_pos, void* workspace, int B, int H, int W, int A,
+                                     int G, hipStream_t stream) {
+    if (!anchors || !anchor_standup || !pos_equal_one || !neg_equal_one || !targets || !num_pos || !workspace) return COBEVT_ERR_ARG;
+    if (G < 0 || G > kTgtMaxGt) return COBEVT_ERR_SHAPE;
+    if (G > 0 && (!gt_boxes || !gt_standup || !mask)) return COBEVT_ERR_ARG;
+    if (B < 1 || B > 65535 || H < 1 || W < 1 || A < 1 || (long)H > 0x7fffffffL / W || (long)H * W > (0x7fffffffL / 8) / A
+        || (long)H * W * A > (0x7fffffffL / 8) / B)
+        return COBEVT_ERR_SHAPE;
+    if (((uintptr_t)anchor_standup & 15) || ((uintptr_t)gt_standup & 15) || ((uintptr_t)workspace & 7)) return COBEVT_ERR_SHAPE;
+    const int M = H * W * A;
+    unsigned long long* best = (unsigned long long*)workspace;           // (B, max(G, 1)) keys
+    if (hipMemsetAsync(best, 0, 8 * (size_t)B * (G > 0 ? G : 1), stream) != hipSuccess) return COBEVT_ERR_LAUNCH;
+    if (hipMemsetAsync(num_pos, 0, 4 * (size_t)B, stream) != hipSuccess) return COBEVT_ERR_LAUNCH;
+    const dim3 grid((unsigned)((M + 255) / 256), (unsigned)B);
+    if (G > 0) hipLaunchKernelGGL(tgt_best_kernel, grid, dim3(256), 0, stream, anchor_standup, gt_standup, mask, best, M, G);
+    hipLaunchKernelGGL(tgt_label_kernel, grid, dim3(256), 0, stream, anchors, anchor_standup, gt_boxes, gt_standup, mask, best,
+                       pos_equal_one, neg_equal_one, targets, num_pos, M, G, pos_threshold, neg_threshold);
+    return cobevt::launch_status();
+}
+
+extern "C" int cobevt_pointpillar_loss(const float* psm, const float* rm, const float* pos_equal_one, const float* targets,
+                                       const int* num_pos, float* loss, float* dpsm, float* drm, void* workspace, int B, int H, int W,
+                                       int A, float cls_weight, float reg, hipStream_t stream) {
+    if (!psm || !rm || !pos_equal_one || !targets || !loss || !workspace || ((dpsm == nullptr) != (drm == nullptr))) return COBEVT_ERR_ARG;
+    if (B < 1 || B > 65535 || A < 1 || A > 65535 || H < 1 || W < 1 || (long)H > 0x7fffffffL / W || (long)H * W > (0x7fffffffL / 8) / A
+        || (long)H * W * A > (0x7fffffffL / 8) / B)
+        return COBEVT_ERR_SHAPE;
+    if ((uintptr_t)workspace & 7) return COBEVT_ERR_SHAPE;
+    const int HW = H * W, M = HW * A;
+    const long nblk = ppl_blocks(B, HW, A);
+    double* partial = (double*)workspace;                                // 2 nblk doubles, then B ints
+    int* counts = (int*)(partial + 2 * nblk);
+    if (!num_pos) {
+        if (hipMemsetAsync(counts, 0, 4 * (size_t)B, stream) != hipSuccess) return COBEVT_ERR_LAUNCH;
+        hipLaunchKernelGGL(ppl_count_kernel, dim3((unsigned)((M + 255) / 256), (unsigned)B), dim3(256), 0, stream, pos_equal_one, counts, M);
+        num_pos = counts;
+    }
+    hipLaunchKernelGGL(ppl_main_kernel, dim3((unsigned)((HW + 255) / 256), (unsigned)A, (unsigned)B), dim3(256), 0, stream, psm, rm,
+                       pos_equal_one, targets, num_pos, partial, dpsm, drm, HW, A, cls_weight / (float)B, reg / (float)B);
+    hipLaunchKernelGGL(ppl_finish_kernel, dim3(1), dim3(256), 0, stream, (const double*)partial, nblk, loss,
+                       (double)cls_weight / B, (double)reg / B);
+    return cobevt::launch_status();
+}

@@ -441,8 +441,6 @@ static int launch1d(K kern, long work_items, hipStream_t stream, Args... args) {
     return cobevt::launch_status();
 }
 
-static bool group_ok(int C) { const int G = C >> 3; return C % 8 == 0 && G >= 1 && G <= 64 && (G & (G - 1)) == 0; }
-
 }  // namespace cobevt
 
 using namespace cobevt;

@@ -286,8 +286,6 @@ static int launch_igemm(const IgemmParams& p, hipStream_t stream) {
 
 }  // namespace cobevt
 
-#include "deconv.hpp"       // cobevt_deconv_nhwc's kernel: the same K loop, tap-major columns, pixel-shuffled wide stores
-
 using namespace cobevt;
 
 // C-ABI entry point, see include/cobevt_hip.h
@@ -324,29 +322,4 @@ extern "C" int cobevt_conv2d_nhwc(const void* in, const void* wgt, const float* 
     if (p.Cin % ch != 0) return COBEVT_ERR_SHAPE;
     if (p.K != p.Kh * p.Kw * p.Cin) return COBEVT_ERR_SHAPE;
     return dtype == 0 ? launch_igemm<bf16_t, false>(p, stream) : launch_igemm<float, false>(p, stream);
-}
-
-// C-ABI entry point, see include/cobevt_hip.h
-extern "C" int cobevt_deconv_nhwc(const void* in, const void* wgt, const float* shift, void* out, const int* dims, hipStream_t stream) {
-    // dims: [dtype, N, H, W, Cin, Cout, Kpad, s, c_off, ldc, act]
-    if (!in || !wgt || !shift || !out || !dims) return COBEVT_ERR_ARG;
-    const int dtype = dims[0], N = dims[1];
-    if (dtype != 0 && dtype != 1) return COBEVT_ERR_ARG;
-    DeconvParams p;
-    p.in = in; p.wgt = wgt; p.shift = shift; p.out = out;
-    p.H = dims[2]; p.W = dims[3]; p.Cin = dims[4]; p.Cout = dims[5]; p.Kpad = dims[6];
-    p.s = dims[7]; p.c_off = dims[8]; p.ldc = dims[9]; p.act = dims[10];
-    if (p.act < 0 || p.act > 4) return COBEVT_ERR_ARG;
-    if (N <= 0 || p.H <= 0 || p.W <= 0 || p.Cin <= 0 || p.Cout <= 0) return COBEVT_ERR_SHAPE;
-    if (p.s < 1 || p.s > 8) return COBEVT_ERR_SHAPE;
-    const int bke = dtype == 0 ? 32 : 16, ch = dtype == 0 ? 8 : 4;
-    if (p.Cin % ch != 0 || p.Cout % 32 != 0) return COBEVT_ERR_SHAPE;
-    if (p.Kpad % bke != 0 || p.Kpad < p.Cin) return COBEVT_ERR_SHAPE;
-    // 16-byte stores: the slice starts on an 8-channel boundary of a row whose length is a multiple of 8 channels
-    if (p.c_off < 0 || p.c_off % 8 != 0 || p.ldc % 8 != 0 || (long long)p.c_off + p.Cout > p.ldc) return COBEVT_ERR_SHAPE;
-    const long long M = (long long)N * p.H * p.W;
-    if (M > 0x7fffffffLL - kDeconvBM || M * p.s * p.s > 0x7fffffffLL) return COBEVT_ERR_SHAPE;     // pixel indices are ints
-    p.M = (int)M;
-    p.NC = p.s * p.s * p.Cout;
-    return dtype == 0 ? launch_deconv<bf16_t>(p, stream) : launch_deconv<float>(p, stream);
 }

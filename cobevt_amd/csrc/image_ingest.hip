@@ -14,7 +14,6 @@
 //                       (a row at a time, so its taps are wave-uniform scalar loads), the table and the stores.  Rows the crop drops
 //                       are never computed.
 //   decode_bev_kernel : common.py:69-78 decode -> * 255 -> uint8 -> ToTensor of the bit-packed BEV label: (x >> c) & 1 as 0.0 / 1.0.
-#pragma once
 #include "common.hpp"
 
 namespace cobevt {
@@ -262,7 +261,7 @@ __global__ __launch_bounds__(256) void decode_bev_kernel(const int* __restrict__
 }
 
 // dims = [n, H, W, channels, h_resize, w_resize, top_crop, out is uint8]
-inline int launch_resize_pil(const unsigned char* src, void* out, const int* hb, const int* hc, const int* vb, const int* vc,
+static int launch_resize_pil(const unsigned char* src, void* out, const int* hb, const int* hc, const int* vb, const int* vc,
                              const float* lut, const int* dims, hipStream_t stream) {
     if (!src || !out || !dims) return COBEVT_ERR_ARG;
     const int n = dims[0], H = dims[1], W = dims[2], C = dims[3], hr = dims[4], wr = dims[5], top = dims[6], out_u8 = dims[7];
@@ -299,7 +298,7 @@ inline int launch_resize_pil(const unsigned char* src, void* out, const int* hb,
     return launch_status();
 }
 
-inline int launch_decode_bev(const int* labels, float* out, int n, int hw, int C, hipStream_t stream) {
+static int launch_decode_bev(const int* labels, float* out, int n, int hw, int C, hipStream_t stream) {
     if (!labels || !out) return COBEVT_ERR_ARG;
     if (n < 1 || n > 65535 || hw < 1 || C < 1 || C > kIngestMaxClasses) return COBEVT_ERR_SHAPE;
     hipLaunchKernelGGL(decode_bev_kernel, dim3((hw + 255) / 256, n), dim3(256), 0, stream, labels, out, hw, C);
@@ -307,3 +306,14 @@ inline int launch_decode_bev(const int* labels, float* out, int n, int hw, int C
 }
 
 }  // namespace cobevt
+
+using namespace cobevt;
+
+extern "C" int cobevt_resize_pil_u8(const unsigned char* src, void* out, const int* hbounds, const int* hcoeffs, const int* vbounds,
+                                    const int* vcoeffs, const float* lut, const int* dims, hipStream_t stream) {
+    return launch_resize_pil(src, out, hbounds, hcoeffs, vbounds, vcoeffs, lut, dims, stream);
+}
+
+extern "C" int cobevt_decode_bev(const int* labels, float* out, int N, int hw, int num_classes, hipStream_t stream) {
+    return launch_decode_bev(labels, out, N, hw, num_classes, stream);
+}

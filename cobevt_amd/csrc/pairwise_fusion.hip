@@ -12,21 +12,6 @@
 namespace cobevt {
 namespace {
 
-// first agent row of sample b and its agent count
-__device__ __forceinline__ void sample_rows(const int* record_len, int b, int& off, int& n) {
-    off = 0;
-    for (int bb = 0; bb < b; ++bb) off += record_len[bb];
-    n = record_len[b];
-}
-
-}  // namespace
-}  // namespace cobevt
-
-#include "att_fuse.hpp"     // att_fuse_kernel: AttFusion over the agents of a sample (uses sample_rows)
-
-namespace cobevt {
-namespace {
-
 // nb[b][i][j] = agent j's map warped into agent i's frame (j, i < record_len[b]; zeros otherwise);
 // roi[b][i][j][h][w] = the reference's mask value that multiplies out pixel (h, w)
 template <typename T>
@@ -232,8 +217,6 @@ int launch1d(K kern, long work_items, hipStream_t stream, Args... args) {
     return cobevt::launch_status();
 }
 
-bool group_ok(int C) { const int G = C >> 3; return C % 8 == 0 && G >= 1 && G <= 64 && (G & (G - 1)) == 0; }
-
 }  // namespace
 }  // namespace cobevt
 
@@ -292,17 +275,4 @@ extern "C" int cobevt_agent_softmax_sum(const void* score, int lds, const void* 
     if (dtype == 0) return launch1d(agent_softmax_sum_kernel<bf16_t>, items, stream, (const bf16_t*)score, lds, (const bf16_t*)nb, roi, record_len, (bf16_t*)out, B, L, HW, C, use_mask);
     if (dtype == 1) return launch1d(agent_softmax_sum_kernel<float>, items, stream, (const float*)score, lds, (const float*)nb, roi, record_len, (float*)out, B, L, HW, C, use_mask);
     return COBEVT_ERR_ARG;
-}
-
-extern "C" int cobevt_att_fuse_nhwc(const void* x, const int* record_len, void* out, int dtype, int B, int N, long HW, int C, float scale,
-                                    hipStream_t stream) {
-    if (!x || !record_len || !out) return COBEVT_ERR_ARG;
-    if (dtype != 0 && dtype != 1) return COBEVT_ERR_ARG;
-    if (!group_ok(C) || B < 1 || B > 65535 || N < 1 || HW < 1) return COBEVT_ERR_SHAPE;
-    const long blocks = (HW * (C >> 3) + 255) / 256;
-    if (blocks > 0x7fffffffL) return COBEVT_ERR_SHAPE;
-    const dim3 grid((unsigned)blocks, (unsigned)B);
-    if (dtype == 0) hipLaunchKernelGGL(att_fuse_kernel<bf16_t>, grid, dim3(256), 0, stream, (const bf16_t*)x, record_len, (bf16_t*)out, N, HW, C, scale);
-    else hipLaunchKernelGGL(att_fuse_kernel<float>, grid, dim3(256), 0, stream, (const float*)x, record_len, (float*)out, N, HW, C, scale);
-    return cobevt::launch_status();
 }

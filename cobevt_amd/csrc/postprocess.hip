@@ -6,7 +6,6 @@
 //   seg_counts_kernel     : the per-class pixel counts mean_IU / mean_precision reduce their masks to
 //                           (seg_utils.py:25-50: n_ii = |pred==c & gt==c|, t_i = |gt==c|, n_ij = |pred==c|) - integer exact.
 #include "common.hpp"
-#include "image_ingest.hpp"             // nuScenes camera ingest: Pillow-exact resize + crop + ToTensor, BEV label unpack (entry points at the end)
 
 namespace cobevt {
 
@@ -513,14 +512,4 @@ extern "C" int cobevt_conv3x3_head_nchw(const void* in, const float* wgt, const 
     if (dtype == 0) return launch_head<bf16_t>(in, wgt, bias, out, N, H, W, Cin, Cout, stream);
     if (dtype == 1) return launch_head<float>(in, wgt, bias, out, N, H, W, Cin, Cout, stream);
     return COBEVT_ERR_ARG;
-}
-
-// ---------------------------------------------------------------------------------------------- nuScenes camera ingest (image_ingest.hpp)
-extern "C" int cobevt_resize_pil_u8(const unsigned char* src, void* out, const int* hbounds, const int* hcoeffs, const int* vbounds,
-                                    const int* vcoeffs, const float* lut, const int* dims, hipStream_t stream) {
-    return launch_resize_pil(src, out, hbounds, hcoeffs, vbounds, vcoeffs, lut, dims, stream);
-}
-
-extern "C" int cobevt_decode_bev(const int* labels, float* out, int N, int hw, int num_classes, hipStream_t stream) {
-    return launch_decode_bev(labels, out, N, hw, num_classes, stream);
 }

@@ -1,7 +1,7 @@
-// Sparse 3-D convolutions over an active-voxel set (gfx950), included by voxelize.hip only: what OpenCOOD's SECOND-style encoder
+// Sparse 3-D convolutions over an active-voxel set (gfx950): what OpenCOOD's SECOND-style encoder
 // (mean_vfe.py, sparse_backbone_3d.py, height_compression.py) delegates to spconv - SubMConv3d, SparseConv3d, SparseConvTensor.dense -
 // and MeanVFE in front of them.  Library-independent: the fp32-storage kernel is the exact v_mfma_f32_32x32x2_f32 one in all three
-// libraries (this header does not reach the fp32 matrix-path header), bf16 storage runs v_mfma_f32_32x32x16_bf16 with fp32 accumulation.
+// libraries (this source does not reach the fp32 matrix-path header), bf16 storage runs v_mfma_f32_32x32x16_bf16 with fp32 accumulation.
 //
 // A LEVEL is a sparse shape (N, D, H, W) with an active set.  Its index, in one int32 workspace of cobevt_sparse_scratch(dims) ints:
 //   bits    one bit per cell, cell = ((b D + z) H + y) W + x, 32 cells per word (padded to whole 1024-word blocks)
@@ -34,7 +34,6 @@
 // applies ReLU and stores 8 / 16 bytes per quad in the storage dtype.  Feature rows at or past the live count are NOT written.
 // Channels: input rows are kgroups x 32 bytes (Cin <= 8 is padded to one k-group with zero weights behind it), Cout is padded to a
 // multiple of 32 in the weight table only.
-#pragma once
 #include "common.hpp"
 
 namespace cobevt {
@@ -420,3 +419,130 @@ __global__ __launch_bounds__(256) void sparse_dense_kernel(const T* __restrict__
 }
 
 }  // namespace cobevt
+
+using namespace cobevt;
+
+// dims: [dtype, P, T, C, Cpad]
+extern "C" int cobevt_mean_vfe(const float* voxel_features, const int* voxel_num_points, const int* voxel_coords, void* out, const long* dims,
+                               hipStream_t stream) {
+    if (!dims) return COBEVT_ERR_ARG;
+    const long dt = dims[0], P = dims[1], T = dims[2], C = dims[3], Cpad = dims[4];
+    if ((dt != 0 && dt != 1) || P < 0 || T < 1 || T > 0x7fffffffL || C < 1 || Cpad < C || Cpad > 64) return COBEVT_ERR_SHAPE;
+    if (P > (0x7fffffffL - 256) / Cpad * 256 || P > 0x7fffffffffffL / (T * C)) return COBEVT_ERR_SHAPE;
+    if (P == 0) return COBEVT_OK;
+    if (!voxel_features || !voxel_num_points || !out) return COBEVT_ERR_ARG;
+    if (((uintptr_t)voxel_features | (uintptr_t)voxel_num_points | (uintptr_t)out) & 3 || ((uintptr_t)voxel_coords & 15)) return COBEVT_ERR_SHAPE;
+    const unsigned blocks = (unsigned)((P * Cpad + 255) / 256);
+    if (dt == 0)
+        hipLaunchKernelGGL(mean_vfe_kernel<bf16_t>, dim3(blocks), dim3(256), 0, stream, voxel_features, voxel_num_points, (const int4*)voxel_coords,
+                           (bf16_t*)out, P, (int)T, (int)C, (int)Cpad);
+    else
+        hipLaunchKernelGGL(mean_vfe_kernel<float>, dim3(blocks), dim3(256), 0, stream, voxel_features, voxel_num_points, (const int4*)voxel_coords,
+                           (float*)out, P, (int)T, (int)C, (int)Cpad);
+    return cobevt::launch_status();
+}
+
+// dims: [N, D, H, W]
+extern "C" int cobevt_sparse_scratch(const long* dims, long* workspace_ints) {
+    if (!dims || !workspace_ints) return COBEVT_ERR_ARG;
+    SpShape s;
+    const int rc = sp_shape_args(dims, s);
+    if (rc != COBEVT_OK) return rc;
+    *workspace_ints = sp_index_ints(s);
+    return COBEVT_OK;
+}
+
+static bool sp_rows_ok(long n, long lo) { return n >= lo && n <= 0x7fffffffL - 256; }
+
+// dims: [N, D, H, W, P, capacity]
+extern "C" int cobevt_sparse_index(const int* voxel_coords, int* workspace, int* indices, int* num, int* source, const long* dims,
+                                   hipStream_t stream) {
+    if (!dims || !workspace || !indices || !num || !source) return COBEVT_ERR_ARG;
+    SpShape s;
+    const int rc = sp_shape_args(dims, s);
+    if (rc != COBEVT_OK) return rc;
+    const long P = dims[4], cap = dims[5];
+    if (!sp_rows_ok(P, 0) || !sp_rows_ok(cap, 1)) return COBEVT_ERR_SHAPE;
+    if (P > 0 && !voxel_coords) return COBEVT_ERR_ARG;
+    if (((uintptr_t)voxel_coords | (uintptr_t)workspace | (uintptr_t)indices) & 15) return COBEVT_ERR_SHAPE;
+    if (((uintptr_t)num | (uintptr_t)source) & 3) return COBEVT_ERR_SHAPE;
+    const SpIndex ix = sp_index(workspace, s);
+    sp_clear(ix.bits, 4 * (size_t)sp_words(s), stream);
+    const unsigned pb = (unsigned)((P + 255) / 256);
+    if (pb) hipLaunchKernelGGL(sp_mark_rows_kernel, dim3(pb), dim3(256), 0, stream, (const int4*)voxel_coords, P, s, ix.bits);
+    sp_rank(ix, s, (int4*)indices, num, source, cap, stream);
+    if (pb)
+        hipLaunchKernelGGL(sp_source_kernel, dim3(pb), dim3(256), 0, stream, (const int4*)voxel_coords, P, s, (const unsigned*)ix.bits,
+                           (const int*)ix.prefix, (const int*)num, source);
+    return cobevt::launch_status();
+}
+
+// dims: [N, D, H, W (the INPUT level), input capacity, output capacity, kernel z y x, stride z y x, pad z y x]
+extern "C" int cobevt_sparse_downsample(const int* in_indices, const int* in_num, int* workspace, int* indices, int* num, const long* dims,
+                                        hipStream_t stream) {
+    if (!dims || !in_indices || !in_num || !workspace || !indices || !num) return COBEVT_ERR_ARG;
+    SpShape si, so;
+    SpGeom g;
+    int rc = sp_shape_args(dims, si);
+    if (rc == COBEVT_OK) rc = sp_geom_args(dims + 6, g);
+    if (rc == COBEVT_OK) rc = sp_out_shape(si, g, so);
+    if (rc != COBEVT_OK) return rc;
+    const long in_cap = dims[4], cap = dims[5];
+    if (!sp_rows_ok(in_cap, 1) || !sp_rows_ok(cap, 1)) return COBEVT_ERR_SHAPE;
+    if (((uintptr_t)in_indices | (uintptr_t)workspace | (uintptr_t)indices) & 15) return COBEVT_ERR_SHAPE;
+    if (((uintptr_t)num | (uintptr_t)in_num) & 3) return COBEVT_ERR_SHAPE;
+    const SpIndex ix = sp_index(workspace, so);
+    sp_clear(ix.bits, 4 * (size_t)sp_words(so), stream);
+    hipLaunchKernelGGL(sp_mark_down_kernel, dim3((unsigned)((in_cap + 255) / 256)), dim3(256), 0, stream, (const int4*)in_indices, in_num, in_cap,
+                       si, g, so, ix.bits);
+    sp_rank(ix, so, (int4*)indices, num, nullptr, cap, stream);
+    return cobevt::launch_status();
+}
+
+// dims: [dtype, N, D, H, W (the INPUT level), input feature rows, output capacity, input row in channels, Cout, kernel z y x, stride z y x,
+// pad z y x]
+extern "C" int cobevt_sparse_conv(const void* in, const int* in_workspace, const int* in_num, const int* row_map, const int* out_indices,
+                                  const int* out_num, const void* weight, const float* bias, void* out, const long* dims, hipStream_t stream) {
+    if (!dims || !in || !in_workspace || !in_num || !out_indices || !out_num || !weight || !bias || !out) return COBEVT_ERR_ARG;
+    SpConvArgs a;
+    int rc = sp_shape_args(dims + 1, a.si);
+    if (rc == COBEVT_OK) rc = sp_geom_args(dims + 9, a.g);
+    if (rc != COBEVT_OK) return rc;
+    const long dt = dims[0], in_rows = dims[5], out_cap = dims[6], cin_pad = dims[7], cout = dims[8];
+    if ((dt != 0 && dt != 1) || !sp_rows_ok(in_rows, 1) || !sp_rows_ok(out_cap, 1) || cin_pad < 1 || cin_pad > 64 || cout < 16 || cout > 128)
+        return COBEVT_ERR_SHAPE;
+    if (((uintptr_t)in | (uintptr_t)in_workspace | (uintptr_t)out_indices | (uintptr_t)weight | (uintptr_t)bias | (uintptr_t)out) & 15)
+        return COBEVT_ERR_SHAPE;
+    if (((uintptr_t)in_num | (uintptr_t)out_num | (uintptr_t)row_map) & 3) return COBEVT_ERR_SHAPE;
+    const SpIndex ix = sp_index((int*)in_workspace, a.si);
+    a.in = in; a.in_bits = ix.bits; a.in_prefix = ix.prefix; a.in_num = in_num; a.row_map = row_map;
+    a.out_idx = (const int4*)out_indices; a.out_num = out_num; a.wgt = weight; a.bias = bias; a.out = out;
+    a.in_rows = in_rows; a.out_cap = out_cap; a.taps = a.g.k[0] * a.g.k[1] * a.g.k[2]; a.cout = (int)cout;
+    if (!(dt == 0 ? sp_conv_dispatch<bf16_t>((int)cin_pad, a, out_cap, stream, false) : sp_conv_dispatch<float>((int)cin_pad, a, out_cap, stream, false)))
+        return COBEVT_ERR_SHAPE;
+    if (dt == 0) sp_conv_dispatch<bf16_t>((int)cin_pad, a, out_cap, stream, true);
+    else sp_conv_dispatch<float>((int)cin_pad, a, out_cap, stream, true);
+    return cobevt::launch_status();
+}
+
+// dims: [dtype, N, D, H, W, capacity, C]
+extern "C" int cobevt_sparse_dense(const void* features, const int* indices, const int* num, void* out, const long* dims, hipStream_t stream) {
+    if (!dims || !features || !indices || !num || !out) return COBEVT_ERR_ARG;
+    SpShape s;
+    const int rc = sp_shape_args(dims + 1, s);
+    if (rc != COBEVT_OK) return rc;
+    const long dt = dims[0], cap = dims[5], C = dims[6];
+    if ((dt != 0 && dt != 1) || !sp_rows_ok(cap, 1) || C < 1 || C > 4096 || cap > (0x7fffffffL - 256) / C * 256) return COBEVT_ERR_SHAPE;
+    if ((((uintptr_t)features | (uintptr_t)num) & 3) || (((uintptr_t)indices | (uintptr_t)out) & 15)) return COBEVT_ERR_SHAPE;
+    const size_t es = dt == 0 ? 2 : 4;
+    sp_clear(out, (size_t)sp_cells(s) * (size_t)C * es, stream);
+    const long total = cap * C;
+    const unsigned blocks = (unsigned)((total + 255) / 256);
+    if (dt == 0)
+        hipLaunchKernelGGL(sparse_dense_kernel<bf16_t>, dim3(blocks), dim3(256), 0, stream, (const bf16_t*)features, (const int4*)indices, num,
+                           (bf16_t*)out, s, (int)C, total);
+    else
+        hipLaunchKernelGGL(sparse_dense_kernel<float>, dim3(blocks), dim3(256), 0, stream, (const float*)features, (const int4*)indices, num,
+                           (float*)out, s, (int)C, total);
+    return cobevt::launch_status();
+}

@@ -1,5 +1,5 @@
-// Shared device helpers of the channels-last glue kernels: 8-channel row pieces as fp32, and the affine-warp arithmetic of the
-// reference's STTF / ROI masks (torch_transformation_utils.py:108-134,160-191,254-355).
+// Shared helpers of the channels-last glue kernels: 8-channel row pieces as fp32 and the lane groups that own them, the agent rows
+// of a sample, and the affine-warp arithmetic of the reference's STTF / ROI masks (torch_transformation_utils.py:108-134,160-191,254-355).
 #pragma once
 #include "common.hpp"
 
@@ -21,6 +21,16 @@ template <typename T> __device__ __forceinline__ void store8(T* p, const float* 
         *(uint4*)p = f32_to_chunk<T>(v);
         *(uint4*)(p + 4) = f32_to_chunk<T>(v + 4);
     }
+}
+
+// a row of C channels splits into G = C / 8 such pieces, one per lane of a group that stays inside a wave: G a power of two <= 64
+inline bool group_ok(int C) { const int G = C >> 3; return C % 8 == 0 && G >= 1 && G <= 64 && (G & (G - 1)) == 0; }
+
+// first agent row of sample b and its agent count
+__device__ __forceinline__ void sample_rows(const int* record_len, int b, int& off, int& n) {
+    off = 0;
+    for (int bb = 0; bb < b; ++bb) off += record_len[bb];
+    n = record_len[b];
 }
 
 struct Affine { float t[6]; };

@@ -1,6 +1,6 @@
 """BevPreprocessor — OpenCOOD's data_utils/pre_processor/bev_preprocessor.py on the device: raw points -> PIXOR's `bev_input`, a
 binary height-slice occupancy volume plus one mean-intensity channel, for every agent in one operator call (ops.bev_points,
-csrc/bev_points.hpp) without a host synchronisation.  The reference is a Python loop over the points of one cloud.
+csrc/bev_points.hip) without a host synchronisation.  The reference is a Python loop over the points of one cloud.
 
 preprocess_params: {'cav_lidar_range': [x0, y0, z0, x1, y1, z1], 'geometry_param': {L1, L2, W1, W2, H1, H2, res, input_shape
 (nx, ny, C), label_shape, downsample_rate}}, optionally 'range_mask' / 'ego_mask' as on SpVoxelPreprocessor

@@ -1,6 +1,6 @@
 """DataAugmentor — OpenCOOD's data_utils/augmentor/data_augmentor.py (random world flip / rotation / scaling of a LiDAR cloud and its
 ground-truth boxes) on the device: the random parameters are drawn on the host with the reference's own NumPy calls, the arithmetic is
-stage 3 of ops.prepare_points (csrc/cloud_prep.hpp).
+stage 3 of ops.prepare_points (csrc/cloud_prep.hip).
 
 augment_config: the reference's list, e.g. [{'NAME': 'random_world_flip', 'ALONG_AXIS_LIST': ['x']}, {'NAME': 'random_world_rotation',
 'WORLD_ROT_ANGLE': [-0.785, 0.785]}, {'NAME': 'random_world_scaling', 'WORLD_SCALE_RANGE': [0.95, 1.05]}].  forward(data_dict) reads

@@ -2,7 +2,7 @@
 per-pixel formulation: `generate_label` rasterises rotated ground-truth boxes into a 7-channel label map, `post_process` decodes a
 per-pixel cls / reg output into rotated 2-D boxes in the ego frame, runs the rotated NMS and the range mask.
 
-Both run on the device.  Labels: ONE launch for a whole batch (ops.bev_labels, csrc/bev_detect.hpp) where the reference loops over
+Both run on the device.  Labels: ONE launch for a whole batch (ops.bev_labels, csrc/bev_labels.hip) where the reference loops over
 the boxes and tests every pixel on the host.  Output: ONE operator call (ops.bev_post_process) - a decode launch in front of the
 select / mask / greedy launches VoxelPostprocessor uses (csrc/detect_post.hip); the host reads the count once.
 `post_process_device` is the same call without that read (fixed-capacity tensors plus a count: graph-capturable).

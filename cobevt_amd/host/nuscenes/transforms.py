@@ -2,7 +2,7 @@
 
 The reference opens a JPEG per camera, resizes it with Pillow's antialiased BILINEAR on one host core, cuts the top rows and calls
 ToTensor; here the six decoded frames go to the device as uint8 and ops.resize_pil_bilinear does all of that in one launch, bit for
-bit (csrc/image_ingest.hpp); the bit-packed BEV label is unpacked by ops.decode_bev.  Disk formats and JPEG decoding stay with the
+bit (csrc/image_ingest.hip); the bit-packed BEV label is unpacked by ops.decode_bev.  Disk formats and JPEG decoding stay with the
 caller: where the reference's Sample holds paths, this one holds arrays.
 
 Placement: `image`, `bev` (and `center`, `visibility` when they arrive as device tensors) are on the device; `cam_idx`, `intrinsics`,

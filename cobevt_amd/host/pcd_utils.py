@@ -1,5 +1,5 @@
 """pcd_utils — the part of OpenCOOD's utils/pcd_utils.py that has a device form.  mask_ego_points, lidar_project, mask_points_by_range
-and projected_lidar_stack are stages of ops.prepare_points (csrc/cloud_prep.hpp); shuffle_points becomes a permutation made on the
+and projected_lidar_stack are stages of ops.prepare_points (csrc/cloud_prep.hip); shuffle_points becomes a permutation made on the
 device and handed to it as `order=`."""
 import torch
 

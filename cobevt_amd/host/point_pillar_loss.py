@@ -8,7 +8,7 @@ reference tree of this package ships no detection loss, so the contract is writt
     total_loss = conf_loss + reg_loss
 
 Same constructor argument (`args` with `cls_weight` and `reg`), same `forward(output_dict, target_dict)` -> total loss and
-`loss_dict` entries.  One operator call (ops.pointpillar_loss, csrc/detect_targets.hpp) computes the three scalars and, when psm or
+`loss_dict` entries.  One operator call (ops.pointpillar_loss, csrc/detect_targets.hip) computes the three scalars and, when psm or
 rm requires grad, both gradients in the same launch; it sits behind a torch.autograd.Function, so `.backward()` hands the kernel's
 gradients to the head maps.  `target_dict` is what VoxelPostprocessor.generate_label_batch returns (its `num_pos` saves the count
 launch) or the reference's collate_batch dict (float64 labels are converted).  There is no CPU fallback."""

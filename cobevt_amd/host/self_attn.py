@@ -1,7 +1,7 @@
 """AttFusion — OpenCOOD's attentive fusion (opencood/models/fusion_modules/self_attn.py): per pixel, scaled-dot-product attention
 over the agents of a sample with the agents' feature vectors as queries, keys and values, of which the ego's row is kept.  The
 reference splits the batch by record_len on the host, permutes every sample to (HW, n, C), runs two bmm's and a softmax and permutes
-back; here it is ONE launch over all samples on the channels-last maps (ops.att_fuse, csrc/att_fuse.hpp) that reads record_len on
+back; here it is ONE launch over all samples on the channels-last maps (ops.att_fuse, csrc/att_fuse.hip) that reads record_len on
 the device.  No parameters."""
 import torch
 

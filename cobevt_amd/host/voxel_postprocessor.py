@@ -7,7 +7,7 @@ ONE operator call (ops.detect_post_process, csrc/detect_post.hip) decodes every 
 same call without that read (fixed-capacity tensors plus a count: graph-capturable).
 
 `generate_label` / `generate_label_batch` build the training targets on the device (ops.boxes_standup + ops.detect_targets,
-csrc/detect_targets.hpp): the reference's anchor-to-ground-truth assignment with the `bbox_overlaps` of its Cython extension restated
+csrc/detect_targets.hip): the reference's anchor-to-ground-truth assignment with the `bbox_overlaps` of its Cython extension restated
 as a kernel, bit-identical to that compiled C given the same standup boxes.  `generate_label` keeps the reference's
 signature and types (numpy in, numpy float64 out, one host read); `generate_label_batch` takes the collated batch and returns device
 tensors without a synchronisation, `num_pos` included for PointPillarLoss.  `collate_batch` is a plain mirror.

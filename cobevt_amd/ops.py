@@ -1352,7 +1352,7 @@ def rotation_cos_sin(angle):
 
 def prepare_points(points, point_offsets, transforms=None, *, order=None, ego_mask=False, lidar_range=None, world=None, boxes=None,
                    box_mask=None, out=None, workspace=None):
-    """Per-agent sensor-frame clouds -> one compact ego-frame cloud (csrc/cloud_prep.hpp), without a host synchronisation: what the
+    """Per-agent sensor-frame clouds -> one compact ego-frame cloud (csrc/cloud_prep.hip), without a host synchronisation: what the
     reference's datasets do in NumPy in front of the pre-processors.
     points (M, 4) contiguous fp32 [x, y, z, intensity] and point_offsets (N + 1,) int32 / int64 on the device, as voxelize_points
     takes them (rows at or past offsets[N] are ignored).  Per agent, in input order - with order (M,) int32 / int64 on the device in
@@ -1452,7 +1452,7 @@ def prepare_points(points, point_offsets, transforms=None, *, order=None, ego_ma
 
 
 # ----------------------------------------------------------------------------------------------
-# the sparse 3-D voxel backbone (csrc/sparse_conv.hpp): MeanVFE, active-set indices, SubMConv3d / SparseConv3d, dense()
+# the sparse 3-D voxel backbone (csrc/sparse_conv.hip): MeanVFE, active-set indices, SubMConv3d / SparseConv3d, dense()
 # ----------------------------------------------------------------------------------------------
 SPARSE_TILE_ROWS = 32      # output rows of one MFMA tile of cobevt_sparse_conv: the unit that skips absent taps
 SPARSE_BLOCK_ROWS = 128    # ... and of one workgroup (four tiles)
@@ -1466,7 +1466,7 @@ def sparse_row_channels(channels, dtype):
 
 
 def mean_vfe(voxel_features, voxel_num_points, voxel_coords=None, dtype=torch.float32, channels=None, out=None):
-    """MeanVFE (csrc/sparse_conv.hpp) in one launch: voxel_features (P, T, C) contiguous fp32, voxel_num_points (P,) int32 / int64 ->
+    """MeanVFE (csrc/sparse_conv.hip) in one launch: voxel_features (P, T, C) contiguous fp32, voxel_num_points (P,) int32 / int64 ->
     (P, channels) in `dtype`: per voxel the sum of its first voxel_num_points point slots, in slot order, divided by
     max(voxel_num_points, 1) - the reference's sum over all T slots whenever the unused ones are zero, which spconv guarantees.
     channels (default C, at most 64) >= C pads every row with zeros: sparse_row_channels(C, dtype) is the row cobevt_sparse_conv reads.
@@ -1789,7 +1789,7 @@ def _pil_lut(device, what):
 
 def resize_pil_bilinear(images_u8, size, top_crop=0, *, dtype=torch.float32, out=None):
     """Image.resize(size, resample=Image.BILINEAR) of Pillow's 8-bit path, the crop of the top rows and ToTensor, for a stack of
-    decoded frames in one launch (csrc/image_ingest.hpp): the camera side of the nuScenes LoadDataTransform.
+    decoded frames in one launch (csrc/image_ingest.hip): the camera side of the nuScenes LoadDataTransform.
     images_u8 (n, H, W, 3) contiguous uint8 on the device (any storage offset); size = (w_resize, h_resize), Pillow's order;
     top_crop rows of the RESIZED image are cut (and never computed).  With h = h_resize - top_crop, w = w_resize:
       dtype=torch.float32 -> (n, 3, h, w) fp32, each byte through the table arange(256) / 255: ToTensor's result, bit for bit;
@@ -1836,7 +1836,7 @@ def resize_pil_bilinear(images_u8, size, top_crop=0, *, dtype=torch.float32, out
 def decode_bev(labels_i32, num_classes, out=None):
     """The bit-packed nuScenes BEV label -> class planes: labels_i32 (n, h, w) contiguous int32 on the device ->
     (n, num_classes <= 16, h, w) fp32 of (x >> c) & 1 - the reference's decode -> * 255 -> uint8 -> ToTensor, exactly 0.0 or 1.0
-    (csrc/image_ingest.hpp).  One streaming launch, no host synchronisation."""
+    (csrc/image_ingest.hip).  One streaming launch, no host synchronisation."""
     what = "decode_bev"
     _need_cuda(labels_i32, out)
     if labels_i32.dtype != torch.int32 or labels_i32.dim() != 3 or not labels_i32.is_contiguous():
@@ -2016,7 +2016,7 @@ def detect_post_process(cavs, score_threshold, nms_thresh, order, out=None, work
 DETECT_MAX_GT = 128        # ground-truth slots per sample cobevt_detect_targets takes (the reference's max_num is 100)
 
 # ----------------------------------------------------------------------------------------------
-# LiDAR BEV maps, the PIXOR formulation (csrc/bev_points.hpp, csrc/bev_detect.hpp)
+# LiDAR BEV maps, the PIXOR formulation (csrc/bev_points.hip, csrc/bev_labels.hip, the bev mode of csrc/detect_post.hip)
 # ----------------------------------------------------------------------------------------------
 BEV_TARGET_MEAN = (0.008, 0.001, 0.202, 0.2, 0.43, 1.368)          # lidar_bev_postprocessor.py :24-25
 BEV_TARGET_STD_DEV = (0.866, 0.5, 0.954, 0.668, 0.09, 0.111)
@@ -2051,7 +2051,7 @@ def bev_points_workspace_ints(num_points, num_agents, input_shape):
 
 def bev_points(points, point_offsets, lidar_range, origin, res, input_shape, range_mask=False, ego_mask=False, channels_last=False,
                out=None, workspace=None):
-    """BevPreprocessor.preprocess for N agents, on the device and without a host synchronisation (csrc/bev_points.hpp).
+    """BevPreprocessor.preprocess for N agents, on the device and without a host synchronisation (csrc/bev_points.hip).
     points (M, 4) contiguous fp32 [x, y, z, intensity] and point_offsets (N + 1,) int32 / int64 on the device, as voxelize_points
     takes them; lidar_range = cav_lidar_range (used by range_mask only), origin = (L1, W1, H1), res the cell size, input_shape =
     (nx, ny, C).  -> bev_input (N, C, nx, ny) fp32, or (N, nx, ny, C) with channels_last: channels 0 .. C - 2 the binary occupancy of
@@ -2095,7 +2095,7 @@ def bev_points(points, point_offsets, lidar_range, origin, res, input_shape, ran
 
 def bev_labels(gt_box_center, mask, origin_xy, res, downsample_rate, label_shape, target_mean=BEV_TARGET_MEAN,
                target_std_dev=BEV_TARGET_STD_DEV, out=None):
-    """LidarBevPostprocessor.generate_label for a batch, on the device and without a synchronisation (csrc/bev_detect.hpp).
+    """LidarBevPostprocessor.generate_label for a batch, on the device and without a synchronisation (csrc/bev_labels.hip).
     gt_box_center (B, max_num, 7) in 'lwh' order and mask (B, max_num), contiguous fp32 on the device, max_num <= 128; origin_xy =
     (L1, W1); label_shape = (lx, ly, 7).  -> label_map (B, 7, lx, ly) fp32, bev_corners (B, max_num, 4, 2) fp32 (valid boxes compacted
     to the front in order, zero rows behind them) and num_valid (B,) int32.  Where boxes overlap the last valid one wins; channels
@@ -2138,7 +2138,7 @@ def _bev_post_out(out, dev):
 
 def bev_post_process(cavs, origin_xy, res, downsample_rate, score_threshold, nms_thresh, target_mean=BEV_TARGET_MEAN,
                      target_std_dev=BEV_TARGET_STD_DEV, out=None, workspace=None):
-    """LidarBevPostprocessor.post_process on the device, without a synchronisation (csrc/bev_detect.hpp + csrc/detect_post.hip).
+    """LidarBevPostprocessor.post_process on the device, without a synchronisation (the bev mode of csrc/detect_post.hip).
     cavs: a sequence of 1 .. 16 (cls, reg, transformation_matrix): cls (1, 1, lx, ly) and reg (1, 6, lx, ly) contiguous fp32 on the
     device, the 4 x 4 matrix a tensor or array (converted to fp32 on the device; give device tensors to capture the call in a graph).
     -> boxes (1000, 4, 2) fp32, scores (1000) fp32, index (1000) int32 (global pixel index: cav 0's pixels in (i, j) order, then cav
@@ -2198,7 +2198,7 @@ def _dev_f32(t, what, shape=None, dims=None):
 def boxes_standup(boxes):
     """boxes (n, 7) contiguous fp32 on the device, 'hwl' order -> (n, 4) fp32 [x1, y1, x2, y2]: the axis-aligned hull of the four
     rotated footprint corners, box_utils.boxes_to_corners_3d + corner2d_to_standup_box (length = column 5, width = column 4), every
-    product and sum a separately rounded fp32 operation (csrc/detect_targets.hpp)."""
+    product and sum a separately rounded fp32 operation (csrc/detect_targets.hip)."""
     if boxes.dim() != 2 or boxes.shape[1] != 7:
         raise CobevtHipError("boxes_standup: boxes must be (n, 7), got %s" % (tuple(boxes.shape),))
     _dev_f32(boxes, "boxes_standup: boxes")
@@ -2208,7 +2208,7 @@ def boxes_standup(boxes):
 
 
 def detect_targets(anchors, anchor_standup, gt_boxes, gt_standup, mask, pos_threshold, neg_threshold):
-    """VoxelPostprocessor.generate_label for a batch, on the device and without a synchronisation (csrc/detect_targets.hpp).
+    """VoxelPostprocessor.generate_label for a batch, on the device and without a synchronisation (csrc/detect_targets.hip).
     anchors (H, W, A, 7) and anchor_standup (H W A, 4); gt_boxes (B, G, 7), gt_standup (B, G, 4), mask (B, G), G <= 128: all
     contiguous fp32 on the device.  A slot is valid when its mask is 1; IoU column k is the k-th valid box and targets come from
     that same box.  -> pos_equal_one (B, H, W, A), neg_equal_one (B, H, W, A), targets (B, H, W, 7A) fp32 and num_pos (B,) int32.
@@ -2245,7 +2245,7 @@ def detect_targets(anchors, anchor_standup, gt_boxes, gt_standup, mask, pos_thre
 
 def pointpillar_loss(psm, rm, pos_equal_one, targets, cls_weight, reg, num_pos=None, want_grad=False):
     """The PointPillar detection loss (upstream OpenCOOD's PointPillarLoss) and, with want_grad, its gradient, in one operator call
-    (csrc/detect_targets.hpp).  psm (B, A, H, W), rm (B, 7A, H, W) NCHW, pos_equal_one (B, H, W, A), targets (B, H, W, 7A): contiguous
+    (csrc/detect_targets.hip).  psm (B, A, H, W), rm (B, 7A, H, W) NCHW, pos_equal_one (B, H, W, A), targets (B, H, W, 7A): contiguous
     fp32 on the device; num_pos (B,) int32 from detect_targets, or None to have the positives counted.
     -> (loss (3,) fp32 = [total, conf_loss, reg_loss], d total / d psm or None, d total / d rm or None).  fp32 per element, fp64 sums
     in a fixed order: bitwise reproducible, and the same bits with num_pos given or counted."""
@@ -2346,7 +2346,7 @@ def agent_softmax_sum(score, nb, roi, record_len, n_agents, use_mask=True):
 
 
 def att_fuse_group_ok(c):
-    """csrc/pairwise_fusion.hip's group_ok: 8 channels per lane, a power-of-two group of at most 64 lanes per pixel"""
+    """csrc/warp_common.hpp's group_ok: 8 channels per lane, a power-of-two group of at most 64 lanes per pixel"""
     g = c >> 3
     return c % 8 == 0 and 1 <= g <= 64 and (g & (g - 1)) == 0
 

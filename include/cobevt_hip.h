@@ -515,7 +515,7 @@ int cobevt_iou_counts(const float* pred, const float* label, const unsigned char
                       int min_visibility, hipStream_t stream);
 
 /*
- * cobevt_resize_pil_u8 (csrc/image_ingest.hpp, compiled into postprocess; identical in every library): the camera side of the
+ * cobevt_resize_pil_u8 (csrc/image_ingest.hip; identical in every library): the camera side of the
  *   nuScenes LoadDataTransform (nuscenes/cross_view_transformer/data/transforms.py:118-149) on decoded frames in device memory -
  *   Image.resize((w_resize, h_resize), resample=BILINEAR) of Pillow's 8-bit path, the crop of the top `top_crop` rows, ToTensor.
  *   src (n, H, W, 3) uint8 contiguous, any alignment.  dims = [n, H, W, channels, h_resize, w_resize, top_crop, out is uint8] (host).
@@ -927,7 +927,7 @@ int cobevt_delta_to_boxes3d(const float* rm, const float* anchors, float* boxes3
 int cobevt_rotated_iou(const float* a, const float* b, double* iou, long N, long M, hipStream_t stream);
 
 /*
- * LiDAR detection targets and loss (csrc/detect_targets.hpp, compiled into detect_post): OpenCOOD's
+ * LiDAR detection targets and loss (csrc/detect_targets.hip): OpenCOOD's
  * VoxelPostprocessor.generate_label with the box_overlaps.bbox_overlaps it needs, and the PointPillar detection loss with its
  * gradient.  fp32 / int32 data, fp64 only in the loss sums; identical in every library.
  *
@@ -971,8 +971,8 @@ int cobevt_pointpillar_loss(const float* psm, const float* rm, const float* pos_
                             float reg, hipStream_t stream);
 
 /*
- * LiDAR BEV maps, the PIXOR formulation: OpenCOOD's BevPreprocessor (csrc/bev_points.hpp, compiled into voxelize) and
- * LidarBevPostprocessor (csrc/bev_detect.hpp, compiled into detect_post).  Identical in every library.  No timing of these entry
+ * LiDAR BEV maps, the PIXOR formulation: OpenCOOD's BevPreprocessor (csrc/bev_points.hip) and
+ * LidarBevPostprocessor (labels: csrc/bev_labels.hip; post_process: the bev mode of csrc/detect_post.hip).  Identical in every library.  No timing of these entry
  * points has been measured yet.
  *
  * cobevt_bev_points: points (M, 4) fp32 [x, y, z, intensity] of N agents and point_offsets (N + 1) int32 ON THE DEVICE, with the
@@ -1016,7 +1016,7 @@ int cobevt_pointpillar_loss(const float* psm, const float* rm, const float* pos_
  *   bitwise reproducible.  workspace: cobevt_detect_scratch(total pixels) BYTES, 8-byte aligned.  Skip rules: none.
  */
 /*
- * cobevt_prepare_points (csrc/cloud_prep.hpp, compiled into voxelize; identical in every library): per-agent SENSOR-frame clouds and
+ * cobevt_prepare_points (csrc/cloud_prep.hip; identical in every library): per-agent SENSOR-frame clouds and
  *   their matrices -> one compact ego-frame cloud, the input of cobevt_voxelize_points / cobevt_bev_points.  What the reference's
  *   datasets do in NumPy: pcd_utils.mask_ego_points, lidar_project, DataAugmentor (world flip / rotation / scaling),
  *   mask_points_by_range and the vstack.
@@ -1061,7 +1061,7 @@ int cobevt_bev_post(const float* const* cls, const float* const* reg, const floa
                     void* workspace, hipStream_t stream);
 
 /*
- * The sparse 3-D voxel backbone (csrc/sparse_conv.hpp, compiled into voxelize; identical in every library): OpenCOOD's MeanVFE,
+ * The sparse 3-D voxel backbone (csrc/sparse_conv.hip; identical in every library): OpenCOOD's MeanVFE,
  * VoxelBackBone8x (spconv's SubMConv3d / SparseConv3d + BatchNorm1d + ReLU) and HeightCompression (SparseConvTensor.dense).
  * dtype: 0 = bf16 storage (bf16 MFMA, fp32 accumulation), 1 = fp32 storage (the exact fp32 MFMA, in all three libraries).  Every
  * `dims` is a host array of longs.  All of them: no host read, no allocation, no floating-point atomics, bitwise reproducible; scalar

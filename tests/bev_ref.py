@@ -14,7 +14,7 @@ F32 = np.float32
 
 # ---------------------------------------------------------------------------------------------- preprocessor
 def kept_mask(points, geom, lidar_range, range_mask=False, ego_mask=False):
-    """the rule of csrc/bev_points.hpp -> (kept (M,) bool, indices (M, 3) int64 (garbage where not kept), the smallest distance of a
+    """the rule of csrc/bev_points.hip -> (kept (M,) bool, indices (M, 3) int64 (garbage where not kept), the smallest distance of a
     FINITE in-map coordinate to a cell boundary, in cells)"""
     p = np.asarray(points)
     assert p.dtype == np.float32

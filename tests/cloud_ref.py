@@ -1,4 +1,4 @@
-"""NumPy restatement of ops.prepare_points (csrc/cloud_prep.hpp): stages 1 - 6 and the box rules, every floating-point operation
+"""NumPy restatement of ops.prepare_points (csrc/cloud_prep.hip): stages 1 - 6 and the box rules, every floating-point operation
 written out with the operator's association - the projection term by term, never as np.dot (BLAS chooses its own order and may
 fuse).  NumPy's element-wise multiply and add are single IEEE operations, so the device result must equal this bit for bit."""
 import numpy as np

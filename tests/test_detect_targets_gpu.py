@@ -1,4 +1,4 @@
-"""The detection targets and the PointPillar detection loss on the GPU: csrc/detect_targets.hpp through ops.boxes_standup /
+"""The detection targets and the PointPillar detection loss on the GPU: csrc/detect_targets.hip through ops.boxes_standup /
 detect_targets / pointpillar_loss, host.VoxelPostprocessor.generate_label / generate_label_batch and host.PointPillarLoss, against
 the reference's own run (tests/golden/gv27_detect_labels.npz, cases of tests/golden/cases_labels.py) and, for the loss, against
 float64 autograd of the restatement (tests/labels_ref.py).

@@ -1,10 +1,10 @@
-"""The LiDAR BEV (PIXOR) pre- and post-processor on the GPU: csrc/bev_points.hpp and csrc/bev_detect.hpp through ops.bev_points /
-bev_labels / bev_post_process, host.BevPreprocessor and host.LidarBevPostprocessor, against the reference's own run
+"""The LiDAR BEV (PIXOR) pre- and post-processor on the GPU: csrc/bev_points.hip, csrc/bev_labels.hip and the bev mode of
+csrc/detect_post.hip through ops.bev_points / bev_labels / bev_post_process, host.BevPreprocessor and host.LidarBevPostprocessor, against the reference's own run
 (tests/golden/gv28_lidar_bev.npz, the cases of tests/golden/cases_bev.py) and the float64 restatement tests/bev_ref.py.
 
 Gates.  Occupancy, the class channel, bev_corners, num_valid, the picked pixel indices and the count are compared EXACTLY: the cases
 keep every decision off a rounding edge or on an exact hit (asserted on the CPU by tests/test_lidar_bev.py and by the generator).
-  intensity   against the float64 mean: the kernel's stated bound 2^-33 + 2^-24 |mean| (1 + 2^-20) (csrc/bev_points.hpp); against the
+  intensity   against the float64 mean: the kernel's stated bound 2^-33 + 2^-24 |mean| (1 + 2^-20) (csrc/bev_points.hip); against the
               fixture: that bound plus the reference's own stored deviation from the float64 mean (its fp32 running sum).
   label map   regression channels within 1 fp32 ulp of the float64 restatement (fp64 arithmetic, one cast; the device's fp64 cos /
               sin / log differ from the host's by parts of an fp64 ulp); against the fixture: 1 ulp plus the stored deviation.

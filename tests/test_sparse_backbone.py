@@ -1,4 +1,4 @@
-"""The sparse 3-D backbone (host.MeanVFE, host.VoxelBackBone8x, host.HeightCompression; csrc/sparse_conv.hpp) without a device: the
+"""The sparse 3-D backbone (host.MeanVFE, host.VoxelBackBone8x, host.HeightCompression; csrc/sparse_conv.hip) without a device: the
 dense restatement tests/sparse_ref.py is pinned against a brute-force per-voxel, per-tap loop (so that the mask-convolution
 construction is not its own witness), the shape chain, the case generator, the state_dict, the lowered weights, the workspace size,
 the refusals (CPU tensors, train(), the C ABI's argument validation before any launch) and the launch traces."""

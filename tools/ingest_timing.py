@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""ops.resize_pil_bilinear (csrc/image_ingest.hpp) on one GPU at the nuScenes shape: six decoded 900 x 1600 frames -> (6, 3, 224, 480)
+"""ops.resize_pil_bilinear (csrc/image_ingest.hip) on one GPU at the nuScenes shape: six decoded 900 x 1600 frames -> (6, 3, 224, 480)
 fp32 (resize to 270 x 480, top 46 rows cut, ToTensor), one launch.  HIP events after warm-up, `--steps` batches of `--calls` calls
 between one event pair each, the median - eager (the host's per-call work included) and replayed from one captured graph of the same
 `--calls` calls (the device's time, us_per_call); next to the time the bytes the call has to move (every source byte once, every output byte

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""host.MeanVFE -> host.VoxelBackBone8x -> host.HeightCompression (csrc/sparse_conv.hpp) on one GPU at the grid of the reference class's
+"""host.MeanVFE -> host.VoxelBackBone8x -> host.HeightCompression (csrc/sparse_conv.hip) on one GPU at the grid of the reference class's
 own comment: sparse shape (41, 1600, 1408), one agent, a synthetic clustered scene of about 40 k voxels (Gaussian clusters of voxels near
 the ground, sigma (1.5, 4, 4) cells - no recorded cloud is part of this repository).  Per compute mode (bf16, fp32):
   * rows per level, and the share of (32-row tile, tap) pairs the convolution skips because no row of the tile has the tap - counted

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""ops.prepare_points (csrc/cloud_prep.hpp) on one GPU at the workload's own shape: 5 agents x 65 536 points, every stage on (ego
+"""ops.prepare_points (csrc/cloud_prep.hip) on one GPU at the workload's own shape: 5 agents x 65 536 points, every stage on (ego
 mask, fp64 projection, flip / rotation / scaling, range mask, compaction), against the same steps written with torch indexing on the
 device - an fp64 matmul per agent, boolean masks, `cat` - in the same job.  HIP events after warm-up, `--steps` batches of 20 calls
 between one event pair each, medians; next to the operator's time an upper bound on the HBM bytes it moves per point (scatter counted as
