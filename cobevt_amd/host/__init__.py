@@ -23,6 +23,7 @@ from .cross_view_transformer_disconet import CrossViewTransformerDiscoNet  # noq
 from .pillar_vfe import PFNLayer, PillarVFE  # noqa: F401
 from .point_pillar_scatter import PointPillarScatter  # noqa: F401
 from .sp_voxel_preprocessor import SpVoxelPreprocessor  # noqa: F401
+from .sp_voxel_preprocessor_3d import SpVoxelPreprocessor3D  # noqa: F401
 from .base_bev_backbone import BaseBEVBackbone  # noqa: F401
 from .point_pillar_fusebevt import PointPillarFuseBEVT  # noqa: F401
 from .self_attn import AttFusion  # noqa: F401

@@ -152,6 +152,8 @@ SIGNATURES = {
     "cobevt_gather_rows": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_long] + [ctypes.c_int] * 4 + [_vp]),
     "cobevt_voxelize_scratch": (ctypes.c_int, [_c_long_p, _c_long_p]),
     "cobevt_voxelize_points": (ctypes.c_int, [_vp] * 7 + [_c_long_p, _c_float_p, _vp]),
+    "cobevt_voxelize3d_scratch": (ctypes.c_int, [_c_long_p, _c_long_p]),
+    "cobevt_voxelize3d_points": (ctypes.c_int, [_vp] * 7 + [_c_long_p, _c_float_p, _vp]),
     "cobevt_detect_scratch": (ctypes.c_int, [ctypes.c_long, _c_long_p]),
     "cobevt_detect_post": (ctypes.c_int, [ctypes.POINTER(_vp)] * 3 + [_vp, _c_int_p, ctypes.c_int, ctypes.c_int, ctypes.c_float,
                                           ctypes.c_float] + [_vp] * 5 + [_vp]),

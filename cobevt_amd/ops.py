@@ -1289,46 +1289,105 @@ def voxelize_points(points, point_offsets, lidar_range, voxel_size, max_points=3
     `out=` held, or are uninitialised): clearing them would cost more than the operator.  out = the four tensors to write into;
     workspace = an int32 tensor of at least voxelize_workspace_ints(...) elements (default: one cached per shape and device).
     Bitwise reproducible: nothing depends on scheduling."""
+    return _voxelize("voxelize_points", points, point_offsets, lidar_range, voxel_size, max_points, max_voxels, range_mask, ego_mask, out,
+                     workspace, None)
+
+
+def _voxelize(what, points, point_offsets, lidar_range, voxel_size, max_points, max_voxels, range_mask, ego_mask, out, workspace, slots):
+    """voxelize_points (slots None: the dense tables, nz = 1) and voxelize_points_3d (slots: the hash table's entries, 0 = the default)"""
     _need_cuda(points, point_offsets, workspace)
     if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 4 or not points.is_contiguous():
-        raise CobevtHipError("voxelize_points: points must be contiguous fp32 (M, 4) as [x, y, z, intensity], got %s %s"
-                             % (points.dtype, tuple(points.shape)))
-    offs = _index_i32(point_offsets, "voxelize_points: point_offsets")
+        raise CobevtHipError("%s: points must be contiguous fp32 (M, 4) as [x, y, z, intensity], got %s %s"
+                             % (what, points.dtype, tuple(points.shape)))
+    offs = _index_i32(point_offsets, what + ": point_offsets")
     if offs.dim() != 1 or offs.shape[0] < 2:
-        raise CobevtHipError("voxelize_points: point_offsets must be (N + 1,) with N >= 1 agents, got %s" % (tuple(offs.shape),))
+        raise CobevtHipError("%s: point_offsets must be (N + 1,) with N >= 1 agents, got %s" % (what, tuple(offs.shape)))
     if max_voxels is None or int(max_voxels) < 1:
-        raise CobevtHipError("voxelize_points: max_voxels (per agent, >= 1) is required")
+        raise CobevtHipError("%s: max_voxels (per agent, >= 1) is required" % what)
     nx, ny, nz = voxel_grid_size(lidar_range, voxel_size)
-    if nz != 1:
+    if slots is None and nz != 1:
         raise CobevtHipError("voxelize_points: the pillar front end implements nz = 1 (one voxel over the height), got grid (%d, %d, %d)"
                              % (nx, ny, nz))
     t, n, m, mv = int(max_points), offs.shape[0] - 1, points.shape[0], int(max_voxels)
     if t < 1 or t > PILLAR_MAX_POINTS:
-        raise CobevtHipError("voxelize_points: 1 <= max_points <= T = %d points per voxel are supported, got %d" % (PILLAR_MAX_POINTS, t))
-    if nx < 1 or ny < 1:
-        raise CobevtHipError("voxelize_points: empty grid (%d, %d, %d)" % (nx, ny, nz))
+        raise CobevtHipError("%s: 1 <= max_points <= T = %d points per voxel are supported, got %d" % (what, PILLAR_MAX_POINTS, t))
+    if nx < 1 or ny < 1 or nz < 1:
+        raise CobevtHipError("%s: empty grid (%d, %d, %d)" % (what, nx, ny, nz))
     dev, pcap = points.device, n * mv
-    dims = (ctypes.c_long * 9)(m, n, t, mv, nx, ny, nz, int(bool(range_mask)), int(bool(ego_mask)))
+    flags = (int(bool(range_mask)), int(bool(ego_mask)))
+    if slots is None:
+        dims = (ctypes.c_long * 9)(m, n, t, mv, nx, ny, nz, *flags)
+        key, ws_ints = (dev, m, n, t, mv, nx, ny), lambda: voxelize_workspace_ints(m, n, (nx, ny, nz), t, mv)       # noqa: E731
+    else:
+        dims = (ctypes.c_long * 10)(m, n, t, mv, nx, ny, nz, *flags, slots)
+        key, ws_ints = (dev, "3d", m, n, t, mv, slots), lambda: voxelize3d_workspace_ints(m, n, t, mv, slots)        # noqa: E731
     geom = (ctypes.c_float * 9)(*[float(v) for v in list(lidar_range) + list(voxel_size)])
     if workspace is None:
-        key = (dev, m, n, t, mv, nx, ny)
         workspace = _VOXEL_WS.get(key)
         if workspace is None:
-            workspace = _VOXEL_WS[key] = torch.empty(voxelize_workspace_ints(m, n, (nx, ny, nz), t, mv), device=dev, dtype=torch.int32)
+            workspace = _VOXEL_WS[key] = torch.empty(ws_ints(), device=dev, dtype=torch.int32)
     else:
-        need = voxelize_workspace_ints(m, n, (nx, ny, nz), t, mv)
+        need = ws_ints()
         if workspace.dtype != torch.int32 or not workspace.is_contiguous() or workspace.numel() < need or workspace.device != dev:
-            raise CobevtHipError("voxelize_points: workspace= must be a contiguous int32 tensor of at least %d elements on %s" % (need, dev))
+            raise CobevtHipError("%s: workspace= must be a contiguous int32 tensor of at least %d elements on %s" % (what, need, dev))
+        if slots is not None and workspace.data_ptr() % 8:
+            raise CobevtHipError("%s: workspace= must start on an 8-byte boundary (the table's 64-bit keys lead it)" % what)
     shapes = [((pcap, t, 4), torch.float32), ((pcap, 4), torch.int32), ((pcap,), torch.int32), ((n,), torch.int32)]
     if out is None:
         out = [None] * 4
     elif len(out) != 4:
-        raise CobevtHipError("voxelize_points: out= is (voxel_features, voxel_coords, voxel_num_points, num_voxels)")
-    vf, coords, npts, nvox = [_canvas(o, s, d, dev, "voxelize_points") for o, (s, d) in zip(out, shapes)]
-    cost = lambda: (0.0, 32.0 * m + 16.0 * m + 16.0 * (n * ny * nx) + 24.0 * pcap)         # noqa: E731
-    with _timed("voxelize|M%d N%d T%d %dx%d" % (m, n, t, ny, nx), cost):
-        _L.call("cobevt_voxelize_points", _p(points), _p(offs), _p(vf), _p(coords), _p(npts), _p(nvox), _p(workspace), dims, geom, _stream())
+        raise CobevtHipError("%s: out= is (voxel_features, voxel_coords, voxel_num_points, num_voxels)" % what)
+    vf, coords, npts, nvox = [_canvas(o, s, d, dev, what) for o, (s, d) in zip(out, shapes)]
+    if slots is None:
+        cost = lambda: (0.0, 32.0 * m + 16.0 * m + 16.0 * (n * ny * nx) + 24.0 * pcap)         # noqa: E731
+        with _timed("voxelize|M%d N%d T%d %dx%d" % (m, n, t, ny, nx), cost):
+            _L.call("cobevt_voxelize_points", _p(points), _p(offs), _p(vf), _p(coords), _p(npts), _p(nvox), _p(workspace), dims, geom, _stream())
+    else:
+        table = voxelize3d_table_slots(m, slots)
+        cost = lambda: (0.0, 32.0 * m + 16.0 * m + 24.0 * table + 24.0 * pcap)                 # noqa: E731
+        with _timed("voxelize3d|M%d N%d T%d %dx%dx%d S%d" % (m, n, t, nz, ny, nx, table), cost):
+            _L.call("cobevt_voxelize3d_points", _p(points), _p(offs), _p(vf), _p(coords), _p(npts), _p(nvox), _p(workspace), dims, geom,
+                    _stream())
     return vf, coords, npts, nvox
+
+
+def voxelize3d_table_slots(num_points, table_slots=None):
+    """entries of voxelize_points_3d's hash table: table_slots, or by default the smallest power of two >= max(2 M, 64), at most 2^31"""
+    if table_slots:
+        return int(table_slots)
+    slots = 64
+    while slots < 2 * int(num_points):
+        slots *= 2
+    return min(slots, 1 << 31)
+
+
+def voxelize3d_workspace_ints(num_points, num_agents, max_points, max_voxels, table_slots=None):
+    """int32 elements of voxelize_points_3d's workspace for M points of N agents (cobevt_voxelize3d_scratch): it follows M, the table
+    (table_slots, default: voxelize3d_table_slots) and N max_voxels, not the grid"""
+    dims = (ctypes.c_long * 10)(int(num_points), int(num_agents), int(max_points), int(max_voxels), 1, 1, 1, 0, 0, int(table_slots or 0))
+    need = ctypes.c_long(0)
+    _L.call("cobevt_voxelize3d_scratch", dims, ctypes.byref(need))
+    return need.value
+
+
+def voxelize_points_3d(points, point_offsets, lidar_range, voxel_size, max_points=32, max_voxels=None, range_mask=False, ego_mask=False,
+                       out=None, workspace=None, table_slots=None):
+    """voxelize_points on a 3-D grid (csrc/voxelize.hip, cobevt_voxelize3d_points): the voxel dict of host.MeanVFE / VoxelBackBone8x from
+    raw points, without a host synchronisation.  Arguments, drop rules, numbering, cap, padding rows and `out=` exactly as
+    voxelize_points; the cell is (z, y, x) with z = floor((p.z - z0) / voxel z) in [0, nz), any nz >= 1 (each of nx, ny, nz <= 2^24).
+    -> voxel_features (N max_voxels, T, 4) fp32, voxel_coords (N max_voxels, 4) int32 [a, z, y, x], voxel_num_points, num_voxels (N,);
+    on an nz = 1 grid all four equal voxelize_points'.
+    The per-cell tables are indexed through an open-addressed hash table of table_slots entries (a power of two > M; default
+    voxelize3d_table_slots(M): a load of at most one half), so time and workspace follow M, the table and N max_voxels and not the grid - the
+    dense tables of voxelize_points would take 1.48 GB per agent at (1408, 1600, 41).  A smaller table only lengthens the probe
+    sequences; the result is the same.  workspace = an int32 tensor of at least voxelize3d_workspace_ints(...) elements on an 8-byte
+    boundary (default: one cached per shape and device).  Bitwise reproducible: nothing in the outputs depends on scheduling."""
+    slots = 0 if table_slots is None else int(table_slots)
+    if table_slots is not None and (slots < 1 or slots & (slots - 1) or slots <= points.shape[0] or slots > 1 << 31):
+        raise CobevtHipError("voxelize_points_3d: table_slots must be a power of two above the %d points and at most 2^31, got %r"
+                             % (points.shape[0], table_slots))
+    return _voxelize("voxelize_points_3d", points, point_offsets, lidar_range, voxel_size, max_points, max_voxels, range_mask, ego_mask,
+                     out, workspace, slots)
 
 
 CLOUD_MAX_BOXES = 128      # ground-truth rows cobevt_prepare_points augments (one thread each of one workgroup)

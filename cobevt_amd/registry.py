@@ -55,6 +55,7 @@ def create_model(hypes):
 
 _PREPROCESSORS = {"BevPreprocessor": ("bev_preprocessor", "BevPreprocessor"),
                   "SpVoxelPreprocessor": ("sp_voxel_preprocessor", "SpVoxelPreprocessor"),
+                  "SpVoxelPreprocessor3D": ("sp_voxel_preprocessor_3d", "SpVoxelPreprocessor3D"),
                   "RgbPreprocessor": ("rgb_preprocessor", "RgbPreProcessor")}
 _POSTPROCESSORS = {"BevPostprocessor": ("lidar_bev_postprocessor", "LidarBevPostprocessor"),
                    "VoxelPostprocessor": ("voxel_postprocessor", "VoxelPostprocessor"),
@@ -70,7 +71,7 @@ def _build(table, name, what):
 
 
 def build_preprocessor(preprocess_cfg, train):
-    """preprocess_cfg['core_method'] in BevPreprocessor / SpVoxelPreprocessor / RgbPreprocessor -> the instance"""
+    """preprocess_cfg['core_method'] in BevPreprocessor / SpVoxelPreprocessor / SpVoxelPreprocessor3D / RgbPreprocessor -> the instance"""
     return _build(_PREPROCESSORS, preprocess_cfg["core_method"], "preprocessor")(preprocess_params=preprocess_cfg, train=train)
 
 

@@ -887,6 +887,27 @@ int cobevt_voxelize_scratch(const long* dims, long* workspace_ints);
 int cobevt_voxelize_points(const float* points, const int* point_offsets, float* voxel_features, int* voxel_coords,
                            int* voxel_num_points, int* num_voxels, int* workspace, const long* dims, const float* geom,
                            hipStream_t stream);
+/*
+ * The same on a 3-D grid (csrc/voxelize.hip): cells (z, y, x), voxel_coords (Pcap, 4) = [a, z, y, x] - the voxel dict cobevt_mean_vfe
+ * and cobevt_sparse_index read.  Pointers, geom, drop rules, numbering, cap, outputs and padding rows exactly as
+ * cobevt_voxelize_points, with floor((p.z - z0) / voxel z) in [0, nz) in place of its single cell over the height; on an nz = 1 grid
+ * the four outputs are bit-identical to cobevt_voxelize_points'.
+ *   dims  = [M, N, T, max_voxels, nx, ny, nz, range_mask, ego_mask, slots] (host), T in 1 .. 32, nx, ny, nz in 1 .. 2^24 each (every
+ *   cell index exact in fp32) and N nx ny nz <= 2^62; slots: the entries of the hash table below - a power of two, M < slots <= 2^31 -
+ *   or 0 for the default, the smallest power of two >= max(2 M, 64).
+ * The per-cell tables of cobevt_voxelize_points are indexed by the slot that the cell's 64-bit key agent * (nx ny nz) + (z ny + y) nx
+ * + x holds in an open-addressed table (64-bit compare-and-swap on the key word, linear probing, at most `slots` probes, no thread
+ * waits on another; slots > M leaves an empty slot at all times), so time and workspace follow M, slots and N max_voxels and not the
+ * grid.  Which slot a key gets depends on scheduling and stays inside the workspace; the outputs do not (bitwise reproducible).
+ * Seven launches, integer atomics only, no host read, no allocation.  workspace: cobevt_voxelize3d_scratch(dims) ints (6 slots +
+ * N max_voxels + 2 M + ...), contents irrelevant on entry, 8-byte aligned (the keys lead it); points, voxel_features and voxel_coords
+ * 16-byte aligned.  A null pointer is COBEVT_ERR_ARG; a T, grid, slots, alignment or voxel size outside the above COBEVT_ERR_SHAPE,
+ * before any launch.
+ */
+int cobevt_voxelize3d_scratch(const long* dims, long* workspace_ints);
+int cobevt_voxelize3d_points(const float* points, const int* point_offsets, float* voxel_features, int* voxel_coords,
+                             int* voxel_num_points, int* num_voxels, int* workspace, const long* dims, const float* geom,
+                             hipStream_t stream);
 
 /*
  * LiDAR detection output (csrc/detect_post.hip): OpenCOOD's VoxelPostprocessor.post_process - box decode, box filters, the cut at

@@ -8,7 +8,10 @@ the ground, sigma (1.5, 4, 4) cells - no recorded cloud is part of this reposito
     (layers of one shape on one level share a line), median of `--steps` forwards, with the fitted capacities;
   * the whole forward: HIP events around `--steps` eager forwards, and around replays of one captured graph of it (the device's
     time, without the host's per-call work), medians - with the default (provable) capacities and with capacities fitted to the scene
-    (1.25 x the live rows), which is what sizes every launch.
+    (1.25 x the live rows), which is what sizes every launch;
+  * from points: the same scene as a cloud - every voxel's 1 .. 5 points placed inside its cell, shuffled, about 120 k points -
+    through host.SpVoxelPreprocessor3D (csrc/voxelize.hip's hash-table form) on the (1408, 1600, 41) grid: the voxelisation alone,
+    and voxelisation -> MeanVFE -> VoxelBackBone8x -> HeightCompression as one eager forward and one captured graph.
 There is nothing to compare with: spconv is not installed and the dense restatement does not fit at this size.  One JSON line, printed
 and written to --out (default profiles/sparse_backbone_timing.json).
 Usage (GPU box): python tools/sparse_timing.py [--steps 20] [--voxels 40000] [--out PATH]"""
@@ -46,6 +49,22 @@ def scene(voxels, dev, seed=0):
     npts = torch.randint(1, SLOTS + 1, (len(cells),), generator=g, dtype=torch.int32)
     vf = torch.rand(len(cells), SLOTS, CHANNELS, generator=g) * (torch.arange(SLOTS)[None, :, None] < npts[:, None, None])
     return {"voxel_features": vf.to(dev), "voxel_num_points": npts.to(dev), "voxel_coords": coords.to(dev), "batch_size": 1}
+
+
+VOXEL_SIZE = [0.05, 0.05, 0.1]
+LIDAR_RANGE = [0.0, -40.0, -3.0, 70.4, 40.0, 1.1]          # (1408, 1600, 41) cells: the sparse shape, whose top plane the scene may use
+
+
+def cloud(data, dev, seed=1):
+    """the scene's voxel dict as raw points: voxel_num_points points inside every cell, in a random order -> (points, offsets)"""
+    g = torch.Generator().manual_seed(seed)
+    coords, npts = data["voxel_coords"].cpu(), data["voxel_num_points"].cpu()
+    cell = coords[:, [3, 2, 1]].repeat_interleave(npts.long(), 0).double()
+    frac = 0.1 + 0.8 * torch.rand(len(cell), 3, generator=g, dtype=torch.float64)
+    xyz = torch.tensor(LIDAR_RANGE[:3], dtype=torch.float64) + (cell + frac) * torch.tensor(VOXEL_SIZE, dtype=torch.float64)
+    pts = torch.cat([xyz, torch.rand(len(cell), 1, generator=g, dtype=torch.float64)], 1).float()
+    pts = pts[torch.randperm(len(pts), generator=g)].contiguous()
+    return pts.to(dev), torch.tensor([0, len(pts)], dtype=torch.int32, device=dev)
 
 
 def skipped_share(x_in, x_out, conv, tile):
@@ -91,6 +110,18 @@ def main():
     def forward():
         return to_bev(backbone(vfe(dict(data))))
 
+    points, offsets = cloud(data, dev)
+    voxels = int(data["voxel_coords"].shape[0])
+    pre = host.SpVoxelPreprocessor3D({"cav_lidar_range": LIDAR_RANGE, "args": {"voxel_size": VOXEL_SIZE, "max_points_per_voxel": SLOTS,
+                                                                              "max_voxel_train": voxels, "max_voxel_test": voxels}}, False)
+    assert tuple(pre.grid_size) == (GRID[0], GRID[1], GRID[2] + 1)
+
+    def voxelise():
+        return pre.preprocess_batch(points, offsets)
+
+    def from_points():
+        return to_bev(backbone(vfe(voxelise())))
+
     def timed(fn):
         ts = []
         for _ in range(args.steps):
@@ -104,7 +135,7 @@ def main():
 
     line = {"what": "MeanVFE -> VoxelBackBone8x -> HeightCompression, sparse shape (41, 1600, 1408), one agent, synthetic clustered scene; "
                     "ms: median of --steps (min, max); skipped: share of (32-row tile, tap) pairs without a present input row",
-            "device": torch.cuda.get_device_name(0), "steps": args.steps, "voxels": int(data["voxel_coords"].shape[0]), "modes": {}}
+            "device": torch.cuda.get_device_name(0), "steps": args.steps, "voxels": voxels, "points": int(points.shape[0]), "modes": {}}
     layers = [name for name, _, _ in backbone._layers()]
     for mode in ("bf16", "fp32"):
         res = {}
@@ -145,6 +176,22 @@ def main():
                 for fam, d in fams.items():
                     per.setdefault(fam, []).append(d["ms"] / d["calls"])
             res["ms_per_call_fitted_capacities"] = {fam: round(median(v), 4) for fam, v in per.items()}
+            backbone.level_capacities = None
+            res["from_points"] = {}
+            for label, fn in (("voxelize_ms", voxelise), ("forward_ms", from_points)):
+                for _ in range(3):
+                    fn()
+                torch.cuda.synchronize()
+                eager = timed(fn)
+                graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graph):
+                    fn()
+                graph.replay()
+                torch.cuda.synchronize()
+                res["from_points"][label] = {"eager": eager, "graph_replay": timed(graph.replay)}
+                del graph
+                torch.cuda.synchronize()
+            res["from_points"]["voxels"] = int(voxelise()["num_voxels"][0])
         line["modes"][mode] = res
     text = json.dumps(line)
     print(text, flush=True)
