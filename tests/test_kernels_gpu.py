@@ -682,6 +682,8 @@ def test_attn_mlp_chain_fused(cuda, c, hd, rows, post, proj_bias, skip):
     ref = F.layer_norm(zz, (c,), g2, be2, 1e-5) if post else zz
     s = ref.abs().max().item()
     e_f, e_3 = (y.float().cpu() - ref).abs().max().item(), (y3.float().cpu() - ref).abs().max().item()
+    # (a max-norm gate: what each instantiation of the row-local kernels may store per element is tests/test_rows_bounds_gpu.py,
+    # DESIGN.md 3u - rows chain_* of rows_bounds_ref.CASES; the gates here and in the row-chain tests below stay for fused vs unfused)
     assert e_f <= 3e-2 * s, "fused chain: %.3e vs scale %.3e" % (e_f, s)
     assert e_3 <= 3e-2 * s
     assert (y.float() - y3.float()).abs().max().item() <= 3e-2 * s
