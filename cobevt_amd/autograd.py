@@ -1605,6 +1605,104 @@ def scatter_rows(rows, coords, num_agents, grid):
     return ScatterRowsFn.apply(rows, coords, int(num_agents), (int(grid[0]), int(grid[1])))
 
 
+# ----------------------------------------------------------------------------------------------
+# the sparse 3-D voxel backbone in train() mode (csrc/sparse_conv.hip)
+# ----------------------------------------------------------------------------------------------
+def _sparse_bn_frozen(bn):
+    """False: batch statistics (bn.training, or a norm without running statistics); True: the frozen running statistics.
+    BatchNorm1d(momentum=None) raises: the kernels keep an exponential running average."""
+    if bn.training or not bn.track_running_stats or bn.running_mean is None:
+        if bn.training and bn.track_running_stats and bn.momentum is None:
+            raise CobevtHipError("BatchNorm1d(momentum=None): the sparse training kernels keep an exponential running average and need a "
+                                 "numeric momentum")
+        return False
+    return True
+
+
+class SparseConvBnReluFn(torch.autograd.Function):
+    """One layer of VoxelBackBone8x in train() mode: SubMConv3d / SparseConv3d (bias=False) -> BatchNorm1d over the live rows -> ReLU.
+    feats (rows, input row) fp32 are the features of the level `x` (an ops.SparseConvTensor: indices, num, workspace, row_map - no
+    gradient flows into those), `level` the output level (x for SubM); conv / bn the parameter containers (bn's own .training flag picks
+    batch or frozen running statistics; its three buffers are updated in place by the kernel).  Forward: ops.sparse_conv_raw on the
+    unfolded weights, ops.sparse_bn_relu; saves x, z, y and the statistics.  Backward: ops.sparse_bn_relu_bwd, ops.sparse_conv_dgrad (only
+    when feats needs a gradient: not for conv_input) and ops.sparse_conv_wgrad.  fp32 in and out under any autocast and any compute dtype."""
+
+    @staticmethod
+    @_amp_fwd
+    def forward(ctx, feats, weight, gamma, beta, x, level, conv, bn, tables=None):
+        frozen = _sparse_bn_frozen(bn)
+        feats = _f32c(feats, "sparse features")
+        wf, wt = tables if tables is not None else ops.sparse_train_weights(weight)
+        xt = ops.SparseConvTensor(feats, x.indices, x.num, x.spatial_shape, x.batch_size, x.workspace, row_map=x.row_map)
+        cout = int(weight.shape[0])
+        geom = (conv.kernel_size, conv.stride, conv.padding, bool(conv.subm))
+        z = ops.sparse_conv_raw(xt, level, wf, cout, *geom)
+        g = _f32c(gamma.detach(), "gamma")
+        stat, y = ops.sparse_bn_relu(z, level.num, g, _f32c(beta.detach(), "beta"), bn, frozen)
+        ctx.save_for_backward(feats, z, y, stat, g, wt)
+        ctx.levels = (xt, level)
+        ctx.cfg = (geom, frozen, int(weight.shape[4]))
+        return y
+
+    @staticmethod
+    @_amp_bwd
+    def backward(ctx, dy):
+        feats, z, y, stat, g, wt = ctx.saved_tensors
+        xt, level = ctx.levels
+        geom, frozen, cin = ctx.cfg
+        dz, dg, db = ops.sparse_bn_relu_bwd(_f32c(dy.float(), "dy"), y, z, level.num, g, stat, frozen)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            lvl_in = ops.SparseConvTensor(None, xt.indices, xt.num, xt.spatial_shape, xt.batch_size, xt.workspace, row_map=xt.row_map)
+            dx = ops.sparse_conv_dgrad(dz, lvl_in, level, wt, int(feats.shape[1]), *geom)
+        dw = ops.sparse_conv_wgrad(xt, level, dz, cin, *geom) if ctx.needs_input_grad[1] else None
+        return dx, dw, dg if ctx.needs_input_grad[2] else None, db if ctx.needs_input_grad[3] else None, None, None, None, None, None
+
+
+def sparse_conv_bn_relu(x, conv, bn, capacity=None, workspace=None, out_level=None):
+    """x (ops.SparseConvTensor with fp32 features) through one conv + BatchNorm1d + ReLU block in train() mode -> SparseConvTensor whose
+    .features carry the autograd graph.  Strided: the output level comes from ops.sparse_downsample(x, ..., capacity, workspace), or is
+    `out_level`."""
+    if conv.subm:
+        level = x
+    elif out_level is not None:
+        level = out_level
+    else:
+        level = ops.sparse_downsample(x, conv.kernel_size, conv.stride, conv.padding, capacity, workspace)
+    _sparse_bn_frozen(bn)                    # momentum=None raises before anything is launched
+    # lowered HERE, from the Parameter object itself: the cache of ops.sparse_train_weights is per object, and what a Function's forward
+    # receives need not be that object (autocast hands it a cast copy)
+    tables = ops.sparse_train_weights(conv.weight)
+    y = SparseConvBnReluFn.apply(x.features, conv.weight, bn.weight, bn.bias, x, level, conv, bn, tables)
+    return ops.SparseConvTensor(y, level.indices, level.num, level.spatial_shape, level.batch_size, level.workspace)
+
+
+class SparseDenseFn(torch.autograd.Function):
+    """HeightCompression's dense() with its adjoint: features (capacity, C) fp32 of the level `x` -> (N, H, W, C D) channels-last, zero
+    off the active set (ops.sparse_dense_nhwc); the backward gathers every live row's cell of the canvas gradient (ops.sparse_dense_bwd)"""
+
+    @staticmethod
+    @_amp_fwd
+    def forward(ctx, feats, x):
+        feats = _f32c(feats, "sparse features")
+        out = ops.sparse_dense_nhwc(ops.SparseConvTensor(feats, x.indices, x.num, x.spatial_shape, x.batch_size, x.workspace))
+        ctx.level = ops.SparseConvTensor(None, x.indices, x.num, x.spatial_shape, x.batch_size, x.workspace)
+        ctx.channels = int(feats.shape[1])
+        return out
+
+    @staticmethod
+    @_amp_bwd
+    def backward(ctx, dcanvas):
+        return ops.sparse_dense_bwd(_f32c(dcanvas.float(), "d canvas"), ctx.level, ctx.channels), None
+
+
+def sparse_dense_nhwc(x):
+    """ops.SparseConvTensor (fp32 features carrying a graph) -> (N, H, W, C D) fp32, differentiable in the features"""
+    if x.row_map is not None:
+        raise CobevtHipError("sparse_dense: the tensor needs features in the level's row order")
+    return SparseDenseFn.apply(x.features, x)
+
+
 def _env_flags():
     """COBEVT_TRAIN_FLAGS="USE_TORCH_OPERAND_PREP=1,USE_WGRAD_BLOCKED=0": the module's USE_* switches from the environment (same-job A/B
     runs of tools/train_probe.py; never set in production)"""

@@ -50,3 +50,6 @@ from .seg_utils import cal_iou_training, mean_IU, mean_precision  # noqa: F401
 from .vanilla_seg_loss import VanillaSegLoss  # noqa: F401
 from .point_pillar_loss import PointPillarLoss  # noqa: F401
 from .train_graph import CapturedTrainStep  # noqa: F401
+# the train()-mode forwards (host.training.pillar_vfe / point_pillar_scatter / point_pillar_fusebevt, and mean_vfe / voxel_backbone8x /
+# height_compression of the SECOND-style encoder) are functions of host.training
+from . import training  # noqa: F401,E402

@@ -3,7 +3,8 @@ dense() (N, C, D, H, W) viewed as (N, C D, H, W) - channel c D + d.  ops.sparse_
 channels-last buffer, so the view costs nothing and host.BaseBEVBackbone.forward reads it without a copy.
 
 forward(batch_dict) is the reference's contract: reads 'encoded_spconv_tensor' and 'encoded_spconv_tensor_stride', writes
-'spatial_features' (N, C D, H, W), in the compute dtype, and 'spatial_features_stride'.  No parameters, no host synchronisation."""
+'spatial_features' (N, C D, H, W), in the compute dtype, and 'spatial_features_stride'.  No parameters, no host synchronisation.
+In train() mode the forward raises; host.training.height_compression is the differentiable form (autograd.SparseDenseFn)."""
 from .runtime import HipModule
 
 

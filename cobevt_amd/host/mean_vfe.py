@@ -6,7 +6,8 @@ forward(batch_dict) is the reference's contract: reads 'voxel_features' (P, T, C
 [:, :C] view of a (P, row) buffer whose rows are whole 32-byte groups with zeros behind the C channels - the row
 VoxelBackBone8x's first convolution reads, so nothing is copied between the two.  The reference sums all T slots; this sums the first
 voxel_num_points of them, the same whenever the unused slots are zero, which spconv's voxel generator guarantees.  Rows with a
-negative batch index in 'voxel_coords' (the padding rows of a fixed-size voxel dict, SpVoxelPreprocessor's convention) give zeros."""
+negative batch index in 'voxel_coords' (the padding rows of a fixed-size voxel dict, SpVoxelPreprocessor's convention) give zeros.
+In train() mode the forward raises; host.training.mean_vfe is the same launch with fp32 rows (no parameters, no graph)."""
 from .. import ops
 from . import runtime as rt
 from .runtime import HipModule

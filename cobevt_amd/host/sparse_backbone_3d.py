@@ -23,7 +23,8 @@ features, indices, num, spatial_shape, batch_size, dense()), 'encoded_spconv_ten
 bound min(cells of the level, 8 x the previous level's capacity) (2 x for conv_out), P for the input level - so nothing can be dropped
 and nothing is read back: no host synchronisation, the forward can be captured in a HIP graph and replayed on clouds of any size up to
 P rows.  `level_capacities` (five ints: the input level, conv2, conv3, conv4, conv_out; None entries keep the default) trades memory
-for the risk of dropping rows, which num[1] of each tensor counts.  Inference only: a train()-mode forward raises."""
+for the risk of dropping rows, which num[1] of each tensor counts.  This forward is the inference path: in train() mode it raises, and
+the module trains through host.training.voxel_backbone8x (batch statistics over the live rows, dgrad and wgrad on fp32 rows: DESIGN.md 3v)."""
 import math
 
 import torch

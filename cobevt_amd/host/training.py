@@ -166,6 +166,70 @@ def point_pillar_fusebevt(model, batch_dict):
     return {"fused_feature": fused.float()}
 
 
+# ----------------------------------------------------------------------------------------------
+# the SECOND-style LiDAR encoder (sub_modules/mean_vfe.py, sparse_backbone_3d.py, height_compression.py) in train() mode
+# ----------------------------------------------------------------------------------------------
+def mean_vfe(module, batch_dict):
+    """MeanVFE.forward in train() mode: no parameters and no graph - the eval launch with fp32 rows, whatever the compute dtype:
+    batch_dict['voxel_features'] (P, T, C) -> the [:, :C] view of the (P, 8) fp32 buffer voxel_backbone8x reads without a copy"""
+    vf, npts = batch_dict["voxel_features"], batch_dict["voxel_num_points"]
+    _check(vf)
+    if vf.requires_grad:
+        raise CobevtHipError("sparse backbone training: no gradient with respect to voxel_features is offered (detach the points)")
+    c = vf.shape[2]
+    rows = ops.mean_vfe(vf, npts, batch_dict.get("voxel_coords"), dtype=torch.float32, channels=ops.sparse_row_channels(c, torch.float32))
+    batch_dict["voxel_features"] = rows[:, :c]
+    return batch_dict
+
+
+def voxel_backbone8x(module, batch_dict, keep_layers=False):
+    """VoxelBackBone8x.forward in train() mode, the eval forward's batch_dict contract and keys: twelve ag.sparse_conv_bn_relu layers
+    (raw convolution on the unfolded fp32 weights, BatchNorm1d with batch statistics over the live rows of each level - or the frozen
+    running statistics where a BatchNorm1d is in eval() - and ReLU), the five active sets from the same index launches, `level_capacities`
+    honoured.  Features are fp32 under every compute dtype and under autocast; the SparseConvTensors' .features carry the graph, so a
+    loss on 'multi_scale_3d_features' reaches the weights too.  No gradient with respect to voxel_features.  keep_layers: also
+    batch_dict['sparse_layer_outputs'] = the twelve layer outputs in forward order.  The running statistics are updated in place and
+    their version counters bumped: the module's cached eval plans rebuild at the next eval forward."""
+    vf, coords = batch_dict["voxel_features"], batch_dict["voxel_coords"]
+    _check(vf)
+    if vf.requires_grad:
+        raise CobevtHipError("sparse backbone training: no gradient with respect to voxel_features is offered (detach the points)")
+    layers = module._layers()
+    for _, _, bn in layers:
+        ag._sparse_bn_frozen(bn)                                            # momentum=None raises before anything is launched
+    if vf.dim() != 2 or vf.shape[1] != layers[0][1].in_channels or coords.shape[0] != vf.shape[0]:
+        raise CobevtHipError("VoxelBackBone8x: voxel_features must be (P, %d) with one row per row of voxel_coords, got %s / %s"
+                             % (layers[0][1].in_channels, tuple(vf.shape), tuple(coords.shape)))
+    caps = list(module.level_capacities or [None] * 5)
+    if len(caps) != 5:
+        raise CobevtHipError("VoxelBackBone8x: level_capacities has five entries (the input level, conv2, conv3, conv4, conv_out), got %r" % (caps,))
+    x = ops.sparse_index(coords, batch_dict["batch_size"], module.sparse_shape, features=module._input_rows(vf, torch.float32), capacity=caps[0])
+    level, feats = 0, {}
+    for name, conv, bn in layers:
+        if not conv.subm:
+            level += 1
+        x = ag.sparse_conv_bn_relu(x, conv, bn, capacity=None if conv.subm else caps[level])
+        feats[name] = x
+    batch_dict.update({"encoded_spconv_tensor": x, "encoded_spconv_tensor_stride": 8})
+    batch_dict.update({"multi_scale_3d_features": {"x_conv1": feats["conv1.0"], "x_conv2": feats["conv2.2"], "x_conv3": feats["conv3.2"],
+                                                   "x_conv4": feats["conv4.2"]}})
+    batch_dict.update({"multi_scale_3d_strides": {"x_conv1": 1, "x_conv2": 2, "x_conv3": 4, "x_conv4": 8}})
+    if keep_layers:
+        batch_dict["sparse_layer_outputs"] = [feats[name] for name, _, _ in layers]
+    return batch_dict
+
+
+def height_compression(module, batch_dict):
+    """HeightCompression.forward in train() mode: differentiable in the features of 'encoded_spconv_tensor' ->
+    batch_dict['spatial_features'] (N, C D, H, W) fp32, the NCHW view of channels-last memory as in eval"""
+    x = batch_dict["encoded_spconv_tensor"]
+    _check(x.features)
+    y = ag.sparse_dense_nhwc(x)                                             # (N, H, W, C D)
+    batch_dict["spatial_features"] = y.permute(0, 3, 1, 2)
+    batch_dict["spatial_features_stride"] = batch_dict["encoded_spconv_tensor_stride"]
+    return batch_dict
+
+
 def _project(seq, t):
     """nn.Sequential(LayerNorm, Linear) of a cross attention on (..., d) -> (rows, inner)"""
     t = t.contiguous()

@@ -176,6 +176,13 @@ SIGNATURES = {
     "cobevt_sparse_downsample": (ctypes.c_int, [_vp] * 5 + [_c_long_p, _vp]),
     "cobevt_sparse_conv": (ctypes.c_int, [_vp] * 9 + [_c_long_p, _vp]),
     "cobevt_sparse_dense": (ctypes.c_int, [_vp] * 4 + [_c_long_p, _vp]),
+    "cobevt_sparse_train_scratch": (ctypes.c_int, [_c_long_p, _c_long_p]),
+    "cobevt_sparse_conv_raw": (ctypes.c_int, [_vp] * 8 + [_c_long_p, _vp]),
+    "cobevt_sparse_bn_relu": (ctypes.c_int, [_vp] * 10 + [_c_long_p, ctypes.c_float, ctypes.c_float, _vp]),
+    "cobevt_sparse_bn_relu_bwd": (ctypes.c_int, [_vp] * 11 + [_c_long_p, _vp]),
+    "cobevt_sparse_conv_dgrad": (ctypes.c_int, [_vp] * 7 + [_c_long_p, _vp]),
+    "cobevt_sparse_conv_wgrad": (ctypes.c_int, [_vp] * 9 + [_c_long_p, _vp]),
+    "cobevt_sparse_dense_bwd": (ctypes.c_int, [_vp] * 4 + [_c_long_p, _vp]),
 }
 
 _libs = {}

@@ -7,6 +7,7 @@ otherwise — there is no CPU path here (the CPU restatement lives in oracle/ an
 import ctypes
 import os
 import math
+import weakref
 from collections import namedtuple
 
 import numpy as np
@@ -1770,6 +1771,223 @@ def sparse_dense(x):
     n, h, w, cd = y.shape
     d = x.spatial_shape[0]
     return y.view(n, h, w, cd // d, d).permute(0, 3, 4, 1, 2)
+
+
+# ---------------------------------------------------------------------------------------------- training of the sparse backbone
+# fp32 rows only.  Every row count is a level's device word num[0]; scratch buffers are cached per size, so a captured graph replays
+# on the buffers it saw (the launches of one stream use them one after the other).
+SPARSE_ROW_CHUNKS = 64     # row chunks of cobevt_sparse_conv_wgrad and of the BatchNorm sums: ceil(ceil(num[0] / 64) / 32) * 32 rows each
+SPARSE_TRAIN_PAIRS = ((8, 16),) + SparseConvPlan.PAIRS          # (input row in channels, Cout)
+SPARSE_STAT_DOUBLES = SPARSE_ROW_CHUNKS * 2 * 128              # the BatchNorm entries' partials (cobevt_sparse_train_scratch's second size)
+_SPARSE_TRAIN_WS = {}      # (device, dtype, elements) -> scratch
+_SPARSE_TRAIN_WEIGHTS = {}  # id(weight) -> (weakref, version, data_ptr, forward table, transposed table)
+
+
+def sparse_train_scratch(cin_pad, cout, taps):
+    """(floats of the weight gradient's partials = SPARSE_ROW_CHUNKS x taps x Cout padded to 32 x input row, doubles of the
+    BatchNorm entries' partials) - independent of every capacity and grid (cobevt_sparse_train_scratch)"""
+    sizes = (ctypes.c_long * 2)(0, 0)
+    _L.call("cobevt_sparse_train_scratch", (ctypes.c_long * 3)(int(cin_pad), int(cout), int(taps)), sizes)
+    return int(sizes[0]), int(sizes[1])
+
+
+def _sparse_train_ws(dev, dtype, n):
+    key = (dev, dtype, n)
+    ws = _SPARSE_TRAIN_WS.get(key)
+    if ws is None:
+        ws = _SPARSE_TRAIN_WS[key] = torch.empty(n, device=dev, dtype=dtype)
+    return ws
+
+
+def sparse_train_weights(weight):
+    """The module weight (Cout, kz, ky, kx, Cin) fp32 -> the two operand tables of the training kernels, UNfolded: forward
+    [taps][Cout padded to 32][input row] and transposed [taps][Cin padded to 32][Cout], tap = (kz KY + ky) KX + kx.  Lowered on the
+    device by torch ops - no host round trip per optimiser step, unlike SparseConvPlan - and cached per weight OBJECT on its version
+    counter and address: hand over the nn.Parameter itself (a .detach() of it is a new object every time and would never hit; the
+    detaching is done here).  An entry goes when its weight does.  Never cached inside a graph capture: there the lowering is part of
+    the graph, so a replay follows the optimiser."""
+    if weight.dim() != 5 or weight.dtype != torch.float32:
+        raise CobevtHipError("sparse_train_weights: weight must be fp32 (Cout, kz, ky, kx, Cin), got %s %s" % (weight.dtype, tuple(weight.shape)))
+    cout, kz, ky, kx, cin = (int(d) for d in weight.shape)
+    cin_pad = sparse_row_channels(cin, torch.float32)
+    if not ((cin <= 8 and cout == 16) or (cin, cout) in SparseConvPlan.PAIRS) or (kz, ky, kx) not in ((3, 3, 3), (3, 1, 1)):
+        raise CobevtHipError("sparse_train_weights: %d -> %d channels, kernel %s; supported are <= 8 -> 16 and %s with kernel 3 or (3, 1, 1)"
+                             % (cin, cout, (kz, ky, kx), ", ".join("%d -> %d" % p for p in SparseConvPlan.PAIRS)))
+    capturing = weight.is_cuda and torch.cuda.is_current_stream_capturing()
+    ent = _SPARSE_TRAIN_WEIGHTS.get(id(weight))
+    if not capturing and ent is not None and ent[0]() is weight and ent[1:3] == (weight._version, weight.data_ptr()):
+        return ent[3], ent[4]
+    taps = kz * ky * kx
+    w = weight.detach()
+    fwd = torch.zeros((taps, (cout + 31) // 32 * 32, cin_pad), device=w.device, dtype=torch.float32)
+    fwd[:, :cout, :cin] = w.permute(1, 2, 3, 0, 4).reshape(taps, cout, cin)
+    tr = torch.zeros((taps, (cin_pad + 31) // 32 * 32, cout), device=w.device, dtype=torch.float32)
+    tr[:, :cin, :] = w.permute(1, 2, 3, 4, 0).reshape(taps, cin, cout)
+    if not capturing:
+        key = id(weight)
+        _SPARSE_TRAIN_WEIGHTS[key] = (weakref.ref(weight, lambda _, key=key: _SPARSE_TRAIN_WEIGHTS.pop(key, None)), weight._version,
+                                      weight.data_ptr(), fwd, tr)
+    return fwd, tr
+
+
+def _sparse_geometry(kernel, stride, padding, subm, what):
+    k, s, p = _triple(kernel), _triple(stride), _triple(padding)
+    if subm:
+        if (k, s, p) != ((3, 3, 3), (1, 1, 1), (1, 1, 1)):
+            raise CobevtHipError("%s: SubMConv3d is supported with kernel 3, stride 1, padding 1, got %s / %s / %s" % (what, k, s, p))
+    elif k not in ((3, 3, 3), (3, 1, 1)) or s not in ((1, 1, 1), (2, 2, 2), (2, 1, 1)) or p not in ((1, 1, 1), (0, 1, 1), (0, 0, 0)) \
+            or (k == (3, 1, 1) and p != (0, 0, 0)):
+        raise CobevtHipError("%s: kernel 3 or (3, 1, 1), stride 1, 2 or (2, 1, 1) and padding 1, (0, 1, 1) or 0 are supported, got %s / %s / %s"
+                             % (what, k, s, p))
+    return k, s, p
+
+
+def _sparse_rows_f32(t, rows, channels, what):
+    if t is None or t.dtype != torch.float32 or t.dim() != 2 or not t.is_contiguous() or (channels is not None and t.shape[1] != channels) \
+            or (rows is not None and t.shape[0] != rows):
+        raise CobevtHipError("%s must be contiguous fp32 (%s, %s), got %s" % (what, "rows" if rows is None else rows,
+                                                                               "C" if channels is None else channels,
+                                                                               None if t is None else "%s %s" % (t.dtype, tuple(t.shape))))
+    return t
+
+
+def sparse_conv_raw(x, level, wgt, cout, kernel, stride, padding, subm):
+    """z = conv(x): no BatchNorm, no ReLU (cobevt_sparse_conv_raw, the inference kernel with a plain-store epilogue).  x: the input
+    SparseConvTensor with fp32 features (rows, input row) (row_map honoured), level: the output level (x itself for SubM), wgt: the
+    forward table of sparse_train_weights -> z (level.capacity, cout) fp32, zeros at and past level.num[0]"""
+    k, s, p = _sparse_geometry(kernel, stride, padding, subm, "sparse_conv_raw")
+    f = _sparse_rows_f32(x.features, None if x.row_map is not None else x.capacity, wgt.shape[2], "sparse_conv_raw: x.features")
+    _need_cuda(f, x.workspace, x.num, x.row_map, level.indices, level.num, wgt)
+    cap, cin_pad = level.capacity, int(f.shape[1])
+    z = torch.empty((cap, cout), device=f.device, dtype=torch.float32)
+    dims = (ctypes.c_long * 17)(x.batch_size, *(x.spatial_shape + (f.shape[0], cap, cin_pad, cout) + k + s + p))
+    taps = k[0] * k[1] * k[2]
+    fam = "sparse_conv_raw|k%d%d%d s%d%d%d %d->%d %dx%dx%d" % (k + s + (cin_pad, cout) + level.spatial_shape)
+    with _timed(fam, lambda: (2.0 * cap * taps * cin_pad * cout, 4.0 * (cap * taps * cin_pad + wgt.numel() + cap * cout))):
+        _L.call("cobevt_sparse_conv_raw", _p(f), _p(x.workspace), _p(x.num), _p(x.row_map), _p(level.indices), _p(level.num), _p(wgt), _p(z), dims,
+                _stream(), variant="")
+    return z
+
+
+def sparse_bn_relu(z, num, gamma, beta, bn=None, frozen=False, eps=1e-3, momentum=0.01, want_y=True):
+    """BatchNorm1d + ReLU over the num[0] live rows of z (capacity, C) (cobevt_sparse_bn_relu) -> (stat (4, C) fp32 = [mean, rstd,
+    scale, shift], y | None).  bn: the nn.BatchNorm1d whose eps / momentum hold and whose running statistics are updated in place
+    (frozen: read instead, nothing updated); its buffers' version counters are bumped, so eval plans folded from them rebuild."""
+    _sparse_rows_f32(z, None, None, "sparse_bn_relu: z")
+    cap, c = (int(v) for v in z.shape)
+    _need_cuda(z, num, gamma, beta)
+    rm = rv = nbt = None
+    if bn is not None:
+        eps = bn.eps
+        if bn.track_running_stats and bn.running_mean is not None:
+            rm, rv, nbt = bn.running_mean, bn.running_var, bn.num_batches_tracked
+        if frozen and rm is None:
+            raise CobevtHipError("sparse_bn_relu: frozen statistics need a BatchNorm1d with running statistics")
+        if not frozen and rm is not None:
+            if bn.momentum is None:
+                raise CobevtHipError("BatchNorm1d(momentum=None): the sparse training kernels keep an exponential running average and need a "
+                                     "numeric momentum")
+            momentum = bn.momentum
+        _need_cuda(rm, rv, nbt)
+    g, b = gamma.detach(), beta.detach()
+    for t, what in ((g, "gamma"), (b, "beta"), (rm, "running_mean"), (rv, "running_var")):
+        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != (c,) or not t.is_contiguous()):
+            raise CobevtHipError("sparse_bn_relu: %s must be contiguous fp32 (%d,), got %s %s" % (what, c, t.dtype, tuple(t.shape)))
+    if nbt is not None and nbt.dtype != torch.int64:
+        raise CobevtHipError("sparse_bn_relu: num_batches_tracked must be int64, got %s" % nbt.dtype)
+    doubles = SPARSE_STAT_DOUBLES
+    partial = _sparse_train_ws(z.device, torch.float64, doubles)
+    stat = torch.empty((4, c), device=z.device, dtype=torch.float32)
+    y = torch.empty_like(z) if want_y else None
+    dims = (ctypes.c_long * 4)(cap, c, 1 if frozen else 0, doubles)
+    with _timed("sparse_bn_relu|C%d" % c, lambda: (4.0 * cap * c, 4.0 * cap * c * (3 if want_y else 1))):
+        _L.call("cobevt_sparse_bn_relu", _p(z), _p(num), _p(g), _p(b), _p(rm), _p(rv), _p(None if frozen else nbt), _p(stat), _p(partial), _p(y), dims,
+                ctypes.c_float(eps), ctypes.c_float(momentum), _stream(), variant="")
+    if not frozen and rm is not None:
+        for t in (rm, rv, nbt):                # written through raw pointers: plans folded from the running statistics must rebuild
+            if t is not None:
+                torch.autograd.graph.increment_version(t)
+    return stat, y
+
+
+def sparse_bn_relu_bwd(dy, y, z, num, gamma, stat, frozen=False):
+    """The backward of sparse_bn_relu (cobevt_sparse_bn_relu_bwd) -> (dz (capacity, C), dgamma (C), dbeta (C)); dy at and past num[0]
+    is never read, dz there is 0.  frozen: the statistics were constants (no / n terms)."""
+    _sparse_rows_f32(z, None, None, "sparse_bn_relu_bwd: z")
+    cap, c = (int(v) for v in z.shape)
+    _sparse_rows_f32(dy, cap, c, "sparse_bn_relu_bwd: dy")
+    _sparse_rows_f32(y, cap, c, "sparse_bn_relu_bwd: y")
+    _need_cuda(dy, y, z, num, gamma, stat)
+    doubles = SPARSE_STAT_DOUBLES
+    partial = _sparse_train_ws(z.device, torch.float64, doubles)
+    dev = z.device
+    dz = torch.empty_like(z)
+    dgb = torch.empty((2, c), device=dev, dtype=torch.float32)
+    coef = torch.empty((3, c), device=dev, dtype=torch.float32)
+    dims = (ctypes.c_long * 4)(cap, c, 1 if frozen else 0, doubles)
+    with _timed("sparse_bn_relu_bwd|C%d" % c, lambda: (10.0 * cap * c, 4.0 * cap * c * 7)):
+        _L.call("cobevt_sparse_bn_relu_bwd", _p(dy), _p(y), _p(z), _p(num), _p(gamma.detach()), _p(stat), _p(partial), _p(dgb[0]), _p(dgb[1]), _p(coef),
+                _p(dz), dims, _stream(), variant="")
+    return dz, dgb[0], dgb[1]
+
+
+def sparse_conv_dgrad(dz, x, level, wgt_t, cin, kernel, stride, padding, subm):
+    """The input gradient of sparse_conv_raw (cobevt_sparse_conv_dgrad): dz (level.capacity, Cout) by the OUTPUT level's rows, x the
+    input level (its indices / num; features not needed), wgt_t the transposed table -> dx (x.capacity, cin), output-stationary over
+    the input rows: a row without a contributing output gets exactly 0, rows at and past x.num[0] too."""
+    k, s, p = _sparse_geometry(kernel, stride, padding, subm, "sparse_conv_dgrad")
+    cout = int(wgt_t.shape[2])
+    _sparse_rows_f32(dz, level.capacity, cout, "sparse_conv_dgrad: dz")
+    if x.row_map is not None:
+        raise CobevtHipError("sparse_conv_dgrad: no gradient is offered through a row_map (the input level of the backbone)")
+    _need_cuda(dz, level.workspace, level.num, x.indices, x.num, wgt_t)
+    dx = torch.empty((x.capacity, cin), device=dz.device, dtype=torch.float32)
+    dims = (ctypes.c_long * 17)(x.batch_size, *(x.spatial_shape + (x.capacity, level.capacity, cin, cout) + k + s + p))
+    taps = k[0] * k[1] * k[2]
+    fam = "sparse_conv_dgrad|k%d%d%d s%d%d%d %d->%d %dx%dx%d" % (k + s + (cin, cout) + level.spatial_shape)
+    with _timed(fam, lambda: (2.0 * x.capacity * taps * cin * cout, 4.0 * (x.capacity * taps * cout + wgt_t.numel() + x.capacity * cin))):
+        _L.call("cobevt_sparse_conv_dgrad", _p(dz), _p(level.workspace), _p(level.num), _p(x.indices), _p(x.num), _p(wgt_t), _p(dx), dims, _stream(),
+                variant="")
+    return dx
+
+
+def sparse_conv_wgrad(x, level, dz, cin, kernel, stride, padding, subm):
+    """The weight gradient of sparse_conv_raw (cobevt_sparse_conv_wgrad, two launches): x the input SparseConvTensor with fp32 features
+    (row_map honoured), dz (level.capacity, Cout) -> dW (Cout, kz, ky, kx, cin) fp32, the module's layout.  No floating-point atomics:
+    SPARSE_ROW_CHUNKS row chunks sized from level.num[0] on the device, added in chunk order in fp64."""
+    k, s, p = _sparse_geometry(kernel, stride, padding, subm, "sparse_conv_wgrad")
+    f = _sparse_rows_f32(x.features, None if x.row_map is not None else x.capacity, None, "sparse_conv_wgrad: x.features")
+    cin_pad, cout = int(f.shape[1]), int(dz.shape[1]) if dz is not None and dz.dim() == 2 else -1
+    _sparse_rows_f32(dz, level.capacity, None, "sparse_conv_wgrad: dz")
+    if (cin_pad, cout) not in SPARSE_TRAIN_PAIRS or not 1 <= cin <= cin_pad or (cin_pad > 8 and cin != cin_pad):
+        raise CobevtHipError("sparse_conv_wgrad: %d (row %d) -> %d channels; supported are <= 8 -> 16 and %s"
+                             % (cin, cin_pad, cout, ", ".join("%d -> %d" % q for q in SparseConvPlan.PAIRS)))
+    _need_cuda(f, x.workspace, x.num, x.row_map, level.indices, level.num, dz)
+    taps = k[0] * k[1] * k[2]
+    floats = sparse_train_scratch(cin_pad, cout, taps)[0]
+    partial = _sparse_train_ws(f.device, torch.float32, floats)
+    dw = torch.empty((cout,) + k + (cin,), device=f.device, dtype=torch.float32)
+    cap = level.capacity
+    dims = (ctypes.c_long * 19)(x.batch_size, *(x.spatial_shape + (f.shape[0], cap, cin, cin_pad, cout) + k + s + p + (floats,)))
+    fam = "sparse_conv_wgrad|k%d%d%d s%d%d%d %d->%d %dx%dx%d" % (k + s + (cin_pad, cout) + level.spatial_shape)
+    with _timed(fam, lambda: (2.0 * cap * taps * cin_pad * cout, 4.0 * (cap * taps * (cin_pad + cout) + 2 * floats))):
+        _L.call("cobevt_sparse_conv_wgrad", _p(f), _p(x.workspace), _p(x.num), _p(x.row_map), _p(level.indices), _p(level.num), _p(dz), _p(partial),
+                _p(dw), dims, _stream(), variant="")
+    return dw
+
+
+def sparse_dense_bwd(dcanvas, x, channels):
+    """The adjoint of sparse_dense_nhwc (cobevt_sparse_dense_bwd, one gather launch): dcanvas (N, H, W, C D) contiguous fp32 ->
+    (x.capacity, C): every live row's cell, 0 at and past x.num[0]"""
+    n, (d, h, w), c = x.batch_size, x.spatial_shape, int(channels)
+    if dcanvas.dtype != torch.float32 or tuple(dcanvas.shape) != (n, h, w, c * d) or not dcanvas.is_contiguous():
+        raise CobevtHipError("sparse_dense_bwd: the gradient must be contiguous fp32 %s, got %s %s" % ((n, h, w, c * d), dcanvas.dtype, tuple(dcanvas.shape)))
+    _need_cuda(dcanvas, x.indices, x.num)
+    out = torch.empty((x.capacity, c), device=dcanvas.device, dtype=torch.float32)
+    dims = (ctypes.c_long * 6)(n, d, h, w, x.capacity, c)
+    with _timed("sparse_dense_bwd|%dx%dx%d C%d" % (d, h, w, c), lambda: (0.0, 8.0 * out.numel())):
+        _L.call("cobevt_sparse_dense_bwd", _p(dcanvas), _p(x.indices), _p(x.num), _p(out), dims, _stream(), variant="")
+    return out
 
 
 PIL_PRECISION_BITS = 22    # Pillow's 8-bit resample: 32 - 8 - 2 bits of coefficient

@@ -1128,6 +1128,57 @@ int cobevt_sparse_conv(const void* in, const int* in_workspace, const int* in_nu
                        const int* out_num, const void* weight, const float* bias, void* out, const long* dims, hipStream_t stream);
 int cobevt_sparse_dense(const void* features, const int* indices, const int* num, void* out, const long* dims, hipStream_t stream);
 
+/*
+ * Training of the sparse backbone (csrc/sparse_conv.hip; fp32 rows only, the exact fp32 MFMA).  A layer's training forward is
+ * z = conv(x) (cobevt_sparse_conv_raw), the BatchNorm statistics of z over the live rows and y = relu(z scale + shift)
+ * (cobevt_sparse_bn_relu); its backward is cobevt_sparse_bn_relu_bwd (dy -> dz, dgamma, dbeta), cobevt_sparse_conv_dgrad (dz -> dx) and
+ * cobevt_sparse_conv_wgrad (dz, x -> dW).  As above: every row count is the level's device word num[0], no host read, no allocation, no
+ * floating-point atomics, bitwise reproducible, arguments validated before any launch (null: code 1; shape, alignment, unsupported pair,
+ * scratch too small: code 2).  Reductions over rows are cut into a fixed number of row chunks (64) whose length,
+ * ceil(ceil(num[0] / 64) / 32) * 32 rows, comes from num[0] on the device: the summation order does not depend on a capacity.
+ * Channel pairs (input row -> Cout): 8 -> 16, 16 -> 16 | 32, 32 -> 32 | 64, 64 -> 64 | 128; kernel / stride / pad as cobevt_sparse_conv.
+ *
+ * cobevt_sparse_train_scratch: dims = [input row in channels, Cout, taps (27 | 3)] -> sizes[0] = floats of cobevt_sparse_conv_wgrad's
+ *   `partial` (64 x taps x Cout padded to 32 x input row), sizes[1] = doubles of the `partial` of the two BatchNorm entries (64 x 2 x 128).
+ * cobevt_sparse_conv_raw: cobevt_sparse_conv's arguments without bias, weight [taps][Cout padded to 32][input row] fp32 UNfolded, ->
+ *   out (output capacity, Cout) = the plain sums; rows in [out_num[0], capacity) are written as 0.
+ *   dims = [N, D, H, W of the input, input feature rows, output capacity, input row in channels, Cout, kernel, stride, pad].  One launch.
+ * cobevt_sparse_bn_relu: z (capacity, C), C = 16 | 32 | 64 | 128 -> stat (4, C) fp32 = [mean, rstd, scale = gamma rstd,
+ *   shift = beta - mean scale] over the n = num[0] live rows (biased variance; fp64 sums about the pivot z[0], per chunk, added in
+ *   chunk order), and y (capacity, C) = relu(z scale + shift), 0 at and past num[0]; y null: the statistics alone.  mode 0: batch
+ *   statistics; with running_mean, running_var (fp32) and num_batches_tracked (int64) given and n > 1 they are updated in place
+ *   (momentum, the variance with n / (n - 1); + 1); n = 0: mean 0, variance 0, n = 1: variance 0, neither updates anything.  mode 1: the
+ *   running statistics as they are.  dims = [capacity, C, mode, doubles of partial].  Two launches + one for y (mode 1: one + one).
+ * cobevt_sparse_bn_relu_bwd: with g = dy [y > 0], xhat = (z - mean) rstd: dgamma = sum g xhat, dbeta = sum g (fp64, chunk order),
+ *   coef (3, C) = [k = gamma rstd, A = k rstd dgamma / n, B = k dbeta / n] (mode 1 or n = 0: A = B = 0), dz = k g - (B + (z - mean) A),
+ *   0 at and past num[0], where dy is never read.  dims as cobevt_sparse_bn_relu.  Three launches.
+ * cobevt_sparse_conv_dgrad: dz (output capacity, Cout) by the OUTPUT level's rows (out_workspace, out_num) -> dx (input capacity, Cin) by
+ *   the input level's rows (in_indices, in_num): dx[i] = sum over taps k of W[k]^T dz[row((i + pad - k) / stride)] where the division
+ *   is exact, the cell lies in the output shape and its row is live; 0 without any, and 0 at and past in_num[0].
+ *   weight_t [taps][Cin padded to 32][Cout] fp32.  dims = [N, D, H, W of the INPUT level, input capacity, output capacity, Cin, Cout,
+ *   kernel, stride, pad], Cin = 16 | 32 | 64.  One launch (cobevt_sparse_conv's kernel with the transposed neighbour rule).
+ * cobevt_sparse_conv_wgrad: x as cobevt_sparse_conv_raw's `in` (row_map honoured), dz (output capacity, Cout) ->
+ *   dw (Cout, kz, ky, kx, Cin) fp32, real channels only.  One wave per (row chunk, tap) with the rows as the MFMA's k dimension writes
+ *   partial [chunk][tap][Cout padded to 32][input row]; a second launch adds the chunks in order in fp64.
+ *   dims = [N, D, H, W of the input, input feature rows, output capacity, Cin, input row in channels, Cout, kernel, stride, pad, floats
+ *   of partial].
+ * cobevt_sparse_dense_bwd: dcanvas (N, H, W, C D) fp32 -> dfeatures (capacity, C): the cell of every live row, 0 at and past num[0].
+ *   dims = [N, D, H, W, capacity, C].  One launch.
+ */
+int cobevt_sparse_train_scratch(const long* dims, long* sizes);
+int cobevt_sparse_conv_raw(const float* in, const int* in_workspace, const int* in_num, const int* row_map, const int* out_indices,
+                           const int* out_num, const float* weight, float* out, const long* dims, hipStream_t stream);
+int cobevt_sparse_bn_relu(const float* z, const int* num, const float* gamma, const float* beta, float* running_mean, float* running_var,
+                          long* num_batches_tracked, float* stat, double* partial, float* y, const long* dims, float eps, float momentum,
+                          hipStream_t stream);
+int cobevt_sparse_bn_relu_bwd(const float* dy, const float* y, const float* z, const int* num, const float* gamma, const float* stat,
+                              double* partial, float* dgamma, float* dbeta, float* coef, float* dz, const long* dims, hipStream_t stream);
+int cobevt_sparse_conv_dgrad(const float* dz, const int* out_workspace, const int* out_num, const int* in_indices, const int* in_num,
+                             const float* weight_t, float* dx, const long* dims, hipStream_t stream);
+int cobevt_sparse_conv_wgrad(const float* x, const int* in_workspace, const int* in_num, const int* row_map, const int* out_indices,
+                             const int* out_num, const float* dz, float* partial, float* dw, const long* dims, hipStream_t stream);
+int cobevt_sparse_dense_bwd(const float* dcanvas, const int* indices, const int* num, float* dfeatures, const long* dims, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

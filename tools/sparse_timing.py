@@ -90,12 +90,119 @@ def skipped_share(x_in, x_out, conv, tile):
     return 1.0 - float(present.float().mean())
 
 
+def train_main(args):
+    """--train: host.training.mean_vfe -> voxel_backbone8x -> height_compression on the same scene with a sum-of-products loss, forward +
+    backward, fp32 rows, capacities fitted to the scene (1.25 x the live rows): eager and as ONE captured graph (side stream, two warm-up
+    steps, as host/train_graph.py does), median of --steps with HIP events; the fp32 inference forward of the same module measured in
+    the same run with the same capacities; the per-launch split of an eager step (ops.LaunchProfile, by family and level shape).  One JSON
+    line, APPENDED to the output file."""
+    from cobevt_amd import autograd as ag
+    from cobevt_amd import host, ops
+    from cobevt_amd.host import training
+    from cobevt_amd.synth import fill_module_
+    if not torch.cuda.is_available():
+        raise SystemExit("sparse_timing: needs a GPU (a timing taken anywhere else says nothing)")
+    dev = torch.device("cuda")
+    out_path = args.out if args.out != os.path.join(ROOT, "profiles", "sparse_backbone_timing.json") else \
+        os.path.join(ROOT, "profiles", "sparse_backbone_train_timing.json")
+    data = scene(args.voxels, dev)
+    vfe, to_bev = host.MeanVFE({}, CHANNELS), host.HeightCompression({"feature_num": 256})
+    backbone = fill_module_(host.VoxelBackBone8x({}, CHANNELS, list(GRID)), 0).to(dev)
+
+    def timed(fn):
+        ts = []
+        for _ in range(args.steps):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            ts.append(e0.elapsed_time(e1))
+        return round(median(ts), 4), round(min(ts), 4), round(max(ts), 4)
+
+    def infer():
+        with torch.no_grad(), host.compute_dtype("fp32"):
+            return to_bev(backbone(vfe(dict(data))))
+
+    for mod in (vfe, backbone, to_bev):
+        mod.eval()
+    out = infer()
+    torch.cuda.synchronize()
+    levels = [out["multi_scale_3d_features"][k] for k in ("x_conv1", "x_conv2", "x_conv3", "x_conv4")] + [out["encoded_spconv_tensor"]]
+    rows = [int(t.num[0]) for t in levels]
+    backbone.level_capacities = [max(int(1.25 * r), 128) for r in rows]
+    for _ in range(3):
+        infer()
+    torch.cuda.synchronize()
+    infer_eager = timed(infer)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        infer()
+    graph.replay()
+    torch.cuda.synchronize()
+    infer_graph = timed(graph.replay)
+    del graph
+    for mod in (vfe, backbone, to_bev):
+        mod.train()
+    d, h, w = backbone.level_shapes()[-1]
+    weights = torch.rand((1, 128 * d, h, w), device=dev, generator=torch.Generator(device=dev).manual_seed(1)) - 0.5
+
+    def step():
+        sf = training.height_compression(to_bev, training.voxel_backbone8x(backbone, training.mean_vfe(vfe, dict(data))))["spatial_features"]
+        (sf * weights).sum().backward()
+
+    stream = torch.cuda.Stream()
+    stream.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(stream):
+        for _ in range(3):
+            step()
+        torch.cuda.synchronize()
+        eager = timed(step)
+        per = {}
+        for _ in range(args.steps):
+            with ops.LaunchProfile() as prof:
+                step()
+                fams = prof.summary(by_shape=True)
+            for fam, v in fams.items():
+                per.setdefault(fam, []).append((v["ms"], v["calls"]))
+        for p in backbone.parameters():
+            p.grad = None
+        graph = torch.cuda.CUDAGraph()
+        ag.begin_capture_zero_pool()
+        try:
+            with torch.cuda.graph(graph, stream=stream):
+                step()
+        finally:
+            ag.end_capture_zero_pool()
+        graph.replay()
+        torch.cuda.synchronize()
+        replay = timed(graph.replay)
+    torch.cuda.current_stream().wait_stream(stream)
+    split = {fam: {"calls": v[0][1], "ms": round(median([m for m, _ in v]), 4)} for fam, v in per.items()}
+    line = {"what": "training.mean_vfe -> voxel_backbone8x -> height_compression, forward + backward, fp32 rows, sparse shape (41, 1600, 1408), "
+                    "one agent, synthetic clustered scene, capacities 1.25 x the live rows; ms: median of --steps (min, max); "
+                    "ms_per_family: all calls of a launch family and level shape in one eager step",
+            "device": torch.cuda.get_device_name(0), "steps": args.steps, "voxels": int(data["voxel_coords"].shape[0]), "rows_per_level": rows,
+            "capacities": backbone.level_capacities, "inference_fp32_ms": {"eager": infer_eager, "graph_replay": infer_graph},
+            "train_step_ms": {"eager": eager, "graph_replay": replay},
+            "train_graph_over_inference_graph": round(replay[0] / infer_graph[0], 2), "ms_per_family": split}
+    text = json.dumps(line)
+    print(text, flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "a") as f:
+        f.write(text + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--voxels", type=int, default=40000)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "sparse_backbone_timing.json"))
+    ap.add_argument("--train", action="store_true", help="time one training step (forward + backward) instead; appends to "
+                                                         "profiles/sparse_backbone_train_timing.json unless --out is given")
     args = ap.parse_args()
+    if args.train:
+        return train_main(args)
     from cobevt_amd import host, ops
     from cobevt_amd.synth import fill_module_
     if not torch.cuda.is_available():
