@@ -857,17 +857,19 @@ class Conv2dFn(torch.autograd.Function):
         return dx, dw, db, None, None
 
 
-def conv2d(x, conv):
-    """x through the nn.Conv2d container `conv` (square kernel / stride / padding, groups 1, dilation 1)"""
+def conv2d(x, conv, pad=None):
+    """x through the nn.Conv2d container `conv` (square kernel / stride / padding, groups 1, dilation 1); pad=: the padding to use
+    instead of the container's (a pad-0 conv behind a ZeroPad2d(1) is a pad-1 conv)"""
     if conv.groups != 1 or conv.dilation != (1, 1) or conv.kernel_size[0] != conv.kernel_size[1] or conv.stride[0] != conv.stride[1] \
             or conv.padding[0] != conv.padding[1]:
         raise CobevtHipError("training conv2d: square kernel / stride / padding, groups 1, dilation 1 only")
+    pad = conv.padding[0] if pad is None else int(pad)
     if torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.bfloat16:
         # a bf16 autocast region: the convolution computes in bf16 like torch's own conv would, from the fp32 master weights (the
         # parameter receives an fp32 gradient); fp16 regions stay on the fp32 kernels (_amp_fwd)
         with torch.autocast("cuda", enabled=False):
-            return Conv2dFn.apply(x.to(torch.bfloat16), _master(conv.weight), conv.bias, conv.stride[0], conv.padding[0])
-    return Conv2dFn.apply(x, _master(conv.weight), conv.bias, conv.stride[0], conv.padding[0])
+            return Conv2dFn.apply(x.to(torch.bfloat16), _master(conv.weight), conv.bias, conv.stride[0], pad)
+    return Conv2dFn.apply(x, _master(conv.weight), conv.bias, conv.stride[0], pad)
 
 
 # ----------------------------------------------------------------------------------------------
@@ -1701,6 +1703,94 @@ def sparse_dense_nhwc(x):
     if x.row_map is not None:
         raise CobevtHipError("sparse_dense: the tensor needs features in the level's row order")
     return SparseDenseFn.apply(x.features, x)
+
+
+# ----------------------------------------------------------------------------------------------
+# the 2-D LiDAR backbones in train() mode: the transposed convolution of the deblocks (csrc/deconv.hip forward, csrc/igemm.hip input
+# gradient, csrc/train_rows.hip weight gradient) and the per-pixel agent attention (csrc/att_fuse.hip).  Both Functions are fp32 in and
+# out under every compute dtype and under autocast: a half input is widened by an explicit differentiable cast in the wrappers.
+# ----------------------------------------------------------------------------------------------
+USE_DECONV_WGRAD = True       # False: the transposed conv's weight gradient through cobevt_conv_wgrad with the roles swapped (fp32 atomics; A/B runs)
+
+
+class DeconvFn(torch.autograd.Function):
+    """nn.ConvTranspose2d(kernel = stride = s, bias=False) on (N, C, H, W)-shaped fp32 tensors (channels-last memory is used as it is).
+    weight is the fp32 MASTER parameter (Cin, Cout, s, s); `tables` = ops.deconv_train_weights(weight).  Forward: ops.deconv_raw (the
+    inference kernel of the native library on the unfolded weights, no shift, no activation).  Backward: the input gradient - only when
+    x needs one - is the stride-s, s x s, pad-0 convolution of dz with the weight read as (out = Cin, in = Cout, s, s) on the
+    implicit-GEMM kernel; the weight gradient is ops.deconv_wgrad (chunked, fp64 chunk sums, no atomics) and comes back in fp32."""
+
+    @staticmethod
+    @_amp_fwd
+    def forward(ctx, x, weight, tables):
+        _need_cuda(x, weight)
+        if weight.dtype != torch.float32 or x.dtype != torch.float32:
+            raise CobevtHipError("training deconv: fp32 master weight and fp32 x (got %s, %s)" % (weight.dtype, x.dtype))
+        xl = x.permute(0, 2, 3, 1).contiguous()
+        cin, cout, s, _ = (int(d) for d in weight.shape)
+        if xl.shape[3] != cin:
+            raise CobevtHipError("training deconv: %d input channels, the weight takes %d" % (xl.shape[3], cin))
+        fwd, rows = tables
+        z = ops.deconv_raw(xl, fwd, cout, s)
+        ctx.save_for_backward(xl, rows if ctx.needs_input_grad[0] else None)
+        ctx.cfg = (cin, cout, s)
+        return z.permute(0, 3, 1, 2)
+
+    @staticmethod
+    @_amp_bwd
+    def backward(ctx, dz):
+        xl, rows = ctx.saved_tensors
+        cin, cout, s = ctx.cfg
+        n, h, w, _ = xl.shape
+        dzl = _f32c(dz.float().permute(0, 2, 3, 1), "dz")
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            dx = _igemm_rows(dzl, rows, cin, cout, s, s, None, s, 0, h, w).permute(0, 3, 1, 2)
+        if ctx.needs_input_grad[1]:
+            if USE_DECONV_WGRAD:
+                dw = ops.deconv_wgrad(xl, dzl, s)
+            else:
+                # the same tensor as the weight gradient of the convolution dz -> x: (out = Cin, in = Cout, s, s), fp32 atomics
+                dw = _zeros((cin, cout, s, s), dzl.device, torch.float32)
+                dims = _ints([n, s * h, s * w, cout, h, w, cin, s, s, 0, ops.FP32])
+                _call("cobevt_conv_wgrad", _p(dzl), _p(xl), _p(dw), dims, _stream())
+        return dx, dw, None
+
+
+def deconv(x, conv):
+    """x through the nn.ConvTranspose2d container `conv` (square kernel = stride, no padding, no bias, groups 1, dilation 1)"""
+    if not isinstance(conv, torch.nn.ConvTranspose2d) or conv.groups != 1 or conv.dilation != (1, 1) or conv.bias is not None \
+            or conv.kernel_size != conv.stride or conv.kernel_size[0] != conv.kernel_size[1] or conv.padding != (0, 0) \
+            or conv.output_padding != (0, 0):
+        raise CobevtHipError("training deconv: nn.ConvTranspose2d with a square kernel = stride, no padding, no bias, groups 1, dilation 1 only")
+    weight = _master(conv.weight)
+    # lowered HERE, from the Parameter object itself (the cache is per object; what a Function's forward receives need not be that object)
+    tables = ops.deconv_train_weights(weight)
+    return DeconvFn.apply(x.float(), weight, tables)
+
+
+class AttFuseFn(torch.autograd.Function):
+    """AttFusion on contiguous (N, H, W, C) fp32 agent maps -> (B, H, W, C): ops.att_fuse forward; the backward is ONE
+    cobevt_att_fuse_bwd_nhwc launch that recomputes the scores from x (nothing else is saved).  No gradient for record_len."""
+
+    @staticmethod
+    @_amp_fwd
+    def forward(ctx, x, record_len):
+        x = _f32c(x, "att_fuse")
+        out = ops.att_fuse(x, record_len)
+        ctx.save_for_backward(x, record_len)
+        return out
+
+    @staticmethod
+    @_amp_bwd
+    def backward(ctx, dout):
+        x, record_len = ctx.saved_tensors
+        return ops.att_fuse_bwd(x, record_len, _f32c(dout.float(), "d out")), None
+
+
+def att_fuse(x, record_len):
+    """(N, H, W, C) agent maps, record_len int32 (B,) on the device -> (B, H, W, C) fp32, differentiable in x"""
+    return AttFuseFn.apply(x.float(), record_len)
 
 
 def _env_flags():

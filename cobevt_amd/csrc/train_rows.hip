@@ -712,3 +712,142 @@ extern "C" int cobevt_conv_wgrad_blocked(const void* xb, const void* db, float* 
     }
     return cobevt::launch_status();
 }
+
+// ---------------------------------------------------------------------------------------------- transposed convolution, kernel = stride
+// Weight gradient of z = ConvTranspose2d(kernel = stride = s, no bias)(x): dW[ci][co][dy][dx] = sum over the INPUT pixels m = (n, y, x) of
+// x[m][ci] dz[n][s y + dy][s x + dx][co].  The taps do not overlap, so every tap is one GEMM over the input pixels, which are the k
+// dimension of v_mfma_f32_32x32x2_f32: lanes 0 .. 31 supply pixel 2 j, lanes 32 .. 63 pixel 2 j + 1, each lane one channel - both
+// operands are read as they lie (128 contiguous bytes per half-wave), nothing is staged or transposed.  One wave per workgroup:
+// (pixel chunk, tap x 32-ci tile x group of CB 32-co tiles); its accumulators go to partial[chunk][tap][Cin padded to 32][Cout] with
+// plain stores, a second launch adds the chunks in order in fp64 and rounds once.  No atomics: bit-reproducible.
+struct DeconvWgradArgs {
+    const float* x;        // (N, H, W, Cin)
+    const float* dz;       // (N, sH, sW, Cout)
+    float* partial;
+    int M, H, W, Cin, Cout, s, L, cin_pad, co_groups, ci_tiles;
+};
+
+// the chunk count as a pure function of the shape (untuned): about 2048 one-wave workgroups (256 CUs x 4 SIMDs x 2), chunks of at least
+// 64 pixels, at most 64 MB of partial sums; the chunk length is even, so a pixel pair never straddles two chunks
+static int deconv_wgrad_plan(const int* dims, DeconvWgradArgs& a, int& cb) {
+    if (!dims) return -COBEVT_ERR_ARG;
+    const long N = dims[0], H = dims[1], W = dims[2], cin = dims[3], cout = dims[4], s = dims[5];
+    if (N < 1 || H < 1 || W < 1 || s < 1 || s > 8 || cin < 4 || cin % 4 || cout < 32 || cout % 32) return -COBEVT_ERR_SHAPE;
+    if (cin > 65536 || cout > 65536) return -COBEVT_ERR_SHAPE;
+    if (N * H * W * s * s >= 0x7fffffffL) return -COBEVT_ERR_SHAPE;
+    const long M = N * H * W, taps = s * s, cin_pad = (cin + 31) / 32 * 32, co_tiles = cout / 32;
+    cb = co_tiles % 4 == 0 ? 4 : (co_tiles % 2 == 0 ? 2 : 1);
+    const long per = taps * (cin_pad / 32) * (co_tiles / cb);
+    const long chunk_bytes = taps * cin_pad * cout * 4;
+    if (per > 0x7fffffffL || chunk_bytes > (64L << 20)) return -COBEVT_ERR_SHAPE;
+    long chunks = (2048 + per - 1) / per;
+    if (chunks > (M + 63) / 64) chunks = (M + 63) / 64;
+    if (chunks > (64L << 20) / chunk_bytes) chunks = (64L << 20) / chunk_bytes;
+    if (chunks > 65535) chunks = 65535;
+    if (chunks < 1) chunks = 1;
+    long L = (M + chunks - 1) / chunks;
+    L += L & 1;
+    chunks = (M + L - 1) / L;                      // every chunk owns at least one pixel
+    a.M = (int)M; a.H = (int)H; a.W = (int)W; a.Cin = (int)cin; a.Cout = (int)cout; a.s = (int)s; a.L = (int)L; a.cin_pad = (int)cin_pad;
+    a.co_groups = (int)(co_tiles / cb); a.ci_tiles = (int)(cin_pad / 32);
+    return (int)chunks;
+}
+
+namespace cobevt {
+namespace {
+
+template <int CB>
+__global__ __launch_bounds__(64) void deconv_wgrad_kernel(DeconvWgradArgs a) {
+    constexpr int PU = 4;                          // pixel pairs per batch of loads
+    const int lane = threadIdx.x, half = lane >> 5, l32 = lane & 31;
+    const int chunk = blockIdx.x;
+    int y = blockIdx.y;
+    const int cg = y % a.co_groups; y /= a.co_groups;
+    const int ct = y % a.ci_tiles;
+    const int tap = y / a.ci_tiles;
+    const int dy = tap / a.s, dx = tap - dy * a.s;
+    const long lo = (long)chunk * a.L, hi = min((long)a.M, lo + a.L);
+    const int ci = ct * 32 + l32;
+    const bool ci_ok = ci < a.Cin;
+    const float* xp = a.x + min(ci, a.Cin - 1);
+    const float* zp = a.dz + (size_t)cg * CB * 32 + l32;
+    const size_t sW = (size_t)a.s * a.W;
+    f32x16 acc[CB];
+#pragma unroll
+    for (int c = 0; c < CB; ++c)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[c][r] = 0.f;
+    for (long m0 = lo; m0 < hi; m0 += 2 * PU) {
+        float av[PU], bv[PU][CB];
+#pragma unroll
+        for (int u = 0; u < PU; ++u) {
+            const long m = m0 + 2 * u + half;
+            const bool ok = m < hi;
+            const int mc = (int)(ok ? m : hi - 1);       // unconditional loads from clamped addresses + select
+            const int row = mc / a.W, px = mc - row * a.W;                          // row = n H + y
+            const size_t zpix = ((size_t)row * a.s + dy) * sW + (size_t)px * a.s + dx;  // (n sH + s y + dy) sW + s x + dx
+            const float xv = xp[(size_t)mc * a.Cin];
+            av[u] = (ok && ci_ok) ? xv : 0.f;
+#pragma unroll
+            for (int c = 0; c < CB; ++c) {
+                const float zv = zp[zpix * a.Cout + c * 32];
+                bv[u][c] = ok ? zv : 0.f;
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < PU; ++u)
+#pragma unroll
+            for (int c = 0; c < CB; ++c) acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u], bv[u][c], acc[c], 0, 0, 0);
+    }
+    // D[ci rows][co columns] -> partial[chunk][tap][cin_pad][Cout]
+    float* p = a.partial + (((size_t)chunk * a.s * a.s + tap) * a.cin_pad + ct * 32) * a.Cout + (size_t)cg * CB * 32 + l32;
+#pragma unroll
+    for (int c = 0; c < CB; ++c)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) p[(size_t)acc_row(r, lane) * a.Cout + c * 32] = acc[c][r];
+}
+
+// the chunks in order, in fp64, rounded once -> dW (Cin, Cout, s, s), the ConvTranspose2d layout
+__global__ __launch_bounds__(256) void deconv_wgrad_reduce_kernel(const float* __restrict__ partial, float* __restrict__ dw, int chunks, int taps, int cin,
+                                                                  int cin_pad, int cout) {
+    const long e = (long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (long)cin * cout * taps) return;
+    const int tap = (int)(e % taps);
+    const long r = e / taps;
+    const int co = (int)(r % cout), ci = (int)(r / cout);
+    const size_t step = (size_t)taps * cin_pad * cout;
+    const float* q = partial + ((size_t)tap * cin_pad + ci) * cout + co;
+    double s = 0.0;
+    for (int c = 0; c < chunks; ++c) s += (double)q[c * step];
+    dw[e] = (float)s;
+}
+
+}  // namespace
+}  // namespace cobevt
+
+extern "C" int cobevt_deconv_wgrad_chunks(const int* dims) {
+    DeconvWgradArgs a;
+    int cb;
+    return deconv_wgrad_plan(dims, a, cb);
+}
+
+extern "C" int cobevt_deconv_wgrad(const float* x, const float* dz, float* partial, float* dw, const int* dims, hipStream_t stream) {
+    // dims: [N, H, W, Cin, Cout, s, chunks (what cobevt_deconv_wgrad_chunks returns: `partial` holds chunks x s s x Cin padded to 32 x Cout floats)]
+    if (!x || !dz || !partial || !dw || !dims) return COBEVT_ERR_ARG;
+    DeconvWgradArgs a;
+    int cb;
+    const int chunks = deconv_wgrad_plan(dims, a, cb);
+    if (chunks < 0) return -chunks;
+    if (dims[6] != chunks) return COBEVT_ERR_SHAPE;
+    if (((uintptr_t)x | (uintptr_t)dz | (uintptr_t)partial | (uintptr_t)dw) & 3) return COBEVT_ERR_SHAPE;
+    a.x = x; a.dz = dz; a.partial = partial;
+    const int taps = a.s * a.s;
+    const dim3 grid((unsigned)chunks, (unsigned)(taps * a.ci_tiles * a.co_groups));
+    if (cb == 4) hipLaunchKernelGGL(cobevt::deconv_wgrad_kernel<4>, grid, dim3(64), 0, stream, a);
+    else if (cb == 2) hipLaunchKernelGGL(cobevt::deconv_wgrad_kernel<2>, grid, dim3(64), 0, stream, a);
+    else hipLaunchKernelGGL(cobevt::deconv_wgrad_kernel<1>, grid, dim3(64), 0, stream, a);
+    const long total = (long)a.Cin * a.Cout * taps;
+    hipLaunchKernelGGL(cobevt::deconv_wgrad_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, (const float*)partial, dw, chunks,
+                       taps, a.Cin, a.cin_pad, a.Cout);
+    return cobevt::launch_status();
+}

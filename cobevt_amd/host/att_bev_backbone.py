@@ -13,10 +13,12 @@ from the reference (num_bev_features without deblocks; num_upsample_filter[-1] =
 forward(data_dict) is the reference's contract: reads 'spatial_features' (N, C, H, W) and 'record_len' (B,), writes and returns
 'spatial_features_2d' (B, num_bev_features, H', W') fp32 (the per-level 'spatial_features_%dx' entries are not produced).
 forward_nhwc(x, record_len) takes NHWC in the compute dtype and an int32 device record_len; models use it.  No host synchronisation.
-Inference only: a train()-mode forward raises."""
+In train() mode on ROCm tensors both forwards take host/training.att_bev_backbone (fp32, differentiable: the agent attention has its
+own backward kernel); on CPU tensors a train()-mode forward raises."""
 import torch.nn as nn
 
 from . import runtime as rt
+from . import training
 from .auto_encoder import AutoEncoder
 from .base_bev_backbone import BaseBEVBackbone
 from .self_attn import AttFusion, record_len_i32
@@ -44,6 +46,9 @@ class AttBEVBackbone(BaseBEVBackbone):
 
     def forward_nhwc(self, x, record_len):
         """(N, H, W, C) in the compute dtype, record_len int32 (B,) on the device -> (B, H', W', num_bev_features)"""
+        if self._trains(x):
+            return training.att_bev_backbone(self, x.permute(0, 3, 1, 2), record_len).permute(0, 2, 3, 1)
+
         def fuse(i, x):
             if self.compress and i < len(self.compression_modules):
                 x = self.compression_modules[i].forward_nhwc(x)
@@ -55,6 +60,9 @@ class AttBEVBackbone(BaseBEVBackbone):
 
     def forward(self, data_dict):
         x = data_dict["spatial_features"]
+        if self._trains(x):
+            data_dict["spatial_features_2d"] = training.att_bev_backbone(self, x, record_len_i32(data_dict["record_len"], x.device)).float()
+            return data_dict
         self._require_inference(x)
         y = self.forward_nhwc(rt.to_nhwc(x), record_len_i32(data_dict["record_len"], x.device))
         data_dict["spatial_features_2d"] = rt.nchw_view(y).float()

@@ -6,13 +6,15 @@ first to last and the decoders LAST TO FIRST, as the reference does.  The contai
 
 Convs run through ops.conv2d, the transposed convs through ops.deconv_into (cobevt_deconv_nhwc, c_off = 0).  That kernel writes 32
 output channels per tile, so every decoder width feature_num / 2^i has to be a multiple of 32 (and its input a multiple of 8):
-AutoEncoder(64, 1) and (128, 2) build, (32, 2) (a transposed conv 8 -> 16) raises CobevtHipError at construction.  Inference only."""
+AutoEncoder(64, 1) and (128, 2) build, (32, 2) (a transposed conv 8 -> 16) raises CobevtHipError at construction.  In train() mode on
+ROCm tensors the forwards take host/training.auto_encoder (fp32, differentiable); on CPU tensors a train()-mode forward raises."""
 import torch
 import torch.nn as nn
 
 from .. import ops
 from ..lib import CobevtHipError
 from . import runtime as rt
+from . import training
 from .base_bev_backbone import _bn
 from .runtime import HipModule
 
@@ -56,6 +58,8 @@ class AutoEncoder(HipModule):
         return h << len(self.decoder), w << len(self.decoder)
 
     def forward_nhwc(self, x):
+        if self.training and torch.is_tensor(x) and x.is_cuda:
+            return training.auto_encoder(self, x.permute(0, 3, 1, 2)).permute(0, 2, 3, 1)
         self._require_inference(x)
         for i, enc in enumerate(self.encoder):
             x = ops.conv2d(x, self._conv_plan("e%d.1" % i, enc[1], enc[2]))        # pad 1 = the ZeroPad2d(1) in front of pad 0
@@ -69,5 +73,7 @@ class AutoEncoder(HipModule):
         return x
 
     def forward(self, x):
+        if self.training and torch.is_tensor(x) and x.is_cuda:
+            return training.auto_encoder(self, x)
         self._require_inference(x)
         return rt.like_input(rt.nchw_view(self.forward_nhwc(rt.to_nhwc(x))), x)

@@ -16,14 +16,18 @@ one H x W raise CobevtHipError before anything is launched.
 forward(data_dict) is the reference's contract: reads data_dict['spatial_features'] (N, C, H, W), writes and returns
 data_dict['spatial_features_2d'] (N, sum(num_upsample_filter), H', W') fp32 (the reference's per-level 'spatial_features_%dx' entries
 are not produced).  forward_nhwc(x) takes and returns NHWC tensors in the compute dtype; models use it.  No host synchronisation:
-the forward can be captured in a HIP graph.  Inference only: the backward of the transposed convolution is not implemented, so a
-train()-mode forward raises."""
+the forward can be captured in a HIP graph.
+
+In train() mode on ROCm tensors both forwards take the differentiable graph of host/training.base_bev_backbone: every conv through
+autograd.conv2d, every BatchNorm2d with batch statistics (or, with its own .training flag off, its frozen running statistics), every
+transposed conv through autograd.deconv; the outputs are fp32.  On CPU tensors a train()-mode forward raises."""
 import torch
 import torch.nn as nn
 
 from .. import ops
 from ..lib import CobevtHipError
 from . import runtime as rt
+from . import training
 from .runtime import HipModule
 
 
@@ -121,8 +125,22 @@ class BaseBEVBackbone(HipModule):
                 out.append(((h - r) // r + 1, (w - r) // r + 1))
         return out
 
+    def _concat_size(self, h, w):
+        """the one H x W the levels' outputs share for an h x w input; raises when they do not (before anything is launched)"""
+        ups = self._up_sizes(self._level_sizes(h, w))
+        if any(hw != ups[0] for hw in ups) or min(ups[0]) < 1:
+            raise CobevtHipError("%s: the levels' outputs must share one H x W to be concatenated; a %d x %d input gives %s"
+                                 % (type(self).__name__, h, w, ", ".join("%d x %d" % hw for hw in ups)))
+        return ups[0]
+
+    def _trains(self, x):
+        """a train()-mode forward on a ROCm tensor takes the differentiable graph; anything else the inference path (which refuses train())"""
+        return self.training and torch.is_tensor(x) and x.is_cuda
+
     def forward_nhwc(self, x):
-        """(N, H, W, C) in the compute dtype -> (N, H', W', num_bev_features) in the compute dtype"""
+        """(N, H, W, C) in the compute dtype -> (N, H', W', num_bev_features) in the compute dtype (train(): fp32, differentiable)"""
+        if self._trains(x):
+            return training.base_bev_backbone(self, x.permute(0, 3, 1, 2)).permute(0, 2, 3, 1)
         return self._forward_levels(x, x.shape[0])
 
     def _forward_levels(self, x, n_out, after_block=None):
@@ -133,14 +151,11 @@ class BaseBEVBackbone(HipModule):
         levels = len(self.blocks)
         if levels == 0:
             return x
-        ups = self._up_sizes(self._level_sizes(h, w))
-        if any(hw != ups[0] for hw in ups) or min(ups[0]) < 1:
-            raise CobevtHipError("%s: the levels' outputs must share one H x W to be concatenated; a %d x %d input gives %s"
-                                 % (type(self).__name__, h, w, ", ".join("%d x %d" % hw for hw in ups)))
+        up = self._concat_size(h, w)
         widths = [(self.deblocks[i][0] if len(self.deblocks) else self.blocks[i][1]).out_channels for i in range(levels)]
         cat = None
         if levels > 1 or len(self.deblocks):
-            cat = torch.empty((n_out, ups[0][0], ups[0][1], sum(widths)), device=x.device, dtype=x.dtype)
+            cat = torch.empty((n_out, up[0], up[1], sum(widths)), device=x.device, dtype=x.dtype)
         c_off = 0
         for i, block in enumerate(self.blocks):
             x = ops.conv2d(x, self._conv_plan("b%d.0" % i, block[1], block[2], 1))
@@ -168,6 +183,9 @@ class BaseBEVBackbone(HipModule):
 
     def forward(self, data_dict):
         x = data_dict["spatial_features"]
+        if self._trains(x):
+            data_dict["spatial_features_2d"] = training.base_bev_backbone(self, x).float()
+            return data_dict
         self._require_inference(x)
         data_dict["spatial_features_2d"] = rt.nchw_view(self.forward_nhwc(rt.to_nhwc(x))).float()
         return data_dict

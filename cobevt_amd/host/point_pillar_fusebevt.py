@@ -18,8 +18,9 @@ graph of host/training.point_pillar_fusebevt (batch statistics over the pillars 
 
 Optional args['anchor_number'] = A adds the detection head OpenCOOD's PointPillar models carry: cls_head (64 -> A, 1 x 1, bias) and
 reg_head (64 -> 7A), and the forward adds 'psm' (B, A, ny, nx) and 'rm' (B, 7A, ny, nx) in fp32 - both from ONE dense product of the
-concatenated weights over the fused rows (ops.linear) - for host.VoxelPostprocessor.post_process.  Inference only: the reference has
-no detection loss, so train() with the argument set raises.  Without the argument the state_dict and the outputs are unchanged.
+concatenated weights over the fused rows (ops.linear) - for host.VoxelPostprocessor.post_process.  In train() mode on ROCm tensors
+both heads run as autograd.conv2d and take the gradient host.PointPillarLoss returns; on CPU tensors train() with the argument set
+raises.  Without the argument the state_dict and the outputs are unchanged.
 
 Optional args['base_bev_backbone'] = model_cfg (BaseBEVBackbone's: layer_nums, layer_strides, num_filters, upsample_strides,
 num_upsample_filter) puts OpenCOOD's 2-D backbone, parameters under backbone.*, on the fused (B, ny, nx, 64) map, between FuseBEVT and
@@ -28,8 +29,9 @@ reasons: FuseBEVT's kernels are built for 64 / 128 channels (not the backbone's 
 instead of B * max_cav.  With it cls_head / reg_head take backbone.num_bev_features inputs, psm / rm come out at the backbone's
 resolution (the standard layer_strides [2, 2, 2] / upsample_strides [1, 2, 4] give ny / 2 x nx / 2, what VoxelPostprocessor's default
 feature_stride = 2 expects), the output gains 'spatial_features_2d' (B, num_bev_features, H', W') fp32 and 'fused_feature' is
-unchanged.  Inference only (the transposed convolution has no backward here): train() with the argument set raises.  Without the
-argument the state_dict, the outputs and the launch sequence are unchanged."""
+unchanged.  In train() mode on ROCm tensors the backbone runs as host/training.base_bev_backbone on the fused map (batch statistics,
+autograd.deconv); on CPU tensors train() with the argument set raises.  Without the argument the state_dict, the outputs and the
+launch sequence are unchanged."""
 import torch
 import torch.nn as nn
 
@@ -120,11 +122,19 @@ class PointPillarFuseBEVT(HipModule):
             return ops.ConvPlan(w, torch.cat([self.cls_head.bias.detach(), self.reg_head.bias.detach()]), dtype=dt, device=dev)
         return self._plan("det_head", tensors, build)
 
+    @staticmethod
+    def on_device(batch_dict):
+        """whether the batch's voxels (or raw points) are ROCm tensors: what a train()-mode forward needs"""
+        lidar = batch_dict.get("processed_lidar")
+        t = lidar.get("voxel_features") if isinstance(lidar, dict) else batch_dict.get("lidar_points")
+        return torch.is_tensor(t) and t.is_cuda
+
     def forward(self, batch_dict):
-        if self.training and self.anchor_number is not None:
+        trains = self.training and self.on_device(batch_dict)
+        if self.training and not trains and self.anchor_number is not None:
             raise CobevtHipError("PointPillarFuseBEVT: the detection head (args['anchor_number']) is inference only - the reference has no "
                                  "detection loss to train it with; call .eval(), or build the model without anchor_number to train")
-        if self.training and self.backbone is not None:
+        if self.training and not trains and self.backbone is not None:
             raise CobevtHipError("PointPillarFuseBEVT: the 2-D backbone (args['base_bev_backbone']) is inference only - its transposed "
                                  "convolutions have no backward; call .eval(), or build the model without base_bev_backbone to train")
         batch_dict = self.with_voxels(batch_dict)

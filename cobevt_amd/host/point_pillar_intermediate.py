@@ -14,14 +14,16 @@ The front end is ops.pillar_vfe_scatter WITHOUT regrouping: one canvas per agent
 each of its levels; both heads are one ops.linear over the fused rows.  The canvas's N = sum(record_len) is an allocation size, so
 the host has to know it: a record_len that lives on the host (a list, a CPU tensor, as the dataset's collate makes it) is summed
 there; with a device record_len the batch carries it as batch_dict['num_agents'] (a host integer).  Either way the forward performs
-no host synchronisation and can be captured in a HIP graph.  Inference only (the reference has no detection loss, the transposed
-convolution no backward): a train()-mode forward raises."""
+no host synchronisation and can be captured in a HIP graph.  In train() mode on ROCm tensors the forward is the differentiable graph of
+host/training.point_pillar_intermediate (the pillar front end with batch statistics, the attentive backbone, both heads), whose psm /
+rm take the gradient host.PointPillarLoss returns; on CPU tensors a train()-mode forward raises."""
 import torch
 import torch.nn as nn
 
 from .. import ops
 from ..lib import CobevtHipError
 from . import runtime as rt
+from . import training
 from .att_bev_backbone import AttBEVBackbone
 from .pillar_vfe import PillarVFE
 from .point_pillar_fusebevt import PointPillarFuseBEVT
@@ -87,6 +89,10 @@ class PointPillarIntermediate(HipModule):
         return canvas
 
     def forward(self, batch_dict):
+        if self.training and PointPillarFuseBEVT.on_device(batch_dict):
+            batch_dict = self.with_voxels(batch_dict)
+            if training.lidar_trains(self.pillar_vfe.pfn_layers[0], batch_dict["processed_lidar"]["voxel_features"]):
+                return training.point_pillar_intermediate(self, batch_dict)
         self._require_inference()
         batch_dict = self.with_voxels(batch_dict)
         x = self.front_end(batch_dict)

@@ -163,7 +163,105 @@ def point_pillar_fusebevt(model, batch_dict):
     b, l, h, w, _ = x.shape
     com_mask = cav_mask[:, None, None, None, :].expand(b, h, w, 1, l).contiguous()
     fused = swap_fusion_encoder_blhwc(model.fusion_net, x, com_mask)           # (B, 64, ny, nx)-shaped
-    return {"fused_feature": fused.float()}
+    out = {"fused_feature": fused.float()}
+    feat = fused
+    if model.backbone is not None:
+        feat = base_bev_backbone(model.backbone, fused)
+        out["spatial_features_2d"] = feat.float()
+    if model.anchor_number is not None:
+        out["psm"], out["rm"] = detection_heads(model, feat)
+    return out
+
+
+# ----------------------------------------------------------------------------------------------
+# the 2-D LiDAR backbones (backbones/base_bev_backbone.py, att_bev_backbone.py, sub_modules/auto_encoder.py,
+# fusion_modules/self_attn.py) and the detectors built on them in train() mode.  Tensors are (N, C, H, W)-shaped in channels-last
+# memory.  Every 3 x 3 conv + BatchNorm2d + ReLU is _conv_bn (each BatchNorm follows its own .training flag), a transposed conv is
+# ag.deconv followed by the same BatchNorm Function, the agent attention ag.att_fuse; no step synchronises with the host.
+# ----------------------------------------------------------------------------------------------
+def deblock(seq, x):
+    """one deblock nn.Sequential(conv, BatchNorm2d, ReLU): ConvTranspose2d(kernel = stride) -> ag.deconv, or the strided Conv2d of
+    upsample_strides < 1"""
+    conv, bn = seq[0], seq[1]
+    if isinstance(conv, torch.nn.ConvTranspose2d):
+        return ag.batch_norm_act(ag.deconv(x, conv), bn, relu=True)
+    return _conv_bn(x, conv, bn, relu=True)
+
+
+def base_bev_backbone(module, x, after_block=None):
+    """BaseBEVBackbone in train() mode: x (N, C, H, W)-shaped -> (N', num_bev_features, H', W')-shaped.  The ZeroPad2d(1) + pad-0 conv is
+    a pad-1 conv, as in eval; after_block(i, x) -> (the map the next level reads, the maps the level's deblock reads) is
+    AttBEVBackbone's hook.  All the eval forward's branches: a strided-conv deblock, a trailing deblock, no deblocks, a single level.
+    The levels' sizes are checked before anything is launched."""
+    _check(x)
+    levels = len(module.blocks)
+    if levels == 0:
+        return x
+    module._concat_size(int(x.shape[2]), int(x.shape[3]))
+    outs = []
+    for i, block in enumerate(module.blocks):
+        x = _conv_bn(x, block[1], block[2], relu=True, pad=1)
+        for k in range(4, len(block), 3):
+            x = _conv_bn(x, block[k], block[k + 1], relu=True)
+        y = x
+        if after_block is not None:
+            x, y = after_block(i, x)
+        if len(module.deblocks):
+            y = deblock(module.deblocks[i], y)
+        outs.append(y)
+    y = outs[0] if len(outs) == 1 else torch.cat(outs, dim=1)
+    if len(module.deblocks) > levels:
+        y = deblock(module.deblocks[-1], y)
+    return y
+
+
+def auto_encoder(module, x):
+    """AutoEncoder in train() mode: the encoders first to last, the decoders last to first"""
+    _check(x)
+    for enc in module.encoder:
+        x = _conv_bn(x, enc[1], enc[2], relu=True, pad=1)
+        x = _conv_bn(x, enc[4], enc[5], relu=True)
+    for i in range(len(module.decoder) - 1, -1, -1):
+        up, conv = module.decoder[i]
+        x = deblock(up, x)
+        x = _conv_bn(x, conv[0], conv[1], relu=True)
+    return x
+
+
+def att_fusion(module, x, record_len):
+    """AttFusion in train() mode: x (N, C, H, W)-shaped, record_len int32 (B,) on the device -> (B, C, H, W)-shaped fp32"""
+    _check(x)
+    if x.shape[1] != module.feature_dim:
+        raise CobevtHipError("AttFusion: %d channels, built for %d" % (x.shape[1], module.feature_dim))
+    return ag.att_fuse(x.permute(0, 2, 3, 1).contiguous(), record_len).permute(0, 3, 1, 2)
+
+
+def att_bev_backbone(module, x, record_len):
+    """AttBEVBackbone in train() mode: per level the block on all N maps, the optional compression, the agent attention N -> B maps,
+    the deblock on the B fused maps; the un-fused maps feed the next level"""
+    def fuse(i, x):
+        if module.compress and i < len(module.compression_modules):
+            x = auto_encoder(module.compression_modules[i], x)
+        return x, att_fusion(module.fuse_modules[i], x, record_len)
+    return base_bev_backbone(module, x, fuse)
+
+
+def detection_heads(model, feat):
+    """cls_head / reg_head (1 x 1, bias) on the (B, C, H', W')-shaped map -> (psm (B, A, H', W'), rm (B, 7A, H', W')) fp32, contiguous"""
+    return ag.conv2d(feat, model.cls_head).float().contiguous(), ag.conv2d(feat, model.reg_head).float().contiguous()
+
+
+def point_pillar_intermediate(model, batch_dict):
+    """PointPillarIntermediate.forward in train() mode: the front-end Function WITHOUT regrouping (one canvas per agent), the attentive
+    backbone, both heads -> the eval forward's keys, shapes and dtypes.  sum(record_len) is known on the host as in eval."""
+    vf, npts, coords = _lidar(batch_dict["processed_lidar"])
+    vfe, sc = model.pillar_vfe, model.scatter
+    x, _ = ag.pillar_vfe(vfe.pfn_layers[0], vf, npts, coords, vfe.geom(), vfe.use_absolute_xyz, vfe.with_distance, grid=(sc.ny, sc.nx),
+                         num_agents=model.num_agents(batch_dict))
+    rl = torch.as_tensor(batch_dict["record_len"]).to(device=vf.device, dtype=torch.int32).contiguous()
+    feat = att_bev_backbone(model.backbone, x.permute(0, 3, 1, 2), rl)
+    psm, rm = detection_heads(model, feat)
+    return {"psm": psm, "rm": rm, "spatial_features_2d": feat.float()}
 
 
 # ----------------------------------------------------------------------------------------------
@@ -382,9 +480,9 @@ def global_attention(m, x):
 # Tensors are (N, C, H, W)-shaped in channels-last memory.
 
 
-def _conv_bn(x, conv, bn=None, relu=False, residual=None):
+def _conv_bn(x, conv, bn=None, relu=False, residual=None, pad=None):
     """conv -> BatchNorm (its own .training flag) [-> + residual] [-> ReLU]; the BN / add / ReLU tail is ONE HIP Function"""
-    y = ag.conv2d(x, conv)
+    y = ag.conv2d(x, conv, pad)
     if bn is not None:
         return ag.batch_norm_act(y, bn, residual=residual, relu=relu)
     if residual is not None:

@@ -45,6 +45,7 @@ SIGNATURES = {
     "cobevt_agent_softmax_sum": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, _vp, _vp] + [ctypes.c_int] * 6 + [_vp]),
     "cobevt_att_fuse_nhwc": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_long, ctypes.c_int,
                                             ctypes.c_float, _vp]),
+    "cobevt_att_fuse_bwd_nhwc": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_long, ctypes.c_int, ctypes.c_float, _vp]),
     "cobevt_window_attention": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _c_int_p, ctypes.c_float, _vp]),
     "cobevt_window_attention_ksplit": (ctypes.c_int, [_vp] * 8 + [_c_int_p, ctypes.c_float, ctypes.c_int, ctypes.c_long, _vp]),
     "cobevt_window_attention_lse": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_int_p, ctypes.c_float, ctypes.c_float,
@@ -55,6 +56,8 @@ SIGNATURES = {
     "cobevt_layernorm_bwd_scratch": (ctypes.c_long, [ctypes.c_int, ctypes.c_int]),
     "cobevt_layernorm_bwd": (ctypes.c_int, [_vp] * 6 + [ctypes.c_int, ctypes.c_int, ctypes.c_float, _vp, _vp]),
     "cobevt_conv_wgrad": (ctypes.c_int, [_vp, _vp, _vp, _c_int_p, _vp]),
+    "cobevt_deconv_wgrad_chunks": (ctypes.c_int, [_c_int_p]),
+    "cobevt_deconv_wgrad": (ctypes.c_int, [_vp, _vp, _vp, _vp, _c_int_p, _vp]),
     "cobevt_conv_wgrad_blocked": (ctypes.c_int, [_vp, _vp, _vp, _c_int_p, _vp]),
     "cobevt_gelu": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_long, _vp]),
     "cobevt_layernorm_fwd_t": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_float, _c_int_p, _vp]),

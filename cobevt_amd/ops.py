@@ -2659,6 +2659,155 @@ def att_fuse(x, record_len, out=None):
     return out
 
 
+def att_fuse_bwd(x, record_len, dout):
+    """The backward of att_fuse with respect to x in one cobevt_att_fuse_bwd_nhwc launch (fp32 storage only): x (N, H, W, C) contiguous
+    fp32, record_len (B,) int32 on the device, dout (B, H, W, C) contiguous fp32 -> dx (N, H, W, C) fp32.  Nothing of the forward is
+    kept: the scores are recomputed per pixel.  Every element of dx is written once; rows of agents outside every sample are 0."""
+    if x.dim() != 4 or not x.is_contiguous() or min(x.shape) < 1:
+        raise CobevtHipError("att_fuse_bwd: x must be a contiguous non-empty (N, H, W, C) tensor, got %s (contiguous=%s)"
+                             % (tuple(x.shape), x.is_contiguous()))
+    if x.dtype != torch.float32:
+        raise CobevtHipError("att_fuse_bwd: fp32 storage only, got %s" % x.dtype)
+    n, h, w, c = (int(d) for d in x.shape)
+    if not att_fuse_group_ok(c):
+        raise CobevtHipError("att_fuse_bwd: C=%d must be 8 times a power of two, at most 512 (8 channels per lane, one group of lanes per pixel)" % c)
+    if record_len.dtype != torch.int32 or record_len.dim() != 1 or not record_len.is_contiguous() or record_len.shape[0] < 1:
+        raise CobevtHipError("att_fuse_bwd: record_len must be a contiguous int32 (B,) tensor with B >= 1, got %s %s"
+                             % (record_len.dtype, tuple(record_len.shape)))
+    b = int(record_len.shape[0])
+    if b > 65535:
+        raise CobevtHipError("att_fuse_bwd: %d samples exceed the grid's 65535" % b)
+    if dout.dtype != torch.float32 or tuple(dout.shape) != (b, h, w, c) or not dout.is_contiguous():
+        raise CobevtHipError("att_fuse_bwd: dout must be a contiguous fp32 tensor of shape %s, got %s %s" % ((b, h, w, c), dout.dtype, tuple(dout.shape)))
+    _need_cuda(x, record_len, dout)
+    dx = torch.empty_like(x)
+    cost = lambda: (2.0 * 6 * n * h * w * c, 4.0 * (3 * n + b) * h * w * c)         # noqa: E731
+    with _timed("att_fuse_bwd|N%d B%d HW=%d C=%d" % (n, b, h * w, c), cost):
+        _L.call("cobevt_att_fuse_bwd_nhwc", _p(x), _p(record_len), _p(dout), _p(dx), b, n, h * w, c, ctypes.c_float(1.0 / math.sqrt(c)), _stream(),
+                variant="")
+    return dx
+
+
+# ---------------------------------------------------------------------------------------------- training of the transposed convolution
+# fp32 only, the native library (exact fp32 products).  Scratch buffers are cached per size like the sparse path's.
+_DECONV_TRAIN_WEIGHTS = {}  # id(weight) -> (weakref, version, data_ptr, forward table, input-gradient rows)
+
+
+def _deconv_geometry(cin, cout, s, what):
+    if not 1 <= s <= DECONV_MAX_STRIDE:
+        raise CobevtHipError("%s: stride %d is outside 1 .. %d" % (what, s, DECONV_MAX_STRIDE))
+    if cin < 4 or cin % 4 != 0:
+        raise CobevtHipError("%s: Cin=%d must be a multiple of 4 for the fp32 kernels" % (what, cin))
+    if cout < 32 or cout % 32 != 0:
+        raise CobevtHipError("%s: Cout=%d must be a multiple of 32 (one MFMA tile = 32 channels of one tap)" % (what, cout))
+
+
+def deconv_train_weights(weight):
+    """The fp32 master weight (Cin, Cout, s, s) of an nn.ConvTranspose2d(kernel = stride = s, bias=False) -> the two UNfolded operand
+    tables of its training kernels: forward [s s Cout][Kpad] with row (dy s + dx) Cout + co = weight[:, co, dy, dx] (DeconvPlan's
+    layout without a BatchNorm) and input-gradient rows [Cin][Kpad'] with k = (dy s + dx) Cout + co (the implicit-GEMM rows of the
+    weight read as (out = Cin, in = Cout, s, s)); both padded with zero columns to a multiple of 16.  Device permutes - no host round
+    trip per optimiser step, unlike DeconvPlan - cached per weight OBJECT on its version counter and address (hand over the
+    nn.Parameter itself); an entry goes when its weight does.  Never cached inside a graph capture."""
+    if weight.dim() != 4 or weight.shape[2] != weight.shape[3] or weight.dtype != torch.float32:
+        raise CobevtHipError("deconv_train_weights: weight must be fp32 (Cin, Cout, s, s), got %s %s" % (weight.dtype, tuple(weight.shape)))
+    cin, cout, s, _ = (int(d) for d in weight.shape)
+    _deconv_geometry(cin, cout, s, "deconv_train_weights")
+    capturing = weight.is_cuda and torch.cuda.is_current_stream_capturing()
+    ent = _DECONV_TRAIN_WEIGHTS.get(id(weight))
+    if not capturing and ent is not None and ent[0]() is weight and ent[1:3] == (weight._version, weight.data_ptr()):
+        return ent[3], ent[4]
+    w = weight.detach()
+    kf, kd = (cin + 15) // 16 * 16, (s * s * cout + 15) // 16 * 16
+    fwd = torch.zeros((s * s * cout, kf), device=w.device, dtype=torch.float32)
+    fwd[:, :cin] = w.permute(2, 3, 1, 0).reshape(s * s * cout, cin)
+    rows = torch.zeros((cin, kd), device=w.device, dtype=torch.float32)
+    rows[:, :s * s * cout] = w.permute(0, 2, 3, 1).reshape(cin, s * s * cout)
+    if not capturing:
+        key = id(weight)
+        _DECONV_TRAIN_WEIGHTS[key] = (weakref.ref(weight, lambda _, key=key: _DECONV_TRAIN_WEIGHTS.pop(key, None)), weight._version,
+                                      weight.data_ptr(), fwd, rows)
+    return fwd, rows
+
+
+def _deconv_map_f32(t, shape, what):
+    if t is None or t.dtype != torch.float32 or t.dim() != 4 or not t.is_contiguous() or min(t.shape) < 1 \
+            or (shape is not None and tuple(t.shape) != tuple(shape)):
+        raise CobevtHipError("%s must be a contiguous non-empty fp32 %s tensor, got %s" % (
+            what, "(N, H, W, C)" if shape is None else tuple(shape), None if t is None else "%s %s" % (t.dtype, tuple(t.shape))))
+    return t
+
+
+def deconv_raw(x, wgt, cout, s):
+    """z = ConvTranspose2d(kernel = stride = s)(x) without BatchNorm or activation: x (N, H, W, Cin) contiguous fp32, wgt the forward
+    table of deconv_train_weights -> z (N, sH, sW, Cout) fp32.  One cobevt_deconv_nhwc launch of the native library (exact fp32) with a
+    zero shift, act = 0, c_off = 0."""
+    _deconv_map_f32(x, None, "deconv_raw: x")
+    n, h, w, cin = (int(d) for d in x.shape)
+    cout, s = int(cout), int(s)
+    _deconv_geometry(cin, cout, s, "deconv_raw")
+    if wgt.dtype != torch.float32 or wgt.dim() != 2 or not wgt.is_contiguous() or wgt.shape[0] != s * s * cout or wgt.shape[1] < cin \
+            or wgt.shape[1] % 16:
+        raise CobevtHipError("deconv_raw: the weight table must be contiguous fp32 (%d, Kpad >= %d in 16s), got %s %s"
+                             % (s * s * cout, cin, wgt.dtype, tuple(wgt.shape)))
+    if n * h * w * s * s >= 2 ** 31 - 1:
+        raise CobevtHipError("deconv_raw: %d destination pixels overflow the kernel's 32-bit pixel index" % (n * h * w * s * s))
+    _need_cuda(x, wgt)
+    z = torch.empty((n, s * h, s * w, cout), device=x.device, dtype=torch.float32)
+    shift = _zero_shift(x.device, cout)
+    dims = _ints([FP32, n, h, w, cin, cout, wgt.shape[1], s, 0, cout, 0])
+    m = n * h * w
+    with _timed("deconv_raw|s%d %d->%d M=%d" % (s, cin, cout, m), lambda: (2.0 * m * s * s * cout * cin, 4.0 * (m * cin + wgt.numel() + m * s * s * cout))):
+        _L.call("cobevt_deconv_nhwc", _p(x), _p(wgt), _p(shift), _p(z), dims, _stream(), variant="")
+    return z
+
+
+_ZERO_SHIFT = {}
+
+
+def _zero_shift(dev, c):
+    """fp32 zeros (c,), never written: the shift operand of the raw transposed convolution"""
+    key = (dev, c)
+    if key in _ZERO_SHIFT:
+        return _ZERO_SHIFT[key]
+    z = torch.zeros(c, device=dev, dtype=torch.float32)
+    if not (dev.type == "cuda" and torch.cuda.is_current_stream_capturing()):       # a capture's allocations belong to its graph
+        _ZERO_SHIFT[key] = z
+    return z
+
+
+def deconv_wgrad_chunks(n, h, w, cin, cout, s):
+    """cobevt_deconv_wgrad_chunks: the pixel chunks of deconv_wgrad, a pure function of the shape (no device)"""
+    rc = _L.load("").cobevt_deconv_wgrad_chunks(_ints([n, h, w, cin, cout, s]))
+    if rc < 0:
+        raise CobevtHipError("deconv_wgrad: shape N=%d H=%d W=%d Cin=%d Cout=%d s=%d is not served (error %d)" % (n, h, w, cin, cout, s, -rc))
+    return int(rc)
+
+
+def deconv_wgrad(x, dz, s):
+    """The weight gradient of deconv_raw (cobevt_deconv_wgrad, two launches): x (N, H, W, Cin), dz (N, sH, sW, Cout) contiguous fp32 ->
+    dW (Cin, Cout, s, s) fp32, the ConvTranspose2d layout, written.  No floating-point atomics: pixel chunks added in order in fp64."""
+    _deconv_map_f32(x, None, "deconv_wgrad: x")
+    n, h, w, cin = (int(d) for d in x.shape)
+    s = int(s)
+    if dz is None or dz.dim() != 4:
+        raise CobevtHipError("deconv_wgrad: dz must be a 4-D tensor")
+    cout = int(dz.shape[3])
+    _deconv_geometry(cin, cout, s, "deconv_wgrad")
+    _deconv_map_f32(dz, (n, s * h, s * w, cout), "deconv_wgrad: dz")
+    if n * h * w * s * s >= 2 ** 31 - 1:
+        raise CobevtHipError("deconv_wgrad: %d pixels of dz overflow the kernel's 32-bit pixel index" % (n * h * w * s * s))
+    _need_cuda(x, dz)
+    chunks = deconv_wgrad_chunks(n, h, w, cin, cout, s)
+    floats = chunks * s * s * ((cin + 31) // 32 * 32) * cout
+    partial = _sparse_train_ws(x.device, torch.float32, floats)
+    dw = torch.empty((cin, cout, s, s), device=x.device, dtype=torch.float32)
+    m = n * h * w
+    with _timed("deconv_wgrad|s%d %d->%d M=%d" % (s, cin, cout, m), lambda: (2.0 * m * s * s * cout * cin, 4.0 * (m * s * s * (cin + cout) + 2 * floats))):
+        _L.call("cobevt_deconv_wgrad", _p(x), _p(dz), _p(partial), _p(dw), _ints([n, h, w, cin, cout, s, chunks]), _stream(), variant="")
+    return dw
+
+
 def invert_small(m):
     """Batched inverse of (..., 3, 3) or (..., 4, 4) fp32 matrices on the device."""
     _need_cuda(m)

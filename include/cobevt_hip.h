@@ -288,6 +288,18 @@ int cobevt_gelu_bf16(const void* x, const void* dy, void* out, long n, hipStream
  * stride, pad, storage type of x and dy (0 bf16 - the autocast path -, 1 fp32).  (cuDNN under autograd in the reference: every
  * nn.Conv2d on the path, train_camera.py:166-173.) */
 int cobevt_conv_wgrad(const void* x, const void* dy, float* dw, const int* dims, hipStream_t stream);
+/* Weight gradient of the transposed convolution z = ConvTranspose2d(kernel = stride = s, no bias) of x, channels-last, exact fp32 in
+ * every library: dw[ci][co][dy][dx] = sum over (n, y, x) of x[n, y, x, ci] dz[n, s y + dy, s x + dx, co], with x (N, H, W, Cin) and
+ * dz (N, sH, sW, Cout) contiguous fp32 and dw fp32 in the ConvTranspose2d layout (Cin, Cout, s, s), WRITTEN (not accumulated).  The
+ * input pixels are the k dimension of v_mfma_f32_32x32x2_f32 and both operands are read as they lie; the pixel range is cut into
+ * chunks whose accumulators go to `partial` (chunks x s s x Cin padded to 32 x Cout floats, plain stores), and a second launch adds
+ * the chunks in order in fp64 and rounds once: no floating-point atomics, bit-reproducible.  dims (int32[7]): N, H, W, Cin, Cout, s,
+ * chunks.  cobevt_deconv_wgrad_chunks reads dims[0..5] and returns the chunk count, a pure function of the shape (about 2048 one-wave
+ * workgroups, at least 64 pixels per chunk, at most 64 MB of partials; not tuned), or MINUS an error code for a shape that is not
+ * served; the launch returns COBEVT_ERR_SHAPE unless dims[6] is that count.  Served: 1 <= s <= 8, Cin % 4 == 0, Cout % 32 == 0,
+ * N sH sW < 2^31 - 1, s s Cin (padded to 32) Cout floats <= 64 MB. */
+int cobevt_deconv_wgrad_chunks(const int* dims);
+int cobevt_deconv_wgrad(const float* x, const float* dz, float* partial, float* dw, const int* dims, hipStream_t stream);
 /* The same weight gradient on the bf16 matrix path from BLOCKED bf16 copies of the operands (8 pixels of one channel = one 16-byte
  * piece, so a lane's matrix operand is one coalesced load and zero padding replaces every bounds test; cobevt_wgrad_block_operand
  * makes them): xb [N][Hp][XB][P][Cin][8] = x zero-padded by `pad` rows / columns, db [N][Ho][DB][Cout][8] = dy with rows zero-padded
@@ -402,6 +414,16 @@ int cobevt_agent_softmax_sum(const void* score, int lds, const void* nb, const f
  * written once.  COBEVT_ERR_SHAPE unless C = 8 * 2^k <= 512, 1 <= B <= 65535, N >= 1, HW >= 1. */
 int cobevt_att_fuse_nhwc(const void* x, const int* record_len, void* out, int dtype, int B, int N, long HW, int C, float scale,
                          hipStream_t stream);
+/* Its backward with respect to x (fp32 storage only): x (N, HW, C), dout (B, HW, C) -> dx (N, HW, C).  Nothing is saved by the forward;
+ * per pixel the scores are recomputed: with g = dout[b, p], P = softmax_j(s), t_j = <g, x_j>, ds_j = P_j (t_j - sum_k P_k t_k):
+ * dx_j = P_j g + scale ds_j x_0 for every agent j of the sample, and the ego's row additionally gets scale sum_j ds_j x_j.  Two
+ * passes over the agents (statistics with a running maximum; rows), fp32 arithmetic, accurate expf, 16-byte accesses, the
+ * forward's groups and grid.  record_len is read on the device and n is clamped to [0, N - off] as in the forward.  Every element of
+ * dx is written exactly once (record_len >= 0): rows of agents that belong to no sample - off + j >= sum(record_len), or a sample
+ * with n <= 0 - get 0; no atomics, no zero-fill needed.  A sample of one agent returns dx_0 = g (P_0 = 1 and ds_0 = 0 exactly).
+ * The forward's shape rules: COBEVT_ERR_SHAPE unless C = 8 * 2^k <= 512, 1 <= B <= 65535, N >= 1, HW >= 1. */
+int cobevt_att_fuse_bwd_nhwc(const float* x, const int* record_len, const float* dout, float* dx, int B, int N, long HW, int C, float scale,
+                             hipStream_t stream);
 
 /* regroup: split by record_len (device int32[B]), zero pad to max_cav, agent mask (B,max_cav) fp32.
  * Replaces fuse_utils.py:8-61 without its host synchronisation (:26). */

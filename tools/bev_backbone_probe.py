@@ -6,7 +6,15 @@ torch-ROCm's own ConvTranspose2d + BatchNorm2d + ReLU + cat / the same container
 Standard OpenCOOD PointPillar backbone (num_filters [64, 128, 256] -> 3 x 128 channels at 128 x 128, from a 256 x 256 canvas of 64
 channels).  The two sides alternate in rounds of `iters` calls between device events; the figure is the median round.  torch runs in
 both memory formats (NCHW as the reference does, channels_last as its best case).  Prints one JSON line per measurement, first the
-box calibration of bench.py."""
+box calibration of bench.py.
+
+    python tools/bev_backbone_probe.py --train [--out profiles/detector_train_timing.json]
+
+times the training path instead (fp32, device events, median of 20 single calls): one forward + backward of the standard backbone at
+B = 1 through host.training.base_bev_backbone against torch's autograd on the same containers; cobevt_deconv_wgrad against
+cobevt_conv_wgrad with the roles swapped (autograd.USE_DECONV_WGRAD = False) at the three standard deblock shapes; and
+cobevt_att_fuse_bwd_nhwc in GB/s of (2 N + B) HW C floats at OPV2V's three levels (5 agents in one sample).  Also the eval forward
+of the backbone (fp32), for comparison across commits.  The chunk counts and grids are untuned."""
 import argparse
 import copy
 import json
@@ -45,13 +53,95 @@ def timed(fns, iters, rounds):
     return {k: round(statistics.median(v), 4) for k, v in ms.items()}, {k: [round(x, 4) for x in v] for k, v in ms.items()}
 
 
+def median_ms(f, n=20):
+    """median of n single calls between device events, after three warm-up calls"""
+    for _ in range(3):
+        f()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(n):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        f()
+        e1.record()
+        torch.cuda.synchronize()
+        ms.append(e0.elapsed_time(e1))
+    return round(statistics.median(ms), 4), [round(min(ms), 4), round(max(ms), 4)]
+
+
+def train(dev, out_path):
+    from cobevt_amd import autograd as ag
+    from cobevt_amd.host import training
+    res = {}
+    try:
+        import bench
+        res["box_calibration"] = bench.box_calibration(dev)
+    except Exception as e:
+        res["box_calibration"] = "unavailable: %r" % (e,)
+    model = fill_module_(host.BaseBEVBackbone(copy.deepcopy(CFG), 64), 0).to(dev)
+    torch.manual_seed(0)
+    x = torch.rand((1, 64, 256, 256), device=dev).contiguous(memory_format=torch.channels_last)
+    with torch.no_grad(), host.compute_dtype("fp32"):
+        model.eval()
+        res["eval_forward_fp32_ms"] = median_ms(lambda: model.forward_nhwc(x.permute(0, 2, 3, 1)))
+    model.train()
+    tmodel = copy.deepcopy(model)
+
+    def hip_step():
+        model.zero_grad(set_to_none=True)
+        training.base_bev_backbone(model, x).sum().backward()
+
+    def torch_step(t):
+        def run():
+            tmodel.zero_grad(set_to_none=True)
+            ups, y = [], t
+            for i in range(3):
+                y = tmodel.blocks[i](y)
+                ups.append(tmodel.deblocks[i](y))
+            torch.cat(ups, dim=1).sum().backward()
+        return run
+    with torch.enable_grad():
+        res["backbone_fwd_bwd_ms"] = {"hip": median_ms(hip_step), "torch_channels_last": median_ms(torch_step(x)),
+                                      "torch_nchw": median_ms(torch_step(x.contiguous()))}
+    res["deconv_wgrad_ms"] = []
+    for i, (cin, s) in enumerate(zip(CFG["num_filters"], CFG["upsample_strides"])):
+        hw = 128 >> i
+        xi, dz = torch.rand((1, hw, hw, cin), device=dev), torch.rand((1, hw * s, hw * s, 128), device=dev)
+        dw = torch.zeros((cin, 128, s, s), device=dev)
+        dims = ops._ints([1, s * hw, s * hw, 128, hw, hw, cin, s, s, 0, ops.FP32])
+
+        def atomics():
+            dw.zero_()
+            ag._call("cobevt_conv_wgrad", ops._p(dz), ops._p(xi), ops._p(dw), dims, ops._stream())
+        new = ops.deconv_wgrad(xi, dz, s)
+        atomics()
+        res["deconv_wgrad_ms"].append({"s": s, "cin": cin, "cout": 128, "pixels": hw * hw, "chunks": ops.deconv_wgrad_chunks(1, hw, hw, cin, 128, s),
+                                       "chunked": median_ms(lambda: ops.deconv_wgrad(xi, dz, s)), "atomics_with_zero_fill": median_ms(atomics),
+                                       "max_rel_diff": float((new - dw).abs().max() / dw.abs().max())})
+    res["att_fuse_bwd"] = []
+    rl = torch.tensor([5], dtype=torch.int32, device=dev)
+    for c, h, w in ((64, 100, 352), (128, 50, 176), (256, 25, 88)):
+        xa, g = torch.rand((5, h, w, c), device=dev) - 0.5, torch.rand((1, h, w, c), device=dev) - 0.5
+        ms = median_ms(lambda: ops.att_fuse_bwd(xa, rl, g))
+        res["att_fuse_bwd"].append({"C": c, "H": h, "W": w, "ms": ms, "GBps": round((2 * 5 + 1) * h * w * c * 4 / ms[0] / 1e6, 1)})
+    print(json.dumps(res), flush=True)
+    if out_path:
+        with open(out_path, "w") as f:
+            json.dump(res, f, indent=1, sort_keys=True)
+            f.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, nargs="+", default=[1, 8])
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--train", action="store_true", help="time the training path (see the module docstring)")
+    ap.add_argument("--out", default=None, help="--train: also write the result as JSON to this file")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
+    if a.train:
+        return train(dev, a.out)
     torch.set_grad_enabled(False)
     try:
         import bench
