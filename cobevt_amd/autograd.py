@@ -1428,78 +1428,36 @@ def conv2d_weight(x, weight, bias, stride=1, pad=0):
 _PILLAR_STAT_DOUBLES = 512
 
 
-def _pillar_mode(norm):
-    """0 batch statistics (norm.training, or a norm without running statistics), 1 frozen running statistics, 2 no norm"""
-    if norm is None:
-        return 2
-    if norm.training or not norm.track_running_stats or norm.running_mean is None:
-        if norm.training and norm.track_running_stats and norm.momentum is None:
-            raise CobevtHipError("BatchNorm1d(momentum=None): the pillar training kernels keep an exponential running average and need a "
-                                 "numeric momentum")
-        return 0
-    return 1
-
-
 def pillar_train_stats(weight, gamma, beta, vf, npts, coords, record_len, norm, cfg):
     """The statistics pass of PillarVfeFn (cobevt_pillar_train_stats: compaction of the valid pillars, fp64 sums, the finishing launch
     incl. the running-statistics update) -> the state the forward and the backward take: the folded operands `wf` (K, 64) / `sf` (64) for
     the inference operator, the valid pillars' order / destination rows / count, and the fp64 statistics block."""
     geom, use_abs, dist, grid, max_cav, num_agents = cfg
-    _need_cuda(weight, gamma, beta, vf, npts, coords, record_len)
-    mode = _pillar_mode(norm)
-    if vf.dtype != torch.float32 or vf.dim() != 3 or not vf.is_contiguous():
-        raise CobevtHipError("pillar VFE training: voxel_features must be contiguous fp32 (P, T, 4)")
-    p, t, f = vf.shape
-    k = (4 if use_abs else 1) + 6 + (1 if dist else 0)
-    if f != 4 or t < 1 or t > ops.PILLAR_MAX_POINTS or tuple(weight.shape) != (ops.PILLAR_CHANNELS, k):
-        raise CobevtHipError("pillar VFE training: F = 4, 1 <= T <= %d and a (%d, %d) weight are supported, got F = %d, T = %d, weight %s"
-                             % (ops.PILLAR_MAX_POINTS, ops.PILLAR_CHANNELS, k, f, t, tuple(weight.shape)))
-    npts = ops._index_i32(npts, "pillar VFE training: voxel_num_points", ())
-    coords = ops._index_i32(coords, "pillar VFE training: voxel_coords", (4,))
-    if npts.shape[0] != p or coords.shape[0] != p:
-        raise CobevtHipError("pillar VFE training: voxel_num_points (P) and voxel_coords (P, 4) must match voxel_features' P = %d" % p)
-    dev = vf.device
+    _need_cuda(weight, gamma, beta)
+    bn = ops.BnTrainMode(norm, "pillar")
+    npts, coords, dims, gm, k, rl, _ = ops.pillar_args("pillar VFE training", vf, npts, coords, geom, use_abs, dist, ops.FP32, grid, record_len,
+                                                       max_cav, num_agents)
+    if tuple(weight.shape) != (ops.PILLAR_CHANNELS, k):
+        raise CobevtHipError("pillar VFE training: a (%d, %d) weight is supported, got %s" % (ops.PILLAR_CHANNELS, k, tuple(weight.shape)))
+    p, dev = vf.shape[0], vf.device
     w = _f32c(weight.detach(), "weight")
     g = None if gamma is None else _f32c(gamma.detach(), "gamma")
     b = None if beta is None else _f32c(beta.detach(), "beta")
-    rows = grid is None
-    ny, nx = (0, 0) if rows else (int(grid[0]), int(grid[1]))
-    rl = None
-    if not rows and record_len is not None:
-        if record_len.dtype != torch.int32 or record_len.dim() != 1 or not record_len.is_contiguous() or max_cav is None:
-            raise CobevtHipError("pillar VFE training: record_len must be int32 (B,) on the device, with max_cav given")
-        rl = record_len
-    if not rows and rl is None and num_agents is None:
-        raise CobevtHipError("pillar VFE training: num_agents (a host integer) is required without record_len")
-    nb = 0 if rl is None else rl.shape[0]
-    n = 0 if rows else (0x7fffffff if num_agents is None else int(num_agents))
-    dims = _ints([p, t, f, k, int(bool(use_abs)), int(bool(dist)), ops.FP32, int(rows), n, nb, int(max_cav or 0), ny, nx])
-    gm = (ctypes.c_float * 6)(*[float(v) for v in geom])
-    n_stat, n_bwd = ctypes.c_long(0), ctypes.c_long(0)
-    _call("cobevt_pillar_train_scratch", p, ctypes.byref(n_stat), ctypes.byref(n_bwd))
+    n_stat, n_bwd = ops._scratch("cobevt_pillar_train_scratch", p, n=2, variant="")
     order = torch.empty(max(p, 1), device=dev, dtype=torch.int32)
     dst = torch.empty(max(p, 1), device=dev, dtype=torch.int64)
     count = torch.empty(1, device=dev, dtype=torch.int32)
-    partial = torch.empty(n_stat.value, device=dev, dtype=torch.float64)
+    partial = torch.empty(n_stat, device=dev, dtype=torch.float64)
     wf = torch.empty((k, ops.PILLAR_CHANNELS), device=dev, dtype=torch.float32)
     sf = torch.empty(ops.PILLAR_CHANNELS, device=dev, dtype=torch.float32)
     stat = torch.empty(_PILLAR_STAT_DOUBLES, device=dev, dtype=torch.float64)
-    track = mode == 0 and norm.track_running_stats and norm.running_mean is not None
-    rm = norm.running_mean if (track or mode == 1) else None
-    rv = norm.running_var if (track or mode == 1) else None
-    nbt = norm.num_batches_tracked if track else None
-    eps = 0.0 if norm is None else norm.eps
-    momentum = 0.0 if (norm is None or norm.momentum is None) else norm.momentum
+    rm, rv, nbt, eps, momentum = bn.buffers()
     _call("cobevt_pillar_train_stats", _p(vf), _p(npts), _p(coords), _p(rl), _p(w), _p(g), _p(b), _p(rm), _p(rv), _p(nbt), _p(order),
-          _p(dst), _p(count), _p(partial), _p(wf), _p(sf), _p(stat), dims, gm, mode, ctypes.c_float(eps), ctypes.c_float(momentum),
+          _p(dst), _p(count), _p(partial), _p(wf), _p(sf), _p(stat), dims, gm, bn.mode, ctypes.c_float(eps), ctypes.c_float(momentum),
           _stream())
-    if track:
-        # written through raw pointers: bump the version counters (plans folded from the running statistics, graph fingerprints)
-        for tns in (norm.running_mean, norm.running_var, norm.num_batches_tracked):
-            if tns is not None:
-                torch.autograd.graph.increment_version(tns)
-    return {"tensors": (vf, npts, coords, order, dst, count, wf, sf, w, g, stat), "rl": rl, "dims": dims, "geom": gm, "mode": mode,
-            "n_bwd": int(n_bwd.value), "k": k, "has_g": gamma is not None, "has_b": beta is not None}
+    bn.written()
+    return {"tensors": (vf, npts, coords, order, dst, count, wf, sf, w, g, stat), "rl": rl, "dims": dims, "geom": gm, "mode": bn.mode,
+            "n_bwd": n_bwd, "k": k, "has_g": gamma is not None, "has_b": beta is not None}
 
 
 def pillar_train_forward(state, cfg):
@@ -1572,7 +1530,7 @@ def pillar_vfe(pfn, vf, npts, coords, geom, use_absolute_xyz, with_distance, gri
     if vf.requires_grad:
         raise CobevtHipError("pillar VFE training: no gradient with respect to voxel_features is offered (detach the points)")
     if pfn.use_norm:
-        _pillar_mode(pfn.norm)           # momentum=None raises before anything is launched
+        ops.BnTrainMode(pfn.norm, "pillar")           # momentum=None raises before anything is launched
         return PillarVfeFn.apply(pfn.linear.weight, pfn.norm.weight, pfn.norm.bias, vf, npts, coords, record_len, pfn.norm, cfg)
     return PillarVfeFn.apply(pfn.linear.weight, None, pfn.linear.bias, vf, npts, coords, record_len, None, cfg)
 
@@ -1610,17 +1568,6 @@ def scatter_rows(rows, coords, num_agents, grid):
 # ----------------------------------------------------------------------------------------------
 # the sparse 3-D voxel backbone in train() mode (csrc/sparse_conv.hip)
 # ----------------------------------------------------------------------------------------------
-def _sparse_bn_frozen(bn):
-    """False: batch statistics (bn.training, or a norm without running statistics); True: the frozen running statistics.
-    BatchNorm1d(momentum=None) raises: the kernels keep an exponential running average."""
-    if bn.training or not bn.track_running_stats or bn.running_mean is None:
-        if bn.training and bn.track_running_stats and bn.momentum is None:
-            raise CobevtHipError("BatchNorm1d(momentum=None): the sparse training kernels keep an exponential running average and need a "
-                                 "numeric momentum")
-        return False
-    return True
-
-
 class SparseConvBnReluFn(torch.autograd.Function):
     """One layer of VoxelBackBone8x in train() mode: SubMConv3d / SparseConv3d (bias=False) -> BatchNorm1d over the live rows -> ReLU.
     feats (rows, input row) fp32 are the features of the level `x` (an ops.SparseConvTensor: indices, num, workspace, row_map - no
@@ -1632,7 +1579,7 @@ class SparseConvBnReluFn(torch.autograd.Function):
     @staticmethod
     @_amp_fwd
     def forward(ctx, feats, weight, gamma, beta, x, level, conv, bn, tables=None):
-        frozen = _sparse_bn_frozen(bn)
+        frozen = ops.BnTrainMode(bn, "sparse").mode == 1
         feats = _f32c(feats, "sparse features")
         wf, wt = tables if tables is not None else ops.sparse_train_weights(weight)
         xt = ops.SparseConvTensor(feats, x.indices, x.num, x.spatial_shape, x.batch_size, x.workspace, row_map=x.row_map)
@@ -1671,7 +1618,7 @@ def sparse_conv_bn_relu(x, conv, bn, capacity=None, workspace=None, out_level=No
         level = out_level
     else:
         level = ops.sparse_downsample(x, conv.kernel_size, conv.stride, conv.padding, capacity, workspace)
-    _sparse_bn_frozen(bn)                    # momentum=None raises before anything is launched
+    ops.BnTrainMode(bn, "sparse")            # momentum=None raises before anything is launched
     # lowered HERE, from the Parameter object itself: the cache of ops.sparse_train_weights is per object, and what a Function's forward
     # receives need not be that object (autocast hands it a cast copy)
     tables = ops.sparse_train_weights(conv.weight)

@@ -120,7 +120,7 @@ def lidar_trains(pfn, voxel_features):
     if voxel_features.requires_grad:
         raise CobevtHipError("pillar VFE training: no gradient with respect to voxel_features is offered (detach the points)")
     if pfn is not None and pfn.use_norm:
-        ag._pillar_mode(pfn.norm)
+        ops.BnTrainMode(pfn.norm, "pillar")
     return voxel_features.is_cuda
 
 
@@ -294,7 +294,7 @@ def voxel_backbone8x(module, batch_dict, keep_layers=False):
         raise CobevtHipError("sparse backbone training: no gradient with respect to voxel_features is offered (detach the points)")
     layers = module._layers()
     for _, _, bn in layers:
-        ag._sparse_bn_frozen(bn)                                            # momentum=None raises before anything is launched
+        ops.BnTrainMode(bn, "sparse")                                           # momentum=None raises before anything is launched
     if vf.dim() != 2 or vf.shape[1] != layers[0][1].in_channels or coords.shape[0] != vf.shape[0]:
         raise CobevtHipError("VoxelBackBone8x: voxel_features must be (P, %d) with one row per row of voxel_coords, got %s / %s"
                              % (layers[0][1].in_channels, tuple(vf.shape), tuple(coords.shape)))

@@ -1149,27 +1149,181 @@ def _index_i32(t, what, shape_tail=None):
     return t if t.is_contiguous() else t.contiguous()
 
 
-def _pillar_call(voxel_features, voxel_num_points, voxel_coords, w, shift, geom, use_absolute_xyz, with_distance, out, dtype, rows,
-                 record_len, cav, n, b, max_cav, ny, nx):
-    _need_cuda(voxel_features, voxel_num_points, voxel_coords, w, shift, record_len, out)
-    if voxel_features.dtype != torch.float32 or voxel_features.dim() != 3 or not voxel_features.is_contiguous():
-        raise CobevtHipError("pillar_vfe: voxel_features must be contiguous fp32 (P, T, F)")
-    p, t, f = voxel_features.shape
+def _scratch(entry, dims, n=1, packed=False, variant=None):
+    """The size question every `*_scratch` entry of the C library answers: dims (a c_long vector, or the one integer the entry takes)
+    -> the size, or the n sizes, written through one output word each (packed: through one c_long vector of n)"""
+    out = (ctypes.c_long * n)() if packed else [ctypes.c_long(0) for _ in range(n)]
+    _L.call(entry, dims, *([out] if packed else [ctypes.byref(v) for v in out]), variant=variant)
+    sizes = tuple(int(v) if packed else v.value for v in out)
+    return sizes[0] if n == 1 else sizes
+
+
+def _longs(*vals):
+    return (ctypes.c_long * len(vals))(*[int(v) for v in vals])
+
+
+_WORKSPACES = {}      # family -> {(device,) + key: the default buffer}, for the life of the process
+WORKSPACE_ALIGN = 16  # bytes: the strictest start any family demands of a workspace; every default has it
+# family -> the arguments its C size formula reads, as the key of its default buffer.  A key that left one out would hand a later call
+# a buffer that is too small; one that held more (bev_points' point count, say) would grow a buffer per distinct value.
+WORKSPACE_KEYS = {
+    "voxelize": lambda m, n, t, max_voxels, nx, ny: (m, n, t, max_voxels, nx, ny),            # voxel_ws_ints (nz = 1)
+    "voxelize3d": lambda m, n, t, max_voxels, slots: (m, n, t, max_voxels, slots),            # ... with the table in place of the grid
+    "prepare_points": lambda m: (m,),                                                         # cloud_ws_ints
+    "sparse": lambda n, shape: (n,) + tuple(shape),                                           # sp_index_ints
+    "detect": lambda total: (total,),                                                         # det_ws_bytes
+    "bev_points": lambda n, nx, ny: (n, nx, ny),                                              # bev_points_ws_ints: 3 N nx ny
+    "sparse_train": lambda dtype, elements: (dtype, elements),                                # sized by its callers
+}
+
+
+def _workspace(what, family, dev, key, need, given, dtype=torch.int32, align=4):
+    """The scratch buffer of one operator call: the caller's `workspace=` after its checks, or the family's default.
+    A default is one buffer per (family, device, key), made on first use and kept for the life of the process, so that a captured
+    graph replays on the buffer it saw; one first made during a capture is cached like any other, which is why the replays and later
+    eager calls share it.  `key` must hold every argument the size depends on (tests pin this against the C formulas).  `need`, in
+    elements of `dtype`, is a number or - where the C library is to be asked only on a miss or for a given buffer - a callable.
+    A default starts on a WORKSPACE_ALIGN boundary whatever the family; a given one must be contiguous `dtype` on `dev`, hold `need`
+    elements and start on the family's own `align` bytes."""
+    if given is None:
+        cache = _WORKSPACES.setdefault(family, {})
+        ws = cache.get((dev,) + key)
+        if ws is None:
+            ws = cache[(dev,) + key] = torch.empty(need() if callable(need) else need, device=dev, dtype=dtype)
+            if ws.data_ptr() % WORKSPACE_ALIGN:       # a fresh torch block starts on 64 (host) / 512 (device) bytes: checked, not assumed
+                raise CobevtHipError("%s: the allocator returned a workspace off the %d-byte boundary" % (what, WORKSPACE_ALIGN))
+        return ws
+    need = need() if callable(need) else need
+    if given.dtype != dtype or not given.is_contiguous() or given.numel() < need or given.device != dev or given.data_ptr() % align:
+        raise CobevtHipError("%s: workspace= must be a contiguous%s %s tensor of at least %d elements on %s"
+                             % (what, ", %d-byte aligned" % align if align > given.element_size() else "", str(dtype).split(".")[-1], need, dev))
+    return given
+
+
+_TABLES = {}          # family -> {id(weight): (weakref, version, data_ptr, tables)}
+# a family's own dict inside the two registries, under the name its tests clear and look into (a test clears one family, never the registry)
+_SPARSE_WS, _SPARSE_TRAIN_WS, _CLOUD_WS = (_WORKSPACES.setdefault(f, {}) for f in ("sparse", "sparse_train", "prepare_points"))
+_SPARSE_TRAIN_WEIGHTS, _DECONV_TRAIN_WEIGHTS = (_TABLES.setdefault(f, {}) for f in ("sparse", "deconv"))
+
+
+def _lowered_tables(family, weight, lower):
+    """lower(weight.detach()) -> the operand tables of a training kernel, cached per weight OBJECT on its version counter and address:
+    hand over the nn.Parameter itself (a .detach() of it is a new object every time and would never hit).  An entry goes when its
+    weight does.  Never cached inside a graph capture: there the lowering is part of the graph, so a replay follows the optimiser."""
+    capturing = weight.is_cuda and torch.cuda.is_current_stream_capturing()
+    cache = _TABLES.setdefault(family, {})
+    key, stamp = id(weight), (weight._version, weight.data_ptr())
+    ent = cache.get(key)
+    if not capturing and ent is not None and ent[0]() is weight and ent[1:3] == stamp:
+        return ent[3]
+    tables = lower(weight.detach())
+    if not capturing:
+        cache[key] = (weakref.ref(weight, lambda _: cache.pop(key, None)),) + stamp + (tables,)
+    return tables
+
+
+def _points_offsets(what, points, point_offsets):
+    """the cloud operators' input: points (M, 4) contiguous fp32, point_offsets (N + 1,) int32 / int64 -> (offsets int32, N, M, device)"""
+    if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 4 or not points.is_contiguous():
+        raise CobevtHipError("%s: points must be contiguous fp32 (M, 4) as [x, y, z, intensity], got %s %s"
+                             % (what, points.dtype, tuple(points.shape)))
+    offs = _index_i32(point_offsets, what + ": point_offsets")
+    if offs.dim() != 1 or offs.shape[0] < 2:
+        raise CobevtHipError("%s: point_offsets must be (N + 1,) with N >= 1 agents, got %s" % (what, tuple(offs.shape)))
+    return offs, offs.shape[0] - 1, points.shape[0], points.device
+
+
+class BnTrainMode(object):
+    """How a train-mode entry normalises with the BatchNorm1d container `bn` (None: no norm), decided in one place.
+    .mode 0: batch statistics (bn.training, or a norm without running statistics); 1: the frozen running statistics, read only;
+    2: no norm.  frozen = True / False overrides the container's own choice.  BatchNorm1d(momentum=None) is refused in the constructor,
+    which callers run before anything is launched: the `kernels` ("pillar", "sparse") keep an exponential running average.  It reads no
+    buffer of a module in train(): it runs several times per layer and step.  .buffers() are the kernel's arguments, .written() follows
+    the launch."""
+    __slots__ = ("bn", "mode", "_written")
+
+    def __init__(self, bn, kernels, frozen=None):
+        self.bn, self.mode, self._written = bn, 2, ()
+        if bn is None:
+            return
+        if frozen is None:
+            frozen = not bn.training and bn.track_running_stats and bn.running_mean is not None
+        elif frozen and not (bn.track_running_stats and bn.running_mean is not None):
+            raise CobevtHipError("the %s training kernels: frozen statistics need a BatchNorm1d with running statistics" % kernels)
+        if not frozen and bn.track_running_stats and bn.momentum is None:
+            raise CobevtHipError("BatchNorm1d(momentum=None): the %s training kernels keep an exponential running average and need a "
+                                 "numeric momentum" % kernels)
+        self.mode = 1 if frozen else 0
+
+    def buffers(self):
+        """-> (running_mean, running_var, num_batches_tracked, eps, momentum): in mode 0 the three buffers the kernel updates where the
+        norm tracks them, in mode 1 the two it reads, None otherwise"""
+        bn = self.bn
+        if bn is None:
+            return None, None, None, 0.0, 0.0
+        rm = rv = nbt = None
+        if self.mode == 1 or (bn.track_running_stats and bn.running_mean is not None):
+            rm, rv = bn.running_mean, bn.running_var
+            if self.mode == 0:
+                nbt = bn.num_batches_tracked
+                self._written = (rm, rv, nbt)
+        return rm, rv, nbt, bn.eps, 0.0 if bn.momentum is None else bn.momentum
+
+    def written(self):
+        """after the launch: the buffers .buffers() handed out for updating were written through raw pointers, so bump their version
+        counters (eval plans folded from the running statistics rebuild, graph fingerprints move)"""
+        for t in self._written:
+            if t is not None:
+                torch.autograd.graph.increment_version(t)
+
+
+def pillar_args(what, vf, npts, coords, geom, use_absolute_xyz, with_distance, code, grid=None, record_len=None, max_cav=None,
+                num_agents=None):
+    """What every entry of the pillar front end takes, checked in one place, and the `dims` / `geom` vectors cobevt_pillar_vfe and
+    cobevt_pillar_train_* share: voxel_features (P, T <= 32, 4) contiguous fp32, voxel_num_points (P), voxel_coords (P, 4) int32 / int64,
+    geom = (voxel x, y, z, offset x, y, z), code = the output's dtype code.  grid None: the rows form (record_len is not used); else
+    (ny, nx) with record_len (int32 (B,) on the device) and max_cav, or with num_agents.
+    -> (npts, coords as int32, dims, geom, k, record_len | None, (n, b, l)): k = the decorated point's features, n = the bound on the
+    batch indices, (b, l) = the regrouped canvas' (B, max_cav), (0, 0) without record_len"""
+    _need_cuda(vf, npts, coords, record_len)
+    if vf.dtype != torch.float32 or vf.dim() != 3 or not vf.is_contiguous():
+        raise CobevtHipError("%s: voxel_features must be contiguous fp32 (P, T, 4)" % what)
+    p, t, f = vf.shape
     k = (4 if use_absolute_xyz else 1) + 6 + (1 if with_distance else 0)
     if f != 4 or t < 1 or t > PILLAR_MAX_POINTS:
-        raise CobevtHipError("pillar_vfe: F = 4 point features and 1 <= T <= %d points per pillar are supported, got F = %d, T = %d"
-                             % (PILLAR_MAX_POINTS, f, t))
+        raise CobevtHipError("%s: F = 4 point features and 1 <= T <= %d points per pillar are supported, got F = %d, T = %d"
+                             % (what, PILLAR_MAX_POINTS, f, t))
+    npts = _index_i32(npts, what + ": voxel_num_points", ())
+    coords = _index_i32(coords, what + ": voxel_coords", (4,))
+    if npts.shape[0] != p or coords.shape[0] != p:
+        raise CobevtHipError("%s: voxel_num_points (P) and voxel_coords (P, 4) must match voxel_features' P = %d" % (what, p))
+    if len(geom) != 6:
+        raise CobevtHipError("%s: geom = (voxel x, y, z, offset x, y, z)" % what)
+    n = b = l = ny = nx = 0
+    if grid is None:
+        record_len = None
+    else:
+        ny, nx = int(grid[0]), int(grid[1])
+        if record_len is not None:
+            if record_len.dtype != torch.int32 or record_len.dim() != 1 or not record_len.is_contiguous() or max_cav is None:
+                raise CobevtHipError("%s: record_len must be int32 (B,) on the device, with max_cav given" % what)
+            # with record_len the slot search already rejects n >= sum(record_len): no second bound unless the caller gives one (a
+            # sample with more than max_cav agents pushes later samples' agent indices past B * max_cav)
+            n, b, l = 0x7fffffff if num_agents is None else int(num_agents), record_len.shape[0], int(max_cav)
+        elif num_agents is None:
+            raise CobevtHipError("%s: num_agents (a host integer) is required without record_len" % what)
+        else:
+            n = int(num_agents)
+    dims = _ints([p, t, f, k, int(bool(use_absolute_xyz)), int(bool(with_distance)), code, int(grid is None), n, b, l, ny, nx])
+    return npts, coords, dims, (ctypes.c_float * 6)(*[float(v) for v in geom]), k, record_len, (n, b, l)
+
+
+def _pillar_call(voxel_features, args, w, shift, out, cav):
+    npts, coords, dims, g, k, record_len, _ = args
+    _need_cuda(w, shift, out)
     if w.dtype != torch.float32 or shift.dtype != torch.float32 or not w.is_contiguous() or not shift.is_contiguous() \
             or tuple(w.shape) != (k, PILLAR_CHANNELS) or tuple(shift.shape) != (PILLAR_CHANNELS,):
         raise CobevtHipError("pillar_vfe: folded weight / shift must be contiguous fp32 (%d, %d) / (%d)" % (k, PILLAR_CHANNELS, PILLAR_CHANNELS))
-    npts = _index_i32(voxel_num_points, "pillar_vfe: voxel_num_points", ())
-    coords = _index_i32(voxel_coords, "pillar_vfe: voxel_coords", (4,))
-    if npts.shape[0] != p or coords.shape[0] != p:
-        raise CobevtHipError("pillar_vfe: voxel_num_points (P) and voxel_coords (P, 4) must match voxel_features' P = %d" % p)
-    if len(geom) != 6:
-        raise CobevtHipError("pillar_vfe: geom = (voxel x, y, z, offset x, y, z)")
-    dims = _ints([p, t, f, k, int(bool(use_absolute_xyz)), int(bool(with_distance)), dcode(dtype), rows, n, b, max_cav, ny, nx])
-    g = (ctypes.c_float * 6)(*[float(v) for v in geom])
     _L.call("cobevt_pillar_vfe", _p(voxel_features), _p(npts), _p(coords), _p(w), _p(shift), _p(record_len), _p(out), _p(cav), dims, g,
             _stream())
 
@@ -1194,31 +1348,18 @@ def pillar_vfe_scatter(voxel_features, voxel_num_points, voxel_coords, w, shift,
     outside the grid or voxel_num_points <= 0 are skipped.  No host synchronisation."""
     ny, nx = int(grid[0]), int(grid[1])
     dev = voxel_features.device
-    if record_len is not None:
-        _need_cuda(record_len)
-        if record_len.dtype != torch.int32 or record_len.dim() != 1 or not record_len.is_contiguous() or max_cav is None:
-            raise CobevtHipError("pillar_vfe_scatter: record_len must be int32 (B,) on the device, with max_cav given")
-        b, l = record_len.shape[0], int(max_cav)
-        # with record_len the slot search already rejects n >= sum(record_len): no second bound unless the caller gives one (a sample
-        # with more than max_cav agents pushes later samples' agent indices past B * max_cav)
-        n = 0x7fffffff if num_agents is None else int(num_agents)
-        shape = (b, l, ny, nx, PILLAR_CHANNELS)
-        cav = torch.empty((b, l), device=dev, dtype=torch.float32)
-    else:
-        if num_agents is None:
-            raise CobevtHipError("pillar_vfe_scatter: num_agents (a host integer) is required without record_len")
-        b, l, n, cav = 0, 0, int(num_agents), None
-        shape = (n, ny, nx, PILLAR_CHANNELS)
+    args = pillar_args("pillar_vfe", voxel_features, voxel_num_points, voxel_coords, geom, use_absolute_xyz, with_distance, dcode(dtype),
+                       (ny, nx), record_len, max_cav, num_agents)
+    k, (n, b, l) = args[4], args[6]
+    shape = (b, l, ny, nx, PILLAR_CHANNELS) if record_len is not None else (n, ny, nx, PILLAR_CHANNELS)
     if n < 1 or ny < 1 or nx < 1 or (record_len is not None and (b < 1 or l < 1)):
         raise CobevtHipError("pillar_vfe_scatter: empty canvas %s" % (shape,))
-    _need_cuda(voxel_features)
+    cav = torch.empty((b, l), device=dev, dtype=torch.float32) if record_len is not None else None
     out = _canvas(out, shape, dtype, dev, "pillar_vfe_scatter")
-    k = (4 if use_absolute_xyz else 1) + 6 + (1 if with_distance else 0)
     pts = voxel_features.shape[0] * voxel_features.shape[1]
     cost = lambda: (2.0 * pts * k * PILLAR_CHANNELS, 16.0 * pts + out.numel() * out.element_size())         # noqa: E731
     with _timed("pillar_vfe|P%d T%d %dx%d" % (voxel_features.shape[0], voxel_features.shape[1], ny, nx), cost):
-        _pillar_call(voxel_features, voxel_num_points, voxel_coords, w, shift, geom, use_absolute_xyz, with_distance, out, dtype, 0,
-                     record_len, cav, n, b, l, ny, nx)
+        _pillar_call(voxel_features, args, w, shift, out, cav)
     return out, cav
 
 
@@ -1230,8 +1371,8 @@ def pillar_vfe_rows(voxel_features, voxel_num_points, voxel_coords, w, shift, ge
     if out.numel() == 0:
         dcode(dtype)
         return out
-    _pillar_call(voxel_features, voxel_num_points, voxel_coords, w, shift, geom, use_absolute_xyz, with_distance, out, dtype, 1,
-                 None, None, 0, 0, 0, 0, 0)
+    _pillar_call(voxel_features, pillar_args("pillar_vfe", voxel_features, voxel_num_points, voxel_coords, geom, use_absolute_xyz,
+                                             with_distance, dcode(dtype)), w, shift, out, None)
     return out
 
 
@@ -1265,13 +1406,7 @@ def voxel_grid_size(lidar_range, voxel_size):
 
 def voxelize_workspace_ints(num_points, num_agents, grid, max_points, max_voxels):
     """int32 elements of voxelize_points' workspace for M points of N agents on an (nx, ny, nz) grid (cobevt_voxelize_scratch)"""
-    dims = (ctypes.c_long * 9)(int(num_points), int(num_agents), int(max_points), int(max_voxels), int(grid[0]), int(grid[1]), int(grid[2]), 0, 0)
-    need = ctypes.c_long(0)
-    _L.call("cobevt_voxelize_scratch", dims, ctypes.byref(need))
-    return need.value
-
-
-_VOXEL_WS = {}        # (device, dims) -> the int32 workspace: one buffer per shape, so a captured graph replays on the buffers it saw
+    return _scratch("cobevt_voxelize_scratch", _longs(num_points, num_agents, max_points, max_voxels, grid[0], grid[1], grid[2], 0, 0))
 
 
 def voxelize_points(points, point_offsets, lidar_range, voxel_size, max_points=32, max_voxels=None, range_mask=False, ego_mask=False,
@@ -1297,42 +1432,29 @@ def voxelize_points(points, point_offsets, lidar_range, voxel_size, max_points=3
 def _voxelize(what, points, point_offsets, lidar_range, voxel_size, max_points, max_voxels, range_mask, ego_mask, out, workspace, slots):
     """voxelize_points (slots None: the dense tables, nz = 1) and voxelize_points_3d (slots: the hash table's entries, 0 = the default)"""
     _need_cuda(points, point_offsets, workspace)
-    if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 4 or not points.is_contiguous():
-        raise CobevtHipError("%s: points must be contiguous fp32 (M, 4) as [x, y, z, intensity], got %s %s"
-                             % (what, points.dtype, tuple(points.shape)))
-    offs = _index_i32(point_offsets, what + ": point_offsets")
-    if offs.dim() != 1 or offs.shape[0] < 2:
-        raise CobevtHipError("%s: point_offsets must be (N + 1,) with N >= 1 agents, got %s" % (what, tuple(offs.shape)))
+    offs, n, m, dev = _points_offsets(what, points, point_offsets)
     if max_voxels is None or int(max_voxels) < 1:
         raise CobevtHipError("%s: max_voxels (per agent, >= 1) is required" % what)
     nx, ny, nz = voxel_grid_size(lidar_range, voxel_size)
     if slots is None and nz != 1:
         raise CobevtHipError("voxelize_points: the pillar front end implements nz = 1 (one voxel over the height), got grid (%d, %d, %d)"
                              % (nx, ny, nz))
-    t, n, m, mv = int(max_points), offs.shape[0] - 1, points.shape[0], int(max_voxels)
+    t, mv = int(max_points), int(max_voxels)
     if t < 1 or t > PILLAR_MAX_POINTS:
         raise CobevtHipError("%s: 1 <= max_points <= T = %d points per voxel are supported, got %d" % (what, PILLAR_MAX_POINTS, t))
     if nx < 1 or ny < 1 or nz < 1:
         raise CobevtHipError("%s: empty grid (%d, %d, %d)" % (what, nx, ny, nz))
-    dev, pcap = points.device, n * mv
+    pcap = n * mv
     flags = (int(bool(range_mask)), int(bool(ego_mask)))
     if slots is None:
         dims = (ctypes.c_long * 9)(m, n, t, mv, nx, ny, nz, *flags)
-        key, ws_ints = (dev, m, n, t, mv, nx, ny), lambda: voxelize_workspace_ints(m, n, (nx, ny, nz), t, mv)       # noqa: E731
+        key, ws_ints = WORKSPACE_KEYS["voxelize"](m, n, t, mv, nx, ny), lambda: voxelize_workspace_ints(m, n, (nx, ny, nz), t, mv)       # noqa: E731
     else:
         dims = (ctypes.c_long * 10)(m, n, t, mv, nx, ny, nz, *flags, slots)
-        key, ws_ints = (dev, "3d", m, n, t, mv, slots), lambda: voxelize3d_workspace_ints(m, n, t, mv, slots)        # noqa: E731
+        key, ws_ints = WORKSPACE_KEYS["voxelize3d"](m, n, t, mv, slots), lambda: voxelize3d_workspace_ints(m, n, t, mv, slots)       # noqa: E731
     geom = (ctypes.c_float * 9)(*[float(v) for v in list(lidar_range) + list(voxel_size)])
-    if workspace is None:
-        workspace = _VOXEL_WS.get(key)
-        if workspace is None:
-            workspace = _VOXEL_WS[key] = torch.empty(ws_ints(), device=dev, dtype=torch.int32)
-    else:
-        need = ws_ints()
-        if workspace.dtype != torch.int32 or not workspace.is_contiguous() or workspace.numel() < need or workspace.device != dev:
-            raise CobevtHipError("%s: workspace= must be a contiguous int32 tensor of at least %d elements on %s" % (what, need, dev))
-        if slots is not None and workspace.data_ptr() % 8:
-            raise CobevtHipError("%s: workspace= must start on an 8-byte boundary (the table's 64-bit keys lead it)" % what)
+    # (the 3-D form's workspace starts with the hash table's 64-bit keys)
+    workspace = _workspace(what, "voxelize" if slots is None else "voxelize3d", dev, key, ws_ints, workspace, align=4 if slots is None else 8)
     shapes = [((pcap, t, 4), torch.float32), ((pcap, 4), torch.int32), ((pcap,), torch.int32), ((n,), torch.int32)]
     if out is None:
         out = [None] * 4
@@ -1365,10 +1487,7 @@ def voxelize3d_table_slots(num_points, table_slots=None):
 def voxelize3d_workspace_ints(num_points, num_agents, max_points, max_voxels, table_slots=None):
     """int32 elements of voxelize_points_3d's workspace for M points of N agents (cobevt_voxelize3d_scratch): it follows M, the table
     (table_slots, default: voxelize3d_table_slots) and N max_voxels, not the grid"""
-    dims = (ctypes.c_long * 10)(int(num_points), int(num_agents), int(max_points), int(max_voxels), 1, 1, 1, 0, 0, int(table_slots or 0))
-    need = ctypes.c_long(0)
-    _L.call("cobevt_voxelize3d_scratch", dims, ctypes.byref(need))
-    return need.value
+    return _scratch("cobevt_voxelize3d_scratch", _longs(num_points, num_agents, max_points, max_voxels, 1, 1, 1, 0, 0, table_slots or 0))
 
 
 def voxelize_points_3d(points, point_offsets, lidar_range, voxel_size, max_points=32, max_voxels=None, range_mask=False, ego_mask=False,
@@ -1392,16 +1511,12 @@ def voxelize_points_3d(points, point_offsets, lidar_range, voxel_size, max_point
 
 
 CLOUD_MAX_BOXES = 128      # ground-truth rows cobevt_prepare_points augments (one thread each of one workgroup)
-_CLOUD_WS = {}             # (device, M) -> prepare_points' int32 workspace, one per shape as for voxelize_points
 _WORLD_KEYS = ("flip_x", "flip_y", "rot", "scale")
 
 
 def prepare_points_workspace_ints(num_points, num_agents=1):
     """int32 elements of prepare_points' workspace for M points of N agents (cobevt_prepare_points_scratch)"""
-    dims = (ctypes.c_long * 10)(int(num_points), int(num_agents), 0, 0, 0, 0, 0, 0, 0, 0)
-    need = ctypes.c_long(0)
-    _L.call("cobevt_prepare_points_scratch", dims, ctypes.byref(need))
-    return need.value
+    return _scratch("cobevt_prepare_points_scratch", _longs(num_points, num_agents, 0, 0, 0, 0, 0, 0, 0, 0))
 
 
 def rotation_cos_sin(angle):
@@ -1440,13 +1555,7 @@ def prepare_points(points, point_offsets, transforms=None, *, order=None, ego_ma
     out = (points_out, out_offsets) to write into, points_out not overlapping points; workspace = an int32 tensor of at least prepare_points_workspace_ints(M) elements
     whose storage is 8-byte aligned (default: one cached per shape and device).  Bitwise reproducible."""
     _need_cuda(points, point_offsets, transforms, order, boxes, box_mask, workspace, *(out or ()))
-    if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 4 or not points.is_contiguous():
-        raise CobevtHipError("prepare_points: points must be contiguous fp32 (M, 4) as [x, y, z, intensity], got %s %s"
-                             % (points.dtype, tuple(points.shape)))
-    offs = _index_i32(point_offsets, "prepare_points: point_offsets")
-    if offs.dim() != 1 or offs.shape[0] < 2:
-        raise CobevtHipError("prepare_points: point_offsets must be (N + 1,) with N >= 1 agents, got %s" % (tuple(offs.shape),))
-    n, m, dev = offs.shape[0] - 1, points.shape[0], points.device
+    offs, n, m, dev = _points_offsets("prepare_points", points, point_offsets)
     if transforms is not None:
         if transforms.dtype not in (torch.float64, torch.float32) or tuple(transforms.shape) != (n, 4, 4):
             raise CobevtHipError("prepare_points: transforms must be fp64 (or fp32) (N, 4, 4) with N = %d agents, got %s %s"
@@ -1480,18 +1589,8 @@ def prepare_points(points, point_offsets, transforms=None, *, order=None, ego_ma
             raise CobevtHipError("prepare_points: box_mask must be contiguous (G,) with G = %d, got %s" % (g, tuple(box_mask.shape)))
         if g > CLOUD_MAX_BOXES:
             raise CobevtHipError("prepare_points: at most G = %d boxes are supported, got %d" % (CLOUD_MAX_BOXES, g))
-    if workspace is None:
-        key = (dev, m)
-        workspace = _CLOUD_WS.get(key)
-        if workspace is None:
-            need = prepare_points_workspace_ints(m, n)
-            workspace = _CLOUD_WS[key] = torch.empty((need + 1) // 2, device=dev, dtype=torch.int64).view(torch.int32)
-    else:
-        need = prepare_points_workspace_ints(m, n)
-        if workspace.dtype != torch.int32 or not workspace.is_contiguous() or workspace.numel() < need or workspace.device != dev \
-                or workspace.data_ptr() % 8:
-            raise CobevtHipError("prepare_points: workspace= must be a contiguous, 8-byte aligned int32 tensor of at least %d elements on %s"
-                                 % (need, dev))
+    workspace = _workspace("prepare_points", "prepare_points", dev, WORKSPACE_KEYS["prepare_points"](m),
+                           lambda: prepare_points_workspace_ints(m, n), workspace, align=8)
     if out is None:
         out = (None, None)
     elif len(out) != 2:
@@ -1516,7 +1615,6 @@ def prepare_points(points, point_offsets, transforms=None, *, order=None, ego_ma
 # ----------------------------------------------------------------------------------------------
 SPARSE_TILE_ROWS = 32      # output rows of one MFMA tile of cobevt_sparse_conv: the unit that skips absent taps
 SPARSE_BLOCK_ROWS = 128    # ... and of one workgroup (four tiles)
-_SPARSE_WS = {}            # (device, N, D, H, W) -> a level's int32 index workspace, one per shape as for voxelize_points
 
 
 def sparse_row_channels(channels, dtype):
@@ -1565,23 +1663,11 @@ def sparse_workspace_ints(batch_size, spatial_shape):
     """int32 elements of one level's index workspace - a bit per cell, a popcount prefix per 32-bit word, the scan's partials - for
     batch_size samples on the sparse shape (D, H, W) (cobevt_sparse_scratch)"""
     n, shape = _sparse_shape(batch_size, spatial_shape, "sparse_workspace_ints")
-    need = ctypes.c_long(0)
-    _L.call("cobevt_sparse_scratch", (ctypes.c_long * 4)(n, *shape), ctypes.byref(need))
-    return need.value
+    return _scratch("cobevt_sparse_scratch", _longs(n, *shape))
 
 
 def _sparse_ws(workspace, dev, n, shape, what):
-    if workspace is None:
-        key = (dev, n) + shape
-        workspace = _SPARSE_WS.get(key)
-        if workspace is None:
-            workspace = _SPARSE_WS[key] = torch.empty(sparse_workspace_ints(n, shape), device=dev, dtype=torch.int32)
-        return workspace
-    need = sparse_workspace_ints(n, shape)
-    if workspace.dtype != torch.int32 or not workspace.is_contiguous() or workspace.numel() < need or workspace.device != dev \
-            or workspace.data_ptr() % 16:
-        raise CobevtHipError("%s: workspace= must be a contiguous, 16-byte aligned int32 tensor of at least %d elements on %s" % (what, need, dev))
-    return workspace
+    return _workspace(what, "sparse", dev, WORKSPACE_KEYS["sparse"](n, shape), lambda: sparse_workspace_ints(n, shape), workspace, align=16)
 
 
 def sparse_out_shape(spatial_shape, kernel, stride, padding):
@@ -1779,33 +1865,24 @@ def sparse_dense(x):
 SPARSE_ROW_CHUNKS = 64     # row chunks of cobevt_sparse_conv_wgrad and of the BatchNorm sums: ceil(ceil(num[0] / 64) / 32) * 32 rows each
 SPARSE_TRAIN_PAIRS = ((8, 16),) + SparseConvPlan.PAIRS          # (input row in channels, Cout)
 SPARSE_STAT_DOUBLES = SPARSE_ROW_CHUNKS * 2 * 128              # the BatchNorm entries' partials (cobevt_sparse_train_scratch's second size)
-_SPARSE_TRAIN_WS = {}      # (device, dtype, elements) -> scratch
-_SPARSE_TRAIN_WEIGHTS = {}  # id(weight) -> (weakref, version, data_ptr, forward table, transposed table)
 
 
 def sparse_train_scratch(cin_pad, cout, taps):
     """(floats of the weight gradient's partials = SPARSE_ROW_CHUNKS x taps x Cout padded to 32 x input row, doubles of the
     BatchNorm entries' partials) - independent of every capacity and grid (cobevt_sparse_train_scratch)"""
-    sizes = (ctypes.c_long * 2)(0, 0)
-    _L.call("cobevt_sparse_train_scratch", (ctypes.c_long * 3)(int(cin_pad), int(cout), int(taps)), sizes)
-    return int(sizes[0]), int(sizes[1])
+    return _scratch("cobevt_sparse_train_scratch", _longs(cin_pad, cout, taps), n=2, packed=True)
 
 
 def _sparse_train_ws(dev, dtype, n):
-    key = (dev, dtype, n)
-    ws = _SPARSE_TRAIN_WS.get(key)
-    if ws is None:
-        ws = _SPARSE_TRAIN_WS[key] = torch.empty(n, device=dev, dtype=dtype)
-    return ws
+    """the partial sums of the training kernels (sparse and transposed convolution): one default buffer per dtype and element count"""
+    return _workspace("training scratch", "sparse_train", dev, WORKSPACE_KEYS["sparse_train"](dtype, n), n, None, dtype)
 
 
 def sparse_train_weights(weight):
     """The module weight (Cout, kz, ky, kx, Cin) fp32 -> the two operand tables of the training kernels, UNfolded: forward
     [taps][Cout padded to 32][input row] and transposed [taps][Cin padded to 32][Cout], tap = (kz KY + ky) KX + kx.  Lowered on the
-    device by torch ops - no host round trip per optimiser step, unlike SparseConvPlan - and cached per weight OBJECT on its version
-    counter and address: hand over the nn.Parameter itself (a .detach() of it is a new object every time and would never hit; the
-    detaching is done here).  An entry goes when its weight does.  Never cached inside a graph capture: there the lowering is part of
-    the graph, so a replay follows the optimiser."""
+    device by torch ops - no host round trip per optimiser step, unlike SparseConvPlan - and cached per weight object
+    (_lowered_tables: hand over the nn.Parameter itself, the detaching is done there)."""
     if weight.dim() != 5 or weight.dtype != torch.float32:
         raise CobevtHipError("sparse_train_weights: weight must be fp32 (Cout, kz, ky, kx, Cin), got %s %s" % (weight.dtype, tuple(weight.shape)))
     cout, kz, ky, kx, cin = (int(d) for d in weight.shape)
@@ -1813,21 +1890,16 @@ def sparse_train_weights(weight):
     if not ((cin <= 8 and cout == 16) or (cin, cout) in SparseConvPlan.PAIRS) or (kz, ky, kx) not in ((3, 3, 3), (3, 1, 1)):
         raise CobevtHipError("sparse_train_weights: %d -> %d channels, kernel %s; supported are <= 8 -> 16 and %s with kernel 3 or (3, 1, 1)"
                              % (cin, cout, (kz, ky, kx), ", ".join("%d -> %d" % p for p in SparseConvPlan.PAIRS)))
-    capturing = weight.is_cuda and torch.cuda.is_current_stream_capturing()
-    ent = _SPARSE_TRAIN_WEIGHTS.get(id(weight))
-    if not capturing and ent is not None and ent[0]() is weight and ent[1:3] == (weight._version, weight.data_ptr()):
-        return ent[3], ent[4]
     taps = kz * ky * kx
-    w = weight.detach()
-    fwd = torch.zeros((taps, (cout + 31) // 32 * 32, cin_pad), device=w.device, dtype=torch.float32)
-    fwd[:, :cout, :cin] = w.permute(1, 2, 3, 0, 4).reshape(taps, cout, cin)
-    tr = torch.zeros((taps, (cin_pad + 31) // 32 * 32, cout), device=w.device, dtype=torch.float32)
-    tr[:, :cin, :] = w.permute(1, 2, 3, 4, 0).reshape(taps, cin, cout)
-    if not capturing:
-        key = id(weight)
-        _SPARSE_TRAIN_WEIGHTS[key] = (weakref.ref(weight, lambda _, key=key: _SPARSE_TRAIN_WEIGHTS.pop(key, None)), weight._version,
-                                      weight.data_ptr(), fwd, tr)
-    return fwd, tr
+
+    def lower(w):
+        fwd = torch.zeros((taps, (cout + 31) // 32 * 32, cin_pad), device=w.device, dtype=torch.float32)
+        fwd[:, :cout, :cin] = w.permute(1, 2, 3, 0, 4).reshape(taps, cout, cin)
+        tr = torch.zeros((taps, (cin_pad + 31) // 32 * 32, cout), device=w.device, dtype=torch.float32)
+        tr[:, :cin, :] = w.permute(1, 2, 3, 4, 0).reshape(taps, cin, cout)
+        return fwd, tr
+
+    return _lowered_tables("sparse", weight, lower)
 
 
 def _sparse_geometry(kernel, stride, padding, subm, what):
@@ -1842,21 +1914,12 @@ def _sparse_geometry(kernel, stride, padding, subm, what):
     return k, s, p
 
 
-def _sparse_rows_f32(t, rows, channels, what):
-    if t is None or t.dtype != torch.float32 or t.dim() != 2 or not t.is_contiguous() or (channels is not None and t.shape[1] != channels) \
-            or (rows is not None and t.shape[0] != rows):
-        raise CobevtHipError("%s must be contiguous fp32 (%s, %s), got %s" % (what, "rows" if rows is None else rows,
-                                                                               "C" if channels is None else channels,
-                                                                               None if t is None else "%s %s" % (t.dtype, tuple(t.shape))))
-    return t
-
-
 def sparse_conv_raw(x, level, wgt, cout, kernel, stride, padding, subm):
     """z = conv(x): no BatchNorm, no ReLU (cobevt_sparse_conv_raw, the inference kernel with a plain-store epilogue).  x: the input
     SparseConvTensor with fp32 features (rows, input row) (row_map honoured), level: the output level (x itself for SubM), wgt: the
     forward table of sparse_train_weights -> z (level.capacity, cout) fp32, zeros at and past level.num[0]"""
     k, s, p = _sparse_geometry(kernel, stride, padding, subm, "sparse_conv_raw")
-    f = _sparse_rows_f32(x.features, None if x.row_map is not None else x.capacity, wgt.shape[2], "sparse_conv_raw: x.features")
+    f = _require_f32(x.features, "sparse_conv_raw: x.features", ("rows" if x.row_map is not None else x.capacity, wgt.shape[2]))
     _need_cuda(f, x.workspace, x.num, x.row_map, level.indices, level.num, wgt)
     cap, cin_pad = level.capacity, int(f.shape[1])
     z = torch.empty((cap, cout), device=f.device, dtype=torch.float32)
@@ -1873,21 +1936,15 @@ def sparse_bn_relu(z, num, gamma, beta, bn=None, frozen=False, eps=1e-3, momentu
     """BatchNorm1d + ReLU over the num[0] live rows of z (capacity, C) (cobevt_sparse_bn_relu) -> (stat (4, C) fp32 = [mean, rstd,
     scale, shift], y | None).  bn: the nn.BatchNorm1d whose eps / momentum hold and whose running statistics are updated in place
     (frozen: read instead, nothing updated); its buffers' version counters are bumped, so eval plans folded from them rebuild."""
-    _sparse_rows_f32(z, None, None, "sparse_bn_relu: z")
+    _require_f32(z, "sparse_bn_relu: z", ("rows", "C"))
     cap, c = (int(v) for v in z.shape)
     _need_cuda(z, num, gamma, beta)
-    rm = rv = nbt = None
+    mode = BnTrainMode(bn, "sparse", bool(frozen))
+    rm, rv, nbt, bn_eps, bn_momentum = mode.buffers()
     if bn is not None:
-        eps = bn.eps
-        if bn.track_running_stats and bn.running_mean is not None:
-            rm, rv, nbt = bn.running_mean, bn.running_var, bn.num_batches_tracked
-        if frozen and rm is None:
-            raise CobevtHipError("sparse_bn_relu: frozen statistics need a BatchNorm1d with running statistics")
-        if not frozen and rm is not None:
-            if bn.momentum is None:
-                raise CobevtHipError("BatchNorm1d(momentum=None): the sparse training kernels keep an exponential running average and need a "
-                                     "numeric momentum")
-            momentum = bn.momentum
+        eps = bn_eps
+        if rm is not None and not frozen:
+            momentum = bn_momentum
         _need_cuda(rm, rv, nbt)
     g, b = gamma.detach(), beta.detach()
     for t, what in ((g, "gamma"), (b, "beta"), (rm, "running_mean"), (rv, "running_var")):
@@ -1901,22 +1958,19 @@ def sparse_bn_relu(z, num, gamma, beta, bn=None, frozen=False, eps=1e-3, momentu
     y = torch.empty_like(z) if want_y else None
     dims = (ctypes.c_long * 4)(cap, c, 1 if frozen else 0, doubles)
     with _timed("sparse_bn_relu|C%d" % c, lambda: (4.0 * cap * c, 4.0 * cap * c * (3 if want_y else 1))):
-        _L.call("cobevt_sparse_bn_relu", _p(z), _p(num), _p(g), _p(b), _p(rm), _p(rv), _p(None if frozen else nbt), _p(stat), _p(partial), _p(y), dims,
+        _L.call("cobevt_sparse_bn_relu", _p(z), _p(num), _p(g), _p(b), _p(rm), _p(rv), _p(nbt), _p(stat), _p(partial), _p(y), dims,
                 ctypes.c_float(eps), ctypes.c_float(momentum), _stream(), variant="")
-    if not frozen and rm is not None:
-        for t in (rm, rv, nbt):                # written through raw pointers: plans folded from the running statistics must rebuild
-            if t is not None:
-                torch.autograd.graph.increment_version(t)
+    mode.written()
     return stat, y
 
 
 def sparse_bn_relu_bwd(dy, y, z, num, gamma, stat, frozen=False):
     """The backward of sparse_bn_relu (cobevt_sparse_bn_relu_bwd) -> (dz (capacity, C), dgamma (C), dbeta (C)); dy at and past num[0]
     is never read, dz there is 0.  frozen: the statistics were constants (no / n terms)."""
-    _sparse_rows_f32(z, None, None, "sparse_bn_relu_bwd: z")
+    _require_f32(z, "sparse_bn_relu_bwd: z", ("rows", "C"))
     cap, c = (int(v) for v in z.shape)
-    _sparse_rows_f32(dy, cap, c, "sparse_bn_relu_bwd: dy")
-    _sparse_rows_f32(y, cap, c, "sparse_bn_relu_bwd: y")
+    _require_f32(dy, "sparse_bn_relu_bwd: dy", (cap, c))
+    _require_f32(y, "sparse_bn_relu_bwd: y", (cap, c))
     _need_cuda(dy, y, z, num, gamma, stat)
     doubles = SPARSE_STAT_DOUBLES
     partial = _sparse_train_ws(z.device, torch.float64, doubles)
@@ -1937,7 +1991,7 @@ def sparse_conv_dgrad(dz, x, level, wgt_t, cin, kernel, stride, padding, subm):
     the input rows: a row without a contributing output gets exactly 0, rows at and past x.num[0] too."""
     k, s, p = _sparse_geometry(kernel, stride, padding, subm, "sparse_conv_dgrad")
     cout = int(wgt_t.shape[2])
-    _sparse_rows_f32(dz, level.capacity, cout, "sparse_conv_dgrad: dz")
+    _require_f32(dz, "sparse_conv_dgrad: dz", (level.capacity, cout))
     if x.row_map is not None:
         raise CobevtHipError("sparse_conv_dgrad: no gradient is offered through a row_map (the input level of the backbone)")
     _need_cuda(dz, level.workspace, level.num, x.indices, x.num, wgt_t)
@@ -1956,9 +2010,9 @@ def sparse_conv_wgrad(x, level, dz, cin, kernel, stride, padding, subm):
     (row_map honoured), dz (level.capacity, Cout) -> dW (Cout, kz, ky, kx, cin) fp32, the module's layout.  No floating-point atomics:
     SPARSE_ROW_CHUNKS row chunks sized from level.num[0] on the device, added in chunk order in fp64."""
     k, s, p = _sparse_geometry(kernel, stride, padding, subm, "sparse_conv_wgrad")
-    f = _sparse_rows_f32(x.features, None if x.row_map is not None else x.capacity, None, "sparse_conv_wgrad: x.features")
+    f = _require_f32(x.features, "sparse_conv_wgrad: x.features", ("rows" if x.row_map is not None else x.capacity, "C"))
     cin_pad, cout = int(f.shape[1]), int(dz.shape[1]) if dz is not None and dz.dim() == 2 else -1
-    _sparse_rows_f32(dz, level.capacity, None, "sparse_conv_wgrad: dz")
+    _require_f32(dz, "sparse_conv_wgrad: dz", (level.capacity, "C"))
     if (cin_pad, cout) not in SPARSE_TRAIN_PAIRS or not 1 <= cin <= cin_pad or (cin_pad > 8 and cin != cin_pad):
         raise CobevtHipError("sparse_conv_wgrad: %d (row %d) -> %d channels; supported are <= 8 -> 16 and %s"
                              % (cin, cin_pad, cout, ", ".join("%d -> %d" % q for q in SparseConvPlan.PAIRS)))
@@ -2133,26 +2187,16 @@ def decode_bev(labels_i32, num_classes, out=None):
 
 DETECT_TOP = 1000          # box_utils.nms_rotated's `top`: the fixed capacity of the detection outputs
 DETECT_MAX_CAV = 16
-_DETECT_WS = {}            # (device, total anchors) -> the workspace: one buffer per size, so a captured graph replays on the buffer it saw
 
 
 def detect_workspace_bytes(total_anchors):
     """bytes of detect_post_process' / nms_rotated's workspace for `total_anchors` candidates (cobevt_detect_scratch)"""
-    need = ctypes.c_long(0)
-    _L.call("cobevt_detect_scratch", int(total_anchors), ctypes.byref(need))
-    return need.value
+    return _scratch("cobevt_detect_scratch", int(total_anchors))
 
 
 def _detect_workspace(workspace, total, dev, what):
-    need = detect_workspace_bytes(total)
-    if workspace is None:
-        workspace = _DETECT_WS.get((dev, total))
-        if workspace is None:
-            workspace = _DETECT_WS[(dev, total)] = torch.empty((need + 7) // 8, device=dev, dtype=torch.int64)
-        return workspace
-    if workspace.dtype != torch.int64 or not workspace.is_contiguous() or workspace.numel() * 8 < need or workspace.device != dev:
-        raise CobevtHipError("%s: workspace= must be a contiguous int64 tensor of at least %d elements on %s" % (what, (need + 7) // 8, dev))
-    return workspace
+    """(asked for its size on every call, in bytes; the buffer is int64 words)"""
+    return _workspace(what, "detect", dev, WORKSPACE_KEYS["detect"](total), (detect_workspace_bytes(total) + 7) // 8, workspace, torch.int64, 8)
 
 
 def _detect_out(out, dev, what):
@@ -2164,8 +2208,9 @@ def _detect_out(out, dev, what):
     return [_canvas(o, sh, d, dev, what) for o, (sh, d) in zip(out, shapes)]
 
 
-def _f32_dev(t, dev, what, shape=None):
-    """a contiguous fp32 tensor on `dev` from a tensor or an array (an anchor box is numpy float64 in the reference)"""
+def _to_f32(t, dev, what, shape=None):
+    """a contiguous fp32 tensor on `dev` CONVERTED from a tensor or an array (an anchor box is numpy float64 in the reference);
+    _require_f32 is the form that refuses instead"""
     t = torch.as_tensor(t)
     if not t.is_floating_point():
         raise CobevtHipError("%s must be floating point, got %s" % (what, t.dtype))
@@ -2196,7 +2241,7 @@ def delta_to_boxes3d(deltas, anchors):
     device, channel a * 7 + k = delta k of anchor a; anchors (H, W, A, 7) (tensor or array, any float type) -> boxes3d (N, H W A, 7)
     fp32 in (h, w, a) order: x, y = delta * sqrt(a4^2 + a5^2) + anchor, z = delta * a3 + anchor, sizes exp(delta) * anchor, yaw added."""
     _need_cuda(deltas)
-    anc = _f32_dev(anchors, deltas.device, "delta_to_boxes3d: anchors")
+    anc = _to_f32(anchors, deltas.device, "delta_to_boxes3d: anchors")
     n, h, w, a = _head_maps(None, deltas, anc, "delta_to_boxes3d")
     out = torch.empty((n, h * w * a, 7), device=deltas.device, dtype=torch.float32)
     _L.call("cobevt_delta_to_boxes3d", _p(deltas), _p(anc), _p(out), n, h, w, a, _stream())
@@ -2231,7 +2276,7 @@ def nms_rotated_device(boxes, scores, threshold, out=None, workspace=None):
         raise CobevtHipError("nms_rotated: boxes must be floating point (N, 8, 3) or (N, 4, 2), got %s %s" % (boxes.dtype, tuple(boxes.shape)))
     dev, n = boxes.device, boxes.shape[0]
     b = boxes.to(torch.float32).contiguous()
-    sc = _f32_dev(scores, dev, "nms_rotated: scores", (n,))
+    sc = _to_f32(scores, dev, "nms_rotated: scores", (n,))
     ws = _detect_workspace(workspace, n, dev, "nms_rotated")
     ob, osc, oi, oc = _detect_out(out, dev, "nms_rotated")
     _L.call("cobevt_nms_rotated", _p(b) if n else None, _p(sc) if n else None, n, b.shape[1] * b.shape[2], float(threshold), _p(ob),
@@ -2271,9 +2316,9 @@ def detect_post_process(cavs, score_threshold, nms_thresh, order, out=None, work
         dev = psm.device if dev is None else dev
         if psm.device != dev or rm.device != dev:
             raise CobevtHipError("detect_post_process: cav %d is on another device" % c)
-        anc = _f32_dev(anchors, dev, "detect_post_process: anchors of cav %d" % c)
+        anc = _to_f32(anchors, dev, "detect_post_process: anchors of cav %d" % c)
         _, h, w, a = _head_maps(psm, rm, anc, "detect_post_process: cav %d" % c, batch=1)
-        mats.append(_f32_dev(mat, dev, "detect_post_process: transformation_matrix of cav %d" % c, (4, 4)))
+        mats.append(_to_f32(mat, dev, "detect_post_process: transformation_matrix of cav %d" % c, (4, 4)))
         keep.append((psm, rm, anc))
         dims += [h, w, a]
         total += h * w * a
@@ -2297,7 +2342,6 @@ DETECT_MAX_GT = 128        # ground-truth slots per sample cobevt_detect_targets
 # ----------------------------------------------------------------------------------------------
 BEV_TARGET_MEAN = (0.008, 0.001, 0.202, 0.2, 0.43, 1.368)          # lidar_bev_postprocessor.py :24-25
 BEV_TARGET_STD_DEV = (0.866, 0.5, 0.954, 0.668, 0.09, 0.111)
-_BEV_WS = {}               # (device, dims) -> bev_points' int32 workspace, one per shape as for voxelize_points
 
 
 def _bev_shape(shape, last, what):
@@ -2320,10 +2364,7 @@ def _bev_params(origin_xy, res, downsample_rate, target_mean, target_std_dev, wh
 
 def bev_points_workspace_ints(num_points, num_agents, input_shape):
     """int32 elements of bev_points' workspace for M points of N agents on an (nx, ny, C) map (cobevt_bev_points_scratch)"""
-    dims = (ctypes.c_long * 8)(int(num_points), int(num_agents), int(input_shape[0]), int(input_shape[1]), int(input_shape[2]), 0, 0, 0)
-    need = ctypes.c_long(0)
-    _L.call("cobevt_bev_points_scratch", dims, ctypes.byref(need))
-    return need.value
+    return _scratch("cobevt_bev_points_scratch", _longs(num_points, num_agents, input_shape[0], input_shape[1], input_shape[2], 0, 0, 0))
 
 
 def bev_points(points, point_offsets, lidar_range, origin, res, input_shape, range_mask=False, ego_mask=False, channels_last=False,
@@ -2338,32 +2379,18 @@ def bev_points(points, point_offsets, lidar_range, origin, res, input_shape, ran
     out = the tensor to write into (the call clears it); workspace = an int32 tensor of at least bev_points_workspace_ints(...)
     elements whose storage is 8-byte aligned (default: one cached per shape and device)."""
     _need_cuda(points, point_offsets, out, workspace)
-    if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 4 or not points.is_contiguous():
-        raise CobevtHipError("bev_points: points must be contiguous fp32 (M, 4) as [x, y, z, intensity], got %s %s"
-                             % (points.dtype, tuple(points.shape)))
-    offs = _index_i32(point_offsets, "bev_points: point_offsets")
-    if offs.dim() != 1 or offs.shape[0] < 2:
-        raise CobevtHipError("bev_points: point_offsets must be (N + 1,) with N >= 1 agents, got %s" % (tuple(offs.shape),))
+    offs, n, m, dev = _points_offsets("bev_points", points, point_offsets)
     nx, ny, c = _bev_shape(input_shape, None, "bev_points: input_shape")
     rng, org = [float(v) for v in lidar_range], [float(v) for v in origin]
     if len(rng) != 6 or len(org) != 3 or not all(np.isfinite(rng + org)) or not (float(res) > 0.0 and np.isfinite(float(res))):
         raise CobevtHipError("bev_points: lidar_range = [x0, y0, z0, x1, y1, z1], origin = (L1, W1, H1) and res > 0, got %r / %r / %r"
                              % (list(lidar_range), list(origin), res))
-    n, m, dev = offs.shape[0] - 1, points.shape[0], points.device
     if n * nx * ny * c > 0x7fffffff // 4:
         raise CobevtHipError("bev_points: %d agents of %d x %d x %d cells are more than the operator indexes" % (n, nx, ny, c))
     dims = (ctypes.c_long * 8)(m, n, nx, ny, c, int(bool(range_mask)), int(bool(ego_mask)), int(bool(channels_last)))
     geom = (ctypes.c_double * 10)(*(rng + org + [float(res)]))
-    need = bev_points_workspace_ints(m, n, (nx, ny, c))
-    if workspace is None:
-        key = (dev, n, nx, ny)
-        workspace = _BEV_WS.get(key)
-        if workspace is None:
-            workspace = _BEV_WS[key] = torch.empty((need + 1) // 2, device=dev, dtype=torch.int64).view(torch.int32)
-    elif workspace.dtype != torch.int32 or not workspace.is_contiguous() or workspace.numel() < need or workspace.device != dev \
-            or workspace.data_ptr() % 8:
-        raise CobevtHipError("bev_points: workspace= must be a contiguous, 8-byte aligned int32 tensor of at least %d elements on %s"
-                             % (need, dev))
+    workspace = _workspace("bev_points", "bev_points", dev, WORKSPACE_KEYS["bev_points"](n, nx, ny),
+                           bev_points_workspace_ints(m, n, (nx, ny, c)), workspace, align=8)      # (asked for its size on every call)
     bev = _canvas(out, (n, nx, ny, c) if channels_last else (n, c, nx, ny), torch.float32, dev, "bev_points")
     with _timed("bev_points|M%d N%d %dx%dx%d" % (m, n, nx, ny, c), lambda: (0.0, 16.0 * m + 12.0 * m + 4.0 * n * nx * ny * (c + 6))):
         _L.call("cobevt_bev_points", _p(points) if m else None, _p(offs), _p(bev), _p(workspace), dims, geom, _stream())
@@ -2386,8 +2413,8 @@ def bev_labels(gt_box_center, mask, origin_xy, res, downsample_rate, label_shape
         raise CobevtHipError("bev_labels: at most %d ground-truth slots per sample are supported, got %d" % (DETECT_MAX_GT, g))
     if b < 1 or b > 65535 or b * lx * ly > 0x7fffffff // 8:
         raise CobevtHipError("bev_labels: %d samples of %d x %d pixels are outside what the operator indexes" % (b, lx, ly))
-    _dev_f32(gt_box_center, "bev_labels: gt_box_center")
-    _dev_f32(mask, "bev_labels: mask", (b, g))
+    _require_f32(gt_box_center, "bev_labels: gt_box_center")
+    _require_f32(mask, "bev_labels: mask", (b, g))
     params = _bev_params(origin_xy, res, downsample_rate, target_mean, target_std_dev, "bev_labels")
     dev = gt_box_center.device
     shapes = [((b, 7, lx, ly), torch.float32), ((b, g, 4, 2), torch.float32), ((b,), torch.int32)]
@@ -2445,7 +2472,7 @@ def bev_post_process(cavs, origin_xy, res, downsample_rate, score_threshold, nms
         if cls.dtype != torch.float32 or tuple(cls.shape) != (1, 1, lx, ly) or not cls.is_contiguous():
             raise CobevtHipError("bev_post_process: cls of cav %d must be contiguous fp32 %s, got %s %s"
                                  % (c, (1, 1, lx, ly), cls.dtype, tuple(cls.shape)))
-        mats.append(_f32_dev(mat, dev, "bev_post_process: transformation_matrix of cav %d" % c, (4, 4)))
+        mats.append(_to_f32(mat, dev, "bev_post_process: transformation_matrix of cav %d" % c, (4, 4)))
         keep.append((cls, reg))
         dims += [lx, ly]
         total += lx * ly
@@ -2462,13 +2489,20 @@ def bev_post_process(cavs, origin_xy, res, downsample_rate, score_threshold, nms
     return ob, osc, oi, oc
 
 
-def _dev_f32(t, what, shape=None, dims=None):
-    """a contiguous fp32 device tensor as it stands, or an error: the target / loss operators convert nothing"""
+def _require_f32(t, what, shape=None, dims=None, nonempty=False):
+    """a contiguous fp32 device tensor as it stands, or an error: nothing is converted (_to_f32 is the form that converts).  shape:
+    the sizes, a name standing for any size - ("rows", 16); dims: the rank alone"""
     _need_cuda(t)
-    if t.dtype != torch.float32 or not t.is_contiguous() or (dims is not None and t.dim() != dims) or \
-            (shape is not None and tuple(t.shape) != tuple(shape)):
-        raise CobevtHipError("%s must be contiguous fp32%s, got %s %s"
-                             % (what, "" if shape is None else " %s" % (tuple(shape),), t.dtype, tuple(t.shape)))
+    ok = t is not None and t.dtype == torch.float32 and t.is_contiguous() and (dims is None or t.dim() == dims) \
+        and (shape is None or t.dim() == len(shape)) and not (nonempty and min(t.shape) < 1)
+    if ok and shape is not None:
+        for want, got in zip(shape, t.shape):       # (a plain loop: this runs some eight times per layer of a training step)
+            if want != got and not isinstance(want, str):
+                ok = False
+    if not ok:
+        raise CobevtHipError("%s must be contiguous%s fp32%s, got %s"
+                             % (what, " non-empty" if nonempty else "", "" if shape is None else " (%s)" % ", ".join(str(v) for v in shape),
+                                None if t is None else "%s %s" % (t.dtype, tuple(t.shape))))
     return t
 
 
@@ -2478,7 +2512,7 @@ def boxes_standup(boxes):
     product and sum a separately rounded fp32 operation (csrc/detect_targets.hip)."""
     if boxes.dim() != 2 or boxes.shape[1] != 7:
         raise CobevtHipError("boxes_standup: boxes must be (n, 7), got %s" % (tuple(boxes.shape),))
-    _dev_f32(boxes, "boxes_standup: boxes")
+    _require_f32(boxes, "boxes_standup: boxes")
     out = torch.empty((boxes.shape[0], 4), device=boxes.device, dtype=torch.float32)
     _L.call("cobevt_boxes_standup", _p(boxes), _p(out), boxes.shape[0], _stream())
     return out
@@ -2502,11 +2536,11 @@ def detect_targets(anchors, anchor_standup, gt_boxes, gt_standup, mask, pos_thre
         raise CobevtHipError("detect_targets: at most %d ground-truth slots per sample are supported, got %d" % (DETECT_MAX_GT, g))
     if b < 1 or m < 1 or m * b > 0x7fffffff // 8:
         raise CobevtHipError("detect_targets: %d samples of %d anchors are outside what the operator indexes" % (b, m))
-    _dev_f32(anchors, "detect_targets: anchors")
-    _dev_f32(anchor_standup, "detect_targets: anchor_standup", (m, 4))
-    _dev_f32(gt_boxes, "detect_targets: gt_boxes")
-    _dev_f32(gt_standup, "detect_targets: gt_standup", (b, g, 4))
-    _dev_f32(mask, "detect_targets: mask", (b, g))
+    _require_f32(anchors, "detect_targets: anchors")
+    _require_f32(anchor_standup, "detect_targets: anchor_standup", (m, 4))
+    _require_f32(gt_boxes, "detect_targets: gt_boxes")
+    _require_f32(gt_standup, "detect_targets: gt_standup", (b, g, 4))
+    _require_f32(mask, "detect_targets: mask", (b, g))
     dev = anchors.device
     pos = torch.empty((b, h, w, a), device=dev, dtype=torch.float32)
     neg = torch.empty((b, h, w, a), device=dev, dtype=torch.float32)
@@ -2526,13 +2560,13 @@ def pointpillar_loss(psm, rm, pos_equal_one, targets, cls_weight, reg, num_pos=N
     fp32 on the device; num_pos (B,) int32 from detect_targets, or None to have the positives counted.
     -> (loss (3,) fp32 = [total, conf_loss, reg_loss], d total / d psm or None, d total / d rm or None).  fp32 per element, fp64 sums
     in a fixed order: bitwise reproducible, and the same bits with num_pos given or counted."""
-    _dev_f32(psm, "pointpillar_loss: psm", dims=4)
+    _require_f32(psm, "pointpillar_loss: psm", dims=4)
     b, a, h, w = psm.shape
     if b < 1 or a < 1 or h < 1 or w < 1 or b * a * h * w > 0x7fffffff // 8:
         raise CobevtHipError("pointpillar_loss: psm %s is outside what the operator indexes" % (tuple(psm.shape),))
-    _dev_f32(rm, "pointpillar_loss: rm", (b, 7 * a, h, w))
-    _dev_f32(pos_equal_one, "pointpillar_loss: pos_equal_one", (b, h, w, a))
-    _dev_f32(targets, "pointpillar_loss: targets", (b, h, w, 7 * a))
+    _require_f32(rm, "pointpillar_loss: rm", (b, 7 * a, h, w))
+    _require_f32(pos_equal_one, "pointpillar_loss: pos_equal_one", (b, h, w, a))
+    _require_f32(targets, "pointpillar_loss: targets", (b, h, w, 7 * a))
     if num_pos is not None:
         _need_cuda(num_pos)
         if num_pos.dtype != torch.int32 or tuple(num_pos.shape) != (b,) or not num_pos.is_contiguous():
@@ -2690,9 +2724,6 @@ def att_fuse_bwd(x, record_len, dout):
 
 # ---------------------------------------------------------------------------------------------- training of the transposed convolution
 # fp32 only, the native library (exact fp32 products).  Scratch buffers are cached per size like the sparse path's.
-_DECONV_TRAIN_WEIGHTS = {}  # id(weight) -> (weakref, version, data_ptr, forward table, input-gradient rows)
-
-
 def _deconv_geometry(cin, cout, s, what):
     if not 1 <= s <= DECONV_MAX_STRIDE:
         raise CobevtHipError("%s: stride %d is outside 1 .. %d" % (what, s, DECONV_MAX_STRIDE))
@@ -2707,42 +2738,28 @@ def deconv_train_weights(weight):
     tables of its training kernels: forward [s s Cout][Kpad] with row (dy s + dx) Cout + co = weight[:, co, dy, dx] (DeconvPlan's
     layout without a BatchNorm) and input-gradient rows [Cin][Kpad'] with k = (dy s + dx) Cout + co (the implicit-GEMM rows of the
     weight read as (out = Cin, in = Cout, s, s)); both padded with zero columns to a multiple of 16.  Device permutes - no host round
-    trip per optimiser step, unlike DeconvPlan - cached per weight OBJECT on its version counter and address (hand over the
-    nn.Parameter itself); an entry goes when its weight does.  Never cached inside a graph capture."""
+    trip per optimiser step, unlike DeconvPlan - cached per weight object (_lowered_tables: hand over the nn.Parameter itself)."""
     if weight.dim() != 4 or weight.shape[2] != weight.shape[3] or weight.dtype != torch.float32:
         raise CobevtHipError("deconv_train_weights: weight must be fp32 (Cin, Cout, s, s), got %s %s" % (weight.dtype, tuple(weight.shape)))
     cin, cout, s, _ = (int(d) for d in weight.shape)
     _deconv_geometry(cin, cout, s, "deconv_train_weights")
-    capturing = weight.is_cuda and torch.cuda.is_current_stream_capturing()
-    ent = _DECONV_TRAIN_WEIGHTS.get(id(weight))
-    if not capturing and ent is not None and ent[0]() is weight and ent[1:3] == (weight._version, weight.data_ptr()):
-        return ent[3], ent[4]
-    w = weight.detach()
     kf, kd = (cin + 15) // 16 * 16, (s * s * cout + 15) // 16 * 16
-    fwd = torch.zeros((s * s * cout, kf), device=w.device, dtype=torch.float32)
-    fwd[:, :cin] = w.permute(2, 3, 1, 0).reshape(s * s * cout, cin)
-    rows = torch.zeros((cin, kd), device=w.device, dtype=torch.float32)
-    rows[:, :s * s * cout] = w.permute(0, 2, 3, 1).reshape(cin, s * s * cout)
-    if not capturing:
-        key = id(weight)
-        _DECONV_TRAIN_WEIGHTS[key] = (weakref.ref(weight, lambda _, key=key: _DECONV_TRAIN_WEIGHTS.pop(key, None)), weight._version,
-                                      weight.data_ptr(), fwd, rows)
-    return fwd, rows
 
+    def lower(w):
+        fwd = torch.zeros((s * s * cout, kf), device=w.device, dtype=torch.float32)
+        fwd[:, :cin] = w.permute(2, 3, 1, 0).reshape(s * s * cout, cin)
+        rows = torch.zeros((cin, kd), device=w.device, dtype=torch.float32)
+        rows[:, :s * s * cout] = w.permute(0, 2, 3, 1).reshape(cin, s * s * cout)
+        return fwd, rows
 
-def _deconv_map_f32(t, shape, what):
-    if t is None or t.dtype != torch.float32 or t.dim() != 4 or not t.is_contiguous() or min(t.shape) < 1 \
-            or (shape is not None and tuple(t.shape) != tuple(shape)):
-        raise CobevtHipError("%s must be a contiguous non-empty fp32 %s tensor, got %s" % (
-            what, "(N, H, W, C)" if shape is None else tuple(shape), None if t is None else "%s %s" % (t.dtype, tuple(t.shape))))
-    return t
+    return _lowered_tables("deconv", weight, lower)
 
 
 def deconv_raw(x, wgt, cout, s):
     """z = ConvTranspose2d(kernel = stride = s)(x) without BatchNorm or activation: x (N, H, W, Cin) contiguous fp32, wgt the forward
     table of deconv_train_weights -> z (N, sH, sW, Cout) fp32.  One cobevt_deconv_nhwc launch of the native library (exact fp32) with a
     zero shift, act = 0, c_off = 0."""
-    _deconv_map_f32(x, None, "deconv_raw: x")
+    _require_f32(x, "deconv_raw: x", ("N", "H", "W", "C"), nonempty=True)
     n, h, w, cin = (int(d) for d in x.shape)
     cout, s = int(cout), int(s)
     _deconv_geometry(cin, cout, s, "deconv_raw")
@@ -2787,14 +2804,14 @@ def deconv_wgrad_chunks(n, h, w, cin, cout, s):
 def deconv_wgrad(x, dz, s):
     """The weight gradient of deconv_raw (cobevt_deconv_wgrad, two launches): x (N, H, W, Cin), dz (N, sH, sW, Cout) contiguous fp32 ->
     dW (Cin, Cout, s, s) fp32, the ConvTranspose2d layout, written.  No floating-point atomics: pixel chunks added in order in fp64."""
-    _deconv_map_f32(x, None, "deconv_wgrad: x")
+    _require_f32(x, "deconv_wgrad: x", ("N", "H", "W", "C"), nonempty=True)
     n, h, w, cin = (int(d) for d in x.shape)
     s = int(s)
     if dz is None or dz.dim() != 4:
         raise CobevtHipError("deconv_wgrad: dz must be a 4-D tensor")
     cout = int(dz.shape[3])
     _deconv_geometry(cin, cout, s, "deconv_wgrad")
-    _deconv_map_f32(dz, (n, s * h, s * w, cout), "deconv_wgrad: dz")
+    _require_f32(dz, "deconv_wgrad: dz", (n, s * h, s * w, cout), nonempty=True)
     if n * h * w * s * s >= 2 ** 31 - 1:
         raise CobevtHipError("deconv_wgrad: %d pixels of dz overflow the kernel's 32-bit pixel index" % (n * h * w * s * s))
     _need_cuda(x, dz)

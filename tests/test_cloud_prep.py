@@ -193,3 +193,8 @@ def test_rotation_cos_sin_is_the_reference_chain():
     assert ops.rotation_cos_sin(a) == (float(torch.cos(t)[0]), float(torch.sin(t)[0]))
     c, s = ops.rotation_cos_sin(a)
     assert np.float32(c) == c and np.float32(s) == s
+
+
+def test_the_workspace_size_follows_its_key():
+    """the default workspace is cached on M alone: the agent count, which the key leaves out, must not move the size"""
+    assert ops.prepare_points_workspace_ints(1000, 1) == ops.prepare_points_workspace_ints(1000, 7) == ops.prepare_points_workspace_ints(1000)

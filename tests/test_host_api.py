@@ -498,3 +498,110 @@ def test_projection_shortcut_fragment_table_layout():
         for chunk in range(nextra):
             got = t[tile, nmain + chunk, :, :, r, :].reshape(64)
             assert torch.equal(got, wdr[cout, chunk * 64:(chunk + 1) * 64, 0, 0])
+
+
+# ---------------------------------------------------------------------------------------------- workspaces and lowered tables of the LiDAR operators
+def test_workspace_keys_move_with_every_argument_they_hold():
+    """one step in any argument of a family's key gives another key (whether the size moves too is the C formula's business: some steps
+    round to the same size); the arguments a key leaves out are pinned beside each operator's own tests"""
+    from cobevt_amd import ops
+    base = {"voxelize": (5000, 2, 32, 700, 16, 12), "voxelize3d": (5000, 2, 32, 700, 16384), "prepare_points": (1000,), "detect": (1536,),
+            "bev_points": (2, 16, 12), "sparse_train": (torch.float32, 4096)}
+    for family, args in base.items():
+        key = ops.WORKSPACE_KEYS[family](*args)
+        assert ops.WORKSPACE_KEYS[family](*args) == key
+        for i, a in enumerate(args):
+            step = torch.float64 if isinstance(a, torch.dtype) else a + 1
+            assert ops.WORKSPACE_KEYS[family](*(args[:i] + (step,) + args[i + 1:])) != key, (family, i)
+    key = ops.WORKSPACE_KEYS["sparse"](2, (41, 13, 21))
+    for other in ((3, (41, 13, 21)), (2, (42, 13, 21)), (2, (41, 14, 21)), (2, (41, 13, 22))):
+        assert ops.WORKSPACE_KEYS["sparse"](*other) != key
+    assert sorted(ops.WORKSPACE_KEYS) == sorted(list(base) + ["sparse"])
+
+
+def test_default_workspace_is_one_buffer_per_family_device_and_key(monkeypatch):
+    import launch_trace as lt
+    from cobevt_amd import ops
+    lt.install(monkeypatch.setattr, lt.Recorder())
+    dev, asked = torch.device("cpu"), []
+
+    def need():
+        asked.append(1)
+        return 24
+
+    try:
+        a = ops._workspace("op", "test_a", dev, (3, 5), need, None)
+        assert ops._workspace("op", "test_a", dev, (3, 5), need, None) is a and asked == [1]            # asked on the miss only
+        assert a.dtype == torch.int32 and a.numel() == 24 and a.data_ptr() % ops.WORKSPACE_ALIGN == 0
+        b = ops._workspace("op", "test_b", dev, (3, 5), 3, None, torch.int64, 8)
+        assert b is not a and b.dtype == torch.int64 and b.numel() == 3                                 # an equal key of another family
+        assert ops._workspace("op", "test_a", dev, (3, 6), need, None) is not a and asked == [1, 1]
+    finally:
+        ops._WORKSPACES.pop("test_a", None)
+        ops._WORKSPACES.pop("test_b", None)
+    # through an operator: two levels of one shape share the default, another shape gets its own
+    coords = torch.zeros(5, 4, dtype=torch.int32)
+    kept = dict(ops._SPARSE_WS)
+    ops._SPARSE_WS.clear()
+    try:
+        x = ops.sparse_index(coords, 1, (4, 4, 4))
+        assert ops.sparse_index(coords, 1, (4, 4, 4)).workspace is x.workspace and ops.sparse_index(coords, 1, (4, 4, 5)).workspace is not x.workspace
+        assert ops._WORKSPACES["sparse"] is ops._SPARSE_WS and sorted(ops._SPARSE_WS) == [(dev, 1, 4, 4, 4), (dev, 1, 4, 4, 5)]
+    finally:
+        ops._SPARSE_WS.clear()                            # (sized by the fake library)
+        ops._SPARSE_WS.update(kept)
+
+
+def test_a_given_workspace_is_checked_by_its_family_s_rules(monkeypatch):
+    """one element short, the wrong dtype, or off the family's alignment (none for voxelize_points and the int64 detection buffer, 8
+    bytes for the 3-D voxeliser, cloud assembly and BEV maps, 16 for the sparse index): refused with the operator's name, the element
+    count, the alignment and the device in the message; at the family's alignment and size it passes"""
+    import launch_trace as lt
+    from cobevt_amd import ops
+    lt.install(monkeypatch.setattr, lt.Recorder())
+    monkeypatch.setattr(ops, "_scratch", lambda entry, dims, n=1, **kw: 64 if n == 1 else (64,) * n)    # every family needs 64 elements (detect: 64 bytes)
+    pts, offs = torch.zeros(10, 4), torch.tensor([0, 10], dtype=torch.int32)
+    rng, coords = [0, 0, 0, 4, 4, 4], torch.zeros(5, 4, dtype=torch.int32)
+    calls = {
+        "voxelize_points": (4, torch.int32, 64, lambda ws: ops.voxelize_points(pts, offs, rng, [1, 1, 4], 32, 7, workspace=ws)),
+        "voxelize_points_3d": (8, torch.int32, 64, lambda ws: ops.voxelize_points_3d(pts, offs, rng, [1, 1, 1], 32, 7, workspace=ws)),
+        "prepare_points": (8, torch.int32, 64, lambda ws: ops.prepare_points(pts, offs, workspace=ws)),
+        "bev_points": (8, torch.int32, 64, lambda ws: ops.bev_points(pts, offs, rng, (0, 0, 0), 1.0, (4, 4, 3), workspace=ws)),
+        "sparse_index": (16, torch.int32, 64, lambda ws: ops.sparse_index(coords, 1, (4, 4, 4), workspace=ws)),
+        "nms_rotated": (8, torch.int64, 8, lambda ws: ops.nms_rotated_device(torch.zeros(3, 4, 2), torch.zeros(3), 0.5, workspace=ws)),
+    }
+    for name, (align, dtype, need, call) in calls.items():
+        big = torch.zeros(need + 16, dtype=dtype)
+        assert big.data_ptr() % 16 == 0
+        call(big[:need])
+        with pytest.raises(CobevtHipError, match="%s: workspace= must be .* at least %d elements on cpu" % (name, need)):
+            call(big[:need - 1])
+        with pytest.raises(CobevtHipError, match="%s: workspace= must be .*%s" % (name, str(dtype).split(".")[1])):
+            call(big[:need].to(torch.int16))
+        for off in (4, 8):
+            if dtype == torch.int32:
+                ws = big[off // 4:off // 4 + need]
+                if off % align:
+                    with pytest.raises(CobevtHipError, match="%s: workspace= must be a contiguous, %d-byte aligned" % (name, align)):
+                        call(ws)
+                else:
+                    call(ws)
+
+
+@pytest.mark.parametrize("family,lower,shape", [("sparse", "sparse_train_weights", (16, 3, 3, 3, 4)), ("deconv", "deconv_train_weights", (8, 32, 2, 2))])
+def test_lowered_tables_follow_the_weight_object(family, lower, shape):
+    """the one cache behind both lowerings: a hit on the same object, a miss on a .detach() of it (another object) and after an in-place
+    update, entries per family, and the entry gone with the weight"""
+    from cobevt_amd import ops
+    lower = getattr(ops, lower)
+    w = torch.nn.Parameter(torch.rand(shape))
+    first = lower(w)
+    assert lower(w)[0] is first[0] and lower(w)[1] is first[1]
+    assert lower(w.detach())[0] is not first[0] and lower(w)[0] is first[0]
+    with torch.no_grad():
+        w.add_(1.0)
+    assert lower(w)[0] is not first[0]
+    key = id(w)
+    assert key in ops._TABLES[family] and all(key not in t for f, t in ops._TABLES.items() if f != family)
+    del w
+    assert key not in ops._TABLES[family]

@@ -219,3 +219,9 @@ def test_null_pointers_return_code_1():
     assert L.cobevt_bev_labels(None, None, None, None, None, None, None, None) == 1
     assert L.cobevt_bev_post(None, None, None, None, 1, params, 0.5, 0.15, None, None, None, None, None, None) == 1
     assert L.cobevt_bev_post(None, None, None, None, 1, None, 0.5, 0.15, None, None, None, None, None, None) == 1
+
+
+def test_the_workspace_size_follows_its_key():
+    """bev_points' default workspace is cached on (N, nx, ny): the point count and the channels, which the key leaves out, must not
+    move the size (a key with M in it would grow one buffer per distinct cloud)"""
+    assert ops.bev_points_workspace_ints(10, 2, (16, 12, 5)) == ops.bev_points_workspace_ints(99999, 2, (16, 12, 9)) == 3 * 2 * 16 * 12

@@ -249,3 +249,12 @@ def test_workspace_ints_is_what_the_scratch_call_returns(m, n, t, mv, slots):
     table = ops.voxelize3d_table_slots(m, slots)
     assert table == (slots or max(64, c3.table_above(2 * m - 1)))
     assert ops.voxelize3d_workspace_ints(m, n, t, mv, slots) == need.value == 6 * table + n * mv + 2 * m + 2 * ((m + 1023) // 1024 or 1) + 2 + n + 1
+
+
+def test_the_workspace_size_follows_its_key_not_the_grid():
+    """the default workspace is cached on (M, N, T, max_voxels, table): the grid, which the key leaves out, must not move the size"""
+    m, n, t, mv, slots = 5000, 2, 32, 700, 16384
+    sizes = [ops._scratch("cobevt_voxelize3d_scratch", ops._longs(m, n, t, mv, nx, ny, nz, 0, 0, slots)) for nx, ny, nz in ((16, 12, 1), (160, 120, 41))]
+    assert sizes[0] == sizes[1] == ops.voxelize3d_workspace_ints(m, n, t, mv, slots)
+    default = [ops._scratch("cobevt_voxelize3d_scratch", ops._longs(m, n, t, mv, nx, ny, nz, 0, 0, 0)) for nx, ny, nz in ((16, 12, 1), (160, 120, 41))]
+    assert default[0] == default[1] == ops.voxelize3d_workspace_ints(m, n, t, mv)
