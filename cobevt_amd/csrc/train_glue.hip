@@ -688,6 +688,151 @@ inline unsigned walk_blocks(long items, int per_thread) {
     return (unsigned)(b < 1 ? 1 : (b > 2048 ? 2048 : b));
 }
 
+// ---- multi-tensor Adam / AdamW (torch.optim.AdamW of train_utils.py:174-199, the last ATen block of the captured step) ----
+// Everything a launch needs to find its tensors travels BY VALUE in the kernel arguments (no pointer table in device memory, no
+// host -> device copy: capture-safe), and everything that changes from step to step - the step counters, the learning rate, the
+// GradScaler's two words - is read from device memory, so a replayed graph follows a scheduler.
+constexpr int kAdamTensors = 64;      // tensors of one update launch: 4 pointers + a count + a chunk count each = 2816 bytes of arguments
+constexpr int kAdamChunk = 4096;      // elements a workgroup owns: 256 threads x 4 pieces of 16 bytes
+constexpr int kAdamPrepare = 448;     // step pointers of one prepare launch (3584 bytes of the 4-KB argument limit)
+
+struct AdamSteps {
+    float* step[kAdamPrepare];
+};
+
+struct AdamPack {
+    float* p[kAdamTensors];
+    const float* g[kAdamTensors];
+    float* m[kAdamTensors];
+    float* v[kAdamTensors];
+    long numel[kAdamTensors];
+    int chunk_end[kAdamTensors];      // running chunk count: tensor t owns workgroups [chunk_end[t - 1], chunk_end[t])
+};
+
+// One thread per tensor: step += 1 and the tensor's coefficient row [decay | wd, step_size, 1 / sqrt(bias_correction2), 1 / grad_scale],
+// each computed in fp64 and rounded once.  found_inf != 0: no step moves and every row says "skip" (a negative last word).
+__global__ __launch_bounds__(64) void adam_prepare_kernel(const AdamSteps st, int n, float* __restrict__ coef, int adamw, double beta1,
+                                                          double beta2, double weight_decay, double lr, const double* lr_dev,
+                                                          const float* grad_scale, const float* found_inf) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    float4 row;
+    if (found_inf && *found_inf != 0.f) {
+        row = make_float4(0.f, 0.f, 0.f, -1.f);
+    } else {
+        float* sp = st.step[i];
+        const float s = *sp + 1.f;
+        *sp = s;
+        const double l = lr_dev ? *lr_dev : lr;
+        row.x = adamw ? (float)(1.0 - l * weight_decay) : (float)weight_decay;
+        row.y = (float)(l / (1.0 - pow(beta1, (double)s)));
+        row.z = (float)(1.0 / sqrt(1.0 - pow(beta2, (double)s)));
+        row.w = grad_scale ? (float)(1.0 / (double)*grad_scale) : 1.f;
+    }
+    *reinterpret_cast<float4*>(coef + 4 * (size_t)i) = row;
+}
+
+// One element's update, every line one rounded fp32 operation (no contraction: tests/optim_ref.py counts these roundings)
+template <bool ADAMW>
+__device__ __forceinline__ void adam_update(float& p, float g, float& m, float& v, const float4 c, float omb1, float b2, float omb2, float eps) {
+#pragma clang fp contract(off)
+    g = g * c.w;
+    if (!ADAMW) {
+        const float l2 = c.x * p;
+        g = g + l2;
+    } else {
+        p = p * c.x;
+    }
+    const float dm = g - m;
+    const float tm = dm * omb1;
+    m = m + tm;
+    const float a = b2 * v;
+    const float b = omb2 * g;
+    const float gg = b * g;
+    v = a + gg;
+    const float s = sqrtf(v);
+    const float r = s * c.z;
+    const float d = r + eps;
+    const float q = m / d;
+    const float u = c.y * q;
+    p = p - u;
+}
+
+template <bool ADAMW>
+__device__ __forceinline__ void adam_update4(float4& p, const float4 g, float4& m, float4& v, const float4 c, float omb1, float b2, float omb2,
+                                             float eps) {
+    adam_update<ADAMW>(p.x, g.x, m.x, v.x, c, omb1, b2, omb2, eps);
+    adam_update<ADAMW>(p.y, g.y, m.y, v.y, c, omb1, b2, omb2, eps);
+    adam_update<ADAMW>(p.z, g.z, m.z, v.z, c, omb1, b2, omb2, eps);
+    adam_update<ADAMW>(p.w, g.w, m.w, v.w, c, omb1, b2, omb2, eps);
+}
+
+// A workgroup owns one chunk of one tensor; the tensor comes from a wave-uniform binary search of the running chunk counts (scalar
+// loads from the argument segment).  A full chunk of a 16-byte-aligned tensor moves as two rounds of two pieces per array, all eight
+// loads of a round issued before the first use; a short chunk checks each piece, its last numel % 4 elements and every chunk of an
+// unaligned tensor go element by element.
+template <bool ADAMW>
+__global__ __launch_bounds__(kThreads, 8) void multi_adam_kernel(const AdamPack pk, const float* __restrict__ coef, int n, float omb1, float b2,
+                                                                 float omb2, float eps) {
+    const int blk = blockIdx.x;
+    int lo = 0, hi = n - 1;                    // the first tensor whose running count exceeds blk
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (pk.chunk_end[mid] > blk) hi = mid;
+        else lo = mid + 1;
+    }
+    const int t = lo;
+    const float4 c = *reinterpret_cast<const float4*>(coef + 4 * t);
+    if (c.w < 0.f) return;                     // found_inf: nothing is written
+    const long base = (long)(blk - (t ? pk.chunk_end[t - 1] : 0)) * kAdamChunk;
+    const long left = pk.numel[t] - base;
+    const int cnt = left < kAdamChunk ? (int)left : kAdamChunk;
+    float* __restrict__ p = pk.p[t] + base;
+    const float* __restrict__ g = pk.g[t] + base;
+    float* __restrict__ m = pk.m[t] + base;
+    float* __restrict__ v = pk.v[t] + base;
+    const int tid = threadIdx.x;
+    if ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) != 0) {
+        for (int i = tid; i < cnt; i += kThreads) {
+            float pe = p[i], me = m[i], ve = v[i];
+            adam_update<ADAMW>(pe, g[i], me, ve, c, omb1, b2, omb2, eps);
+            p[i] = pe; m[i] = me; v[i] = ve;
+        }
+        return;
+    }
+    float4* p4 = reinterpret_cast<float4*>(p);
+    const float4* g4 = reinterpret_cast<const float4*>(g);
+    float4* m4 = reinterpret_cast<float4*>(m);
+    float4* v4 = reinterpret_cast<float4*>(v);
+    if (cnt == kAdamChunk) {
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            const int i0 = r * 2 * kThreads + tid, i1 = i0 + kThreads;
+            float4 pa = p4[i0], pb = p4[i1];
+            const float4 ga = g4[i0], gb = g4[i1];
+            float4 ma = m4[i0], mb = m4[i1];
+            float4 va = v4[i0], vb = v4[i1];
+            adam_update4<ADAMW>(pa, ga, ma, va, c, omb1, b2, omb2, eps);
+            adam_update4<ADAMW>(pb, gb, mb, vb, c, omb1, b2, omb2, eps);
+            p4[i0] = pa; m4[i0] = ma; v4[i0] = va;
+            p4[i1] = pb; m4[i1] = mb; v4[i1] = vb;
+        }
+        return;
+    }
+    const int pieces = cnt >> 2;
+    for (int i = tid; i < pieces; i += kThreads) {
+        float4 pa = p4[i], ma = m4[i], va = v4[i];
+        adam_update4<ADAMW>(pa, g4[i], ma, va, c, omb1, b2, omb2, eps);
+        p4[i] = pa; m4[i] = ma; v4[i] = va;
+    }
+    const int i = pieces * 4 + tid;
+    if (i < cnt) {
+        float pe = p[i], me = m[i], ve = v[i];
+        adam_update<ADAMW>(pe, g[i], me, ve, c, omb1, b2, omb2, eps);
+        p[i] = pe; m[i] = me; v[i] = ve;
+    }
+}
+
 }  // namespace
 }  // namespace cobevt
 
@@ -893,5 +1038,57 @@ extern "C" int cobevt_sttf_warp_bwd(const float* dout, const float* tmat, const 
     const long items = (long)H * W * (C >> 3);
     const dim3 grid((unsigned)((items + kThreads - 1) / kThreads), (unsigned)(B * L));
     hipLaunchKernelGGL(sttf_warp_bwd_kernel, grid, dim3(kThreads), 0, stream, dout, tmat, record_len, dx, B, L, H, W, C, discrete_ratio, downsample_rate);
+    return cobevt::launch_status();
+}
+
+// steps: HOST array of n device pointers (fp32 step counters); coef: device fp32 [n][4], 16-byte aligned.  One launch per 448 tensors.
+extern "C" int cobevt_adam_prepare(float* const* steps, int n, float* coef, int adamw, double beta1, double beta2, double weight_decay,
+                                   double lr, const double* lr_dev, const float* grad_scale, const float* found_inf, hipStream_t stream) {
+    if (!steps || !coef) return COBEVT_ERR_ARG;
+    if (n < 1 || (adamw != 0 && adamw != 1) || ((uintptr_t)coef & 15) || ((uintptr_t)lr_dev & 7)) return COBEVT_ERR_SHAPE;
+    if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(weight_decay >= 0.0) || !(lr_dev || lr >= 0.0))
+        return COBEVT_ERR_SHAPE;
+    for (int i = 0; i < n; ++i) {
+        if (!steps[i]) return COBEVT_ERR_ARG;
+        if ((uintptr_t)steps[i] & 3) return COBEVT_ERR_SHAPE;
+    }
+    for (int i0 = 0; i0 < n; i0 += kAdamPrepare) {
+        AdamSteps st;
+        const int cnt = n - i0 < kAdamPrepare ? n - i0 : kAdamPrepare;
+        for (int i = 0; i < kAdamPrepare; ++i) st.step[i] = i < cnt ? steps[i0 + i] : nullptr;
+        hipLaunchKernelGGL(adam_prepare_kernel, dim3((cnt + 63) / 64), dim3(64), 0, stream, st, cnt, coef + 4 * (size_t)i0, adamw, beta1, beta2,
+                           weight_decay, lr, lr_dev, grad_scale, found_inf);
+    }
+    return cobevt::launch_status();
+}
+
+// params / grads / exp_avgs / exp_avg_sqs: HOST arrays of n <= 64 device pointers (fp32, contiguous, numels[i] >= 1 elements each);
+// coef: the n rows cobevt_adam_prepare wrote for these tensors.  One launch of sum ceil(numels[i] / 4096) workgroups.
+extern "C" int cobevt_multi_adam(void* const* params, const void* const* grads, void* const* exp_avgs, void* const* exp_avg_sqs,
+                                 const long* numels, int n, const float* coef, int adamw, double beta1, double beta2, double eps,
+                                 hipStream_t stream) {
+    if (!params || !grads || !exp_avgs || !exp_avg_sqs || !numels || !coef) return COBEVT_ERR_ARG;
+    if (n < 1 || n > kAdamTensors || (adamw != 0 && adamw != 1) || ((uintptr_t)coef & 15)) return COBEVT_ERR_SHAPE;
+    if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(eps >= 0.0)) return COBEVT_ERR_SHAPE;
+    AdamPack pk;
+    long chunks = 0;
+    for (int i = 0; i < kAdamTensors; ++i) {
+        if (i < n) {
+            if (!params[i] || !grads[i] || !exp_avgs[i] || !exp_avg_sqs[i]) return COBEVT_ERR_ARG;
+            if ((((uintptr_t)params[i] | (uintptr_t)grads[i] | (uintptr_t)exp_avgs[i] | (uintptr_t)exp_avg_sqs[i]) & 3) || numels[i] < 1)
+                return COBEVT_ERR_SHAPE;
+            chunks += (numels[i] + kAdamChunk - 1) / kAdamChunk;
+            if (chunks > 0x7fffffffL) return COBEVT_ERR_SHAPE;
+        }
+        pk.p[i] = i < n ? (float*)params[i] : nullptr;
+        pk.g[i] = i < n ? (const float*)grads[i] : nullptr;
+        pk.m[i] = i < n ? (float*)exp_avgs[i] : nullptr;
+        pk.v[i] = i < n ? (float*)exp_avg_sqs[i] : nullptr;
+        pk.numel[i] = i < n ? numels[i] : 0;
+        pk.chunk_end[i] = (int)chunks;
+    }
+    const float omb1 = (float)(1.0 - beta1), b2 = (float)beta2, omb2 = (float)(1.0 - beta2), epsf = (float)eps;
+    if (adamw) hipLaunchKernelGGL(multi_adam_kernel<true>, dim3((unsigned)chunks), dim3(kThreads), 0, stream, pk, coef, n, omb1, b2, omb2, epsf);
+    else hipLaunchKernelGGL(multi_adam_kernel<false>, dim3((unsigned)chunks), dim3(kThreads), 0, stream, pk, coef, n, omb1, b2, omb2, epsf);
     return cobevt::launch_status();
 }

@@ -45,7 +45,9 @@ from . import eval_utils  # noqa: F401
 from .eval_utils import calculate_ap, caluclate_tp_fp, eval_final_results, voc_ap  # noqa: F401
 from .rgb_preprocessor import RgbPreProcessor  # noqa: F401
 from .intermediate_fusion_dataset import collate_batch  # noqa: F401
-from .train_utils import load_saved_model  # noqa: F401
+from .train_utils import load_saved_model, setup_lr_schedular, setup_optimizer, to_device  # noqa: F401
+from .optim import FusedAdam, FusedAdamW  # noqa: F401
+from .lr_scheduler import CosineLRScheduler  # noqa: F401
 from .seg_utils import cal_iou_training, mean_IU, mean_precision  # noqa: F401
 from .vanilla_seg_loss import VanillaSegLoss  # noqa: F401
 from .point_pillar_loss import PointPillarLoss  # noqa: F401

@@ -36,7 +36,9 @@ class CapturedTrainStep(GraphOwner):
     model      a HipModule in train() mode on a ROCm device (CorpBEVT / FaxFusedTransformer / PointPillarFuseBEVT, whose voxel
                tensors sit in the nested 'processed_lidar' dict: pad P to a fixed size with rows of agent index -1)
     criterion  callable (output_dict, batch) -> scalar loss (e.g. VanillaSegLoss via a lambda picking the ground-truth keys)
-    optimizer  torch.optim.SGD, or Adam / AdamW built with capturable=True
+    optimizer  host.FusedAdamW / FusedAdam (host.setup_optimizer builds them; their learning rate is read from device memory, so
+               the replayed step follows a scheduler: step() uploads param_group["lr"] before every replay), torch.optim.SGD, or
+               torch's Adam / AdamW built with capturable=True (their float lr is baked into the graph at capture)
     example_batch  dict of tensors with the shapes every later batch will have
     reducer    optional cobevt_amd.dist.GradAllReducer over the same parameters (world size > 1)
     warmup     eager steps run before the capture (they build the optimizer state and the autograd / allocator caches); the
@@ -173,6 +175,9 @@ class CapturedTrainStep(GraphOwner):
     def step(self, batch=None):
         if batch is not None:
             self.load(batch)
+        sync = getattr(self.optimizer, "sync_hyperparameters", None)
+        if sync is not None:                      # FusedAdam / FusedAdamW: this step's learning rate, read by the replayed kernels
+            sync()
         self.graphs[0].replay()
         if self.reducer is not None:
             self.reducer.finish()

@@ -186,6 +186,8 @@ SIGNATURES = {
     "cobevt_sparse_conv_dgrad": (ctypes.c_int, [_vp] * 7 + [_c_long_p, _vp]),
     "cobevt_sparse_conv_wgrad": (ctypes.c_int, [_vp] * 9 + [_c_long_p, _vp]),
     "cobevt_sparse_dense_bwd": (ctypes.c_int, [_vp] * 4 + [_c_long_p, _vp]),
+    "cobevt_adam_prepare": (ctypes.c_int, [ctypes.POINTER(_vp), ctypes.c_int, _vp, ctypes.c_int] + [ctypes.c_double] * 4 + [_vp] * 3 + [_vp]),
+    "cobevt_multi_adam": (ctypes.c_int, [ctypes.POINTER(_vp)] * 4 + [_c_long_p, ctypes.c_int, _vp, ctypes.c_int] + [ctypes.c_double] * 3 + [_vp]),
 }
 
 _libs = {}

@@ -3267,3 +3267,73 @@ def sigmoid_focal_loss_mean(pred, label, visibility, label_indices, min_visibili
     _L.call("cobevt_sigmoid_focal_loss", _p(pred.float().contiguous()), _p(label), _p(vis), _p(masks), _p(scratch), _p(out), n, c, nl, hw,
             mv, ctypes.c_float(alpha), ctypes.c_float(gamma), int(soft), _stream())
     return out[0]
+
+
+# ----------------------------------------------------------------------------------------------
+# multi-tensor Adam / AdamW (csrc/train_glue.hip; host/optim.py is the torch.optim.Optimizer in front of it)
+# ----------------------------------------------------------------------------------------------
+ADAM_MAX_TENSORS = 64      # tensors of one cobevt_multi_adam launch: their pointers travel in the kernel arguments
+ADAM_CHUNK = 4096          # elements per workgroup
+AdamLaunch = namedtuple("AdamLaunch", "first count chunks")     # tensors [first, first + count) and the chunk count of each
+
+
+def adam_groups(numels):
+    """How the tensors of one param group are dealt to update launches: in order, at most ADAM_MAX_TENSORS per launch, a launch's
+    grid (the sum of its chunk counts) below 2^31.  -> [AdamLaunch]; pure, no device."""
+    out, first, chunks, total = [], 0, [], 0
+    for i, n in enumerate(numels):
+        n = int(n)
+        if n < 1:
+            raise CobevtHipError("adam_groups: tensor %d has %d elements" % (i, n))
+        c = (n + ADAM_CHUNK - 1) // ADAM_CHUNK
+        if c > 0x7fffffff:
+            raise CobevtHipError("adam_groups: tensor %d needs %d chunks, more than one launch can hold" % (i, c))
+        if len(chunks) == ADAM_MAX_TENSORS or total + c > 0x7fffffff:
+            out.append(AdamLaunch(first, len(chunks), tuple(chunks)))
+            first, chunks, total = i, [], 0
+        chunks.append(c)
+        total += c
+    if chunks:
+        out.append(AdamLaunch(first, len(chunks), tuple(chunks)))
+    return out
+
+
+def _ptr_array(tensors):
+    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
+def multi_adam(params, grads, exp_avgs, exp_avg_sqs, steps, coef, lr, beta1, beta2, eps, weight_decay, adamw=True, lr_dev=None,
+               grad_scale=None, found_inf=None):
+    """One Adam (adamw=False: L2 weight decay) or AdamW step on lists of fp32 contiguous device tensors, in place: `steps` (one fp32
+    word each) advance by one, then params / exp_avgs / exp_avg_sqs are updated from grads.  coef: fp32 scratch of >= 4 floats per
+    tensor, overwritten.  lr_dev (an fp64 device word) replaces the float `lr` when given - inside a stream capture that is what
+    lets a replay follow a scheduler; grad_scale / found_inf are torch.amp.GradScaler's device words (found_inf != 0: nothing moves).
+    One prepare launch per 448 tensors + one update launch per 64."""
+    n = len(params)
+    if n < 1 or not (len(grads) == len(exp_avgs) == len(exp_avg_sqs) == len(steps) == n):
+        raise CobevtHipError("multi_adam: five lists of one length >= 1, got %s" % ([len(x) for x in (params, grads, exp_avgs, exp_avg_sqs, steps)],))
+    if not (0.0 <= beta1 < 1.0 and 0.0 <= beta2 < 1.0 and eps >= 0.0 and weight_decay >= 0.0 and (lr_dev is not None or lr >= 0.0)):
+        raise CobevtHipError("multi_adam: need 0 <= beta < 1, eps >= 0, weight_decay >= 0, lr >= 0")
+    dev = params[0].device
+    for i in range(n):
+        p = params[i]
+        for t, what in ((p, "param"), (grads[i], "grad"), (exp_avgs[i], "exp_avg"), (exp_avg_sqs[i], "exp_avg_sq")):
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != p.numel() or t.device != dev or t.is_sparse:
+                raise CobevtHipError("multi_adam: %s %d must be a dense contiguous fp32 tensor of %d elements on %s, got %s %s on %s"
+                                     % (what, i, p.numel(), dev, t.dtype, tuple(t.shape), t.device))
+        if steps[i].dtype != torch.float32 or steps[i].numel() != 1 or steps[i].device != dev:
+            raise CobevtHipError("multi_adam: step %d must be one fp32 word on %s" % (i, dev))
+    if coef.dtype != torch.float32 or not coef.is_contiguous() or coef.numel() < 4 * n or coef.device != dev:
+        raise CobevtHipError("multi_adam: coef must be contiguous fp32 with >= %d elements on %s" % (4 * n, dev))
+    for t, what, dt in ((lr_dev, "lr_dev", torch.float64), (grad_scale, "grad_scale", torch.float32), (found_inf, "found_inf", torch.float32)):
+        if t is not None and (t.dtype != dt or t.numel() != 1 or t.device != dev):
+            raise CobevtHipError("multi_adam: %s must be one %s word on %s" % (what, dt, dev))
+    _need_cuda(params[0], coef)
+    launches = adam_groups([p.numel() for p in params])
+    _L.call("cobevt_adam_prepare", _ptr_array(steps), n, _p(coef), int(bool(adamw)), float(beta1), float(beta2), float(weight_decay),
+            float(lr), _p(lr_dev), _p(grad_scale), _p(found_inf), _stream())
+    for la in launches:
+        sl = slice(la.first, la.first + la.count)
+        _L.call("cobevt_multi_adam", _ptr_array(params[sl]), _ptr_array(grads[sl]), _ptr_array(exp_avgs[sl]), _ptr_array(exp_avg_sqs[sl]),
+                _longs(*[p.numel() for p in params[sl]]), la.count, ctypes.c_void_p(coef.data_ptr() + 16 * la.first), int(bool(adamw)),
+                float(beta1), float(beta2), float(eps), _stream())

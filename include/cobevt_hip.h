@@ -1201,6 +1201,31 @@ int cobevt_sparse_conv_wgrad(const float* x, const int* in_workspace, const int*
                              const int* out_num, const float* dz, float* partial, float* dw, const long* dims, hipStream_t stream);
 int cobevt_sparse_dense_bwd(const float* dcanvas, const int* indices, const int* num, float* dfeatures, const long* dims, hipStream_t stream);
 
+/*
+ * Multi-tensor Adam / AdamW (csrc/train_glue.hip; torch.optim.Adam / AdamW without amsgrad / maximize, fp32 contiguous tensors only).
+ * The tensor lists are HOST arrays of device pointers, copied by value into the kernel arguments: no pointer table in device memory
+ * and no host -> device copy, so both entry points may be captured into a HIP graph.  What changes between replays is read from
+ * device memory: the step counters, lr_dev, grad_scale, found_inf.  Arguments are validated before any launch (null: code 1; count,
+ * range, alignment: code 2).
+ *
+ * cobevt_adam_prepare: n >= 1 step counters (fp32 words) and coef, device fp32 [n][4], 16-byte aligned.  lr_dev (nullable, a device
+ *   fp64 word, 8-byte aligned) replaces lr when given; grad_scale and found_inf (nullable, device fp32 words) are torch.amp.GradScaler's.
+ *   found_inf != 0: no counter moves and every row is [0, 0, 0, -1] = "skip".  Otherwise step += 1 and row i =
+ *   [adamw ? 1 - lr weight_decay : weight_decay, lr / (1 - beta1^step), 1 / sqrt(1 - beta2^step), grad_scale ? 1 / grad_scale : 1],
+ *   each computed in fp64 and rounded to fp32 once.  0 <= beta < 1, weight_decay >= 0, lr >= 0.  One launch per 448 tensors.
+ * cobevt_multi_adam: 1 <= n <= 64 tensors of numels[i] >= 1 elements and the n rows of coef written for them.  Per element, every line
+ *   one rounded fp32 operation (no contraction; division and square root correctly rounded), c = the tensor's row:
+ *     g = g c[3];  adamw ? p = p c[0] : g = g + c[0] p;  m = m + (g - m) (1 - beta1);  v = beta2 v + ((1 - beta2) g) g;
+ *     p = p - c[1] (m / (sqrt(v) c[2] + eps))
+ *   with (1 - beta1), beta2, (1 - beta2) and eps rounded from fp64 once.  A "skip" row leaves p, m and v untouched, bit for bit; grads
+ *   are never written.  One launch of sum ceil(numels[i] / 4096) workgroups (< 2^31); tensors whose four pointers are not all 16-byte
+ *   aligned are served element by element.
+ */
+int cobevt_adam_prepare(float* const* steps, int n, float* coef, int adamw, double beta1, double beta2, double weight_decay, double lr,
+                        const double* lr_dev, const float* grad_scale, const float* found_inf, hipStream_t stream);
+int cobevt_multi_adam(void* const* params, const void* const* grads, void* const* exp_avgs, void* const* exp_avg_sqs, const long* numels,
+                      int n, const float* coef, int adamw, double beta1, double beta2, double eps, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
