@@ -4,7 +4,8 @@ from .fax_modules import (Attention as FaxAttention, BEVEmbedding, Bottleneck, C
                           CrossWinAttention, FAXModule, generate_grid, get_view_matrix)
 from .swap_fusion_modules import (Attention as SwapAttention, SwapFusionBlock, SwapFusionBlockMask,  # noqa: F401
                                   SwapFusionEncoder)
-from .base_transformer import BaseEncoder, BaseTransformer, CavAttention, FeedForward, PreNorm, PreNormResidual  # noqa: F401
+from .base_transformer import (BaseEncoder, BaseTransformer, CavAttention, CavPositionalEncoding, FeedForward, HGTCavAttention, PreNorm,  # noqa: F401
+                               PreNormResidual, RelTemporalEncoding, RTE)  # noqa: F401
 from .resnet_ms import ResnetEncoder  # noqa: F401
 from .naive_decoder import NaiveDecoder  # noqa: F401
 from .naive_compress import NaiveCompressor  # noqa: F401

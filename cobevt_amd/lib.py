@@ -46,6 +46,9 @@ SIGNATURES = {
     "cobevt_att_fuse_nhwc": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_long, ctypes.c_int,
                                             ctypes.c_float, _vp]),
     "cobevt_att_fuse_bwd_nhwc": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_long, ctypes.c_int, ctypes.c_float, _vp]),
+    "cobevt_typed_linear": (ctypes.c_int, [_vp] * 6 + [_c_long_p, ctypes.c_float, _vp]),
+    "cobevt_hgt_attention_nhwc": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_long, ctypes.c_int,
+                                                 ctypes.c_int, ctypes.c_float, _vp]),
     "cobevt_window_attention": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _c_int_p, ctypes.c_float, _vp]),
     "cobevt_window_attention_ksplit": (ctypes.c_int, [_vp] * 8 + [_c_int_p, ctypes.c_float, ctypes.c_int, ctypes.c_long, _vp]),
     "cobevt_window_attention_lse": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_int_p, ctypes.c_float, ctypes.c_float,

@@ -2722,6 +2722,161 @@ def att_fuse_bwd(x, record_len, dout):
     return dx
 
 
+# ---------------------------------------------------------------------------------------------- typed agent attention (HGTCavAttention)
+HGT_MAX_AGENTS = 8         # cobevt_hgt_attention_nhwc refuses more keys per pixel
+HgtFold = namedtuple("HgtFold", "w_in b_in w_out b_out num_types heads")
+_HGT_FOLDS = {}            # (ids of the parameter objects, dtype, device) -> (weakrefs, stamps, HgtFold)
+
+
+def _hgt_source(src):
+    """module or state dict -> {key: tensor} with the module's own Parameter objects (state_dict() hands out new objects every call)"""
+    if isinstance(src, dict):
+        return src
+    return dict(src.named_parameters())
+
+
+def _hgt_fold64(sd, ln):
+    """the float64 fold: per row type b the rows [Wq_b | R_att[a T + b] Wk_b, a = 0 .. T - 1 | R_msg[a T + b]^T Wv_b, a = 0 .. T - 1] and the
+    same for the biases, the LayerNorm affine folded last (W' = W g, b' = b + W beta)"""
+    num_types = len([k for k in sd if k.startswith("q_linears.") and k.endswith(".weight")])
+    ratt, rmsg = sd["relation_att"].detach().double(), sd["relation_msg"].detach().double()
+    if num_types < 1 or ratt.dim() != 4 or ratt.shape != rmsg.shape or ratt.shape[2] != ratt.shape[3]:
+        raise CobevtHipError("hgt_fold: not an HGTCavAttention state (q_linears.*, relation_att / relation_msg (R, heads, d, d))")
+    if ratt.shape[0] < num_types * num_types:
+        raise CobevtHipError("hgt_fold: %d relations cannot serve %d x %d type pairs (index a T + b)" % (ratt.shape[0], num_types, num_types))
+    heads, dh = int(ratt.shape[1]), int(ratt.shape[2])
+    w_in, b_in, w_out, b_out = [], [], [], []
+    for b in range(num_types):
+        w = {n: sd["%s_linears.%d.weight" % (n, b)].detach().double() for n in "qkva"}
+        bs = {n: sd["%s_linears.%d.bias" % (n, b)].detach().double() for n in "qkva"}
+        dim = w["q"].shape[1]
+        rows_w, rows_b = [w["q"]], [bs["q"]]
+        for name, rel, transpose in (("k", ratt, False), ("v", rmsg, True)):
+            for a in range(num_types):
+                r = rel[a * num_types + b]                                   # (heads, d, d)
+                r = r.transpose(1, 2) if transpose else r
+                rows_w.append(torch.einsum("mpq,mqc->mpc", r, w[name].reshape(heads, dh, dim)).reshape(heads * dh, dim))
+                rows_b.append(torch.einsum("mpq,mq->mp", r, bs[name].reshape(heads, dh)).reshape(heads * dh))
+        wt, bt = torch.cat(rows_w, 0), torch.cat(rows_b, 0)
+        if ln is not None:
+            g, be = ln.weight.detach().double().to(wt.device), ln.bias.detach().double().to(wt.device)
+            bt = bt + wt @ be
+            wt = wt * g[None, :]
+        w_in.append(wt)
+        b_in.append(bt)
+        w_out.append(w["a"])
+        b_out.append(bs["a"])
+    return torch.stack(w_in), torch.stack(b_in), torch.stack(w_out), torch.stack(b_out), num_types, heads
+
+
+def hgt_fold(module_or_state, ln=None, dtype=torch.float32, device=None):
+    """HGTCavAttention's parameters (the module, or a state dict of its 2 + 8 T tensors) -> HgtFold: w_in (T, (1 + 2 T) inner, dim) and
+    b_in (T, (1 + 2 T) inner), selected by a ROW's own type b: the query projection, then for every query type a the key projection
+    with relation_att[a T + b] folded in and the value projection with relation_msg[a T + b]^T folded in (block-diagonal over the
+    heads); ln = the LayerNorm in front, whose affine is folded too.  w_out (T, dim, inner), b_out (T, dim): the a_linears.  Folded in
+    float64 on the tensors' own device (CPU tensors work: pure torch), rounded once: weights to `dtype`, biases to fp32.  Cached per
+    parameter OBJECTS on their version counters and addresses; never filled inside a stream capture (there the fold is part of the graph)."""
+    sd = _hgt_source(module_or_state)
+    keys = sorted(k for k in sd if k.startswith(("q_linears.", "k_linears.", "v_linears.", "a_linears.")) or k in ("relation_att", "relation_msg"))
+    if "relation_att" not in sd or "relation_msg" not in sd:
+        raise CobevtHipError("hgt_fold: relation_att / relation_msg are missing")
+    tensors = [sd[k] for k in keys] + ([ln.weight, ln.bias] if ln is not None else [])
+    dev = torch.device(device) if device is not None else tensors[0].device
+    capturing = tensors[0].is_cuda and torch.cuda.is_current_stream_capturing()
+    key = (tuple(id(t) for t in tensors), dtype, str(dev), None if ln is None else float(ln.eps))
+    stamp = tuple((t._version, t.data_ptr()) for t in tensors)
+    ent = _HGT_FOLDS.get(key)
+    if not capturing and ent is not None and ent[1] == stamp and all(r() is t for r, t in zip(ent[0], tensors)):
+        return ent[2]
+    w_in, b_in, w_out, b_out, num_types, heads = _hgt_fold64(sd, ln)
+    fold = HgtFold(w_in.to(torch.float32).to(dtype).to(dev).contiguous(), b_in.to(torch.float32).to(dev).contiguous(),
+                   w_out.to(torch.float32).to(dtype).to(dev).contiguous(), b_out.to(torch.float32).to(dev).contiguous(), num_types, heads)
+    if not capturing:
+        _HGT_FOLDS[key] = ([weakref.ref(t, lambda _, k=key: _HGT_FOLDS.pop(k, None)) for t in tensors], stamp, fold)
+    return fold
+
+
+def typed_linear(x, w, bias, types, rows, residual=None, ln_eps=None, out=None):
+    """y[row] = W[t] n(x[row]) + bias[t] (+ residual[row]) in one cobevt_typed_linear launch: x (..., K) contiguous in the compute dtype,
+    its rows in G = types.numel() groups of `rows` consecutive rows; t = types[g] clamped to 0 .. T - 1 ON THE DEVICE (int32, no host
+    read); w (T, N, K) in x's dtype, bias (T, N) fp32; n = the LayerNorm normalisation with ln_eps (affine folded into w / bias) or the
+    identity (ln_eps None).  -> (..., N).  K, N multiples of 32; K <= 512 with ln_eps, <= 1024 without."""
+    code = dcode(x.dtype)
+    if x.dim() < 2 or not x.is_contiguous() or x.numel() == 0:
+        raise CobevtHipError("typed_linear: x must be a contiguous non-empty (..., K) tensor, got %s (contiguous=%s)" % (tuple(x.shape), x.is_contiguous()))
+    if w.dim() != 3 or w.dtype != x.dtype or not w.is_contiguous() or w.shape[2] != x.shape[-1]:
+        raise CobevtHipError("typed_linear: w must be a contiguous %s (T, N, K=%d) tensor, got %s %s" % (x.dtype, x.shape[-1], w.dtype, tuple(w.shape)))
+    t, n, k = (int(d) for d in w.shape)
+    if k % 32 or n % 32:
+        raise CobevtHipError("typed_linear: K=%d and N=%d must be multiples of 32 (one MFMA tile)" % (k, n))
+    if k > (512 if ln_eps is not None else 1024):
+        raise CobevtHipError("typed_linear: K=%d exceeds the row tile the kernel keeps in LDS (512 with LayerNorm, 1024 without)" % k)
+    if bias.dtype != torch.float32 or tuple(bias.shape) != (t, n) or not bias.is_contiguous():
+        raise CobevtHipError("typed_linear: bias must be a contiguous fp32 (%d, %d) tensor, got %s %s" % (t, n, bias.dtype, tuple(bias.shape)))
+    if types.dtype != torch.int32 or not types.is_contiguous() or types.numel() < 1:
+        raise CobevtHipError("typed_linear: types must be a contiguous non-empty int32 tensor, got %s %s" % (types.dtype, tuple(types.shape)))
+    g, rows = int(types.numel()), int(rows)
+    m = x.numel() // k
+    if rows < 1 or g * rows != m:
+        raise CobevtHipError("typed_linear: %d rows are not %d groups of %d rows" % (m, g, rows))
+    if g > 65535:
+        raise CobevtHipError("typed_linear: %d groups exceed the grid's 65535" % g)
+    oshape = tuple(x.shape[:-1]) + (n,)
+    for name, tns in (("residual", residual), ("out", out)):
+        if tns is not None and (tuple(tns.shape) != oshape or tns.dtype != x.dtype or not tns.is_contiguous()):
+            raise CobevtHipError("typed_linear: %s must be a contiguous %s tensor of shape %s, got %s %s" % (name, x.dtype, oshape, tns.dtype, tuple(tns.shape)))
+    if ln_eps is not None and not float(ln_eps) >= 0.0:
+        raise CobevtHipError("typed_linear: ln_eps=%r must be >= 0" % (ln_eps,))
+    _need_cuda(x, w, bias, types, residual, out)
+    if out is None:
+        out = torch.empty(oshape, device=x.device, dtype=x.dtype)
+    esz = 2 if code == BF16 else 4
+    dims = (ctypes.c_long * 7)(code, g, rows, k, n, t, int(ln_eps is not None))
+    cost = lambda: (2.0 * m * n * k, float(esz * (m * k + t * n * k + m * n * (2 if residual is not None else 1))))         # noqa: E731
+    with _timed("typed_linear|G%d R=%d K=%d N=%d T=%d" % (g, rows, k, n, t), cost):
+        _L.call("cobevt_typed_linear", _p(x), _p(w), _p(bias), _p(types), _p(residual), _p(out), dims, ctypes.c_float(ln_eps or 0.0), _stream())
+    return out
+
+
+def hgt_attention(proj, types, heads, num_types, mask=None, out=None):
+    """The per-pixel typed agent attention in one cobevt_hgt_attention_nhwc launch: proj (B, L, H, W, (1 + 2 T) inner) contiguous in the
+    compute dtype with rows [q | k'_0 .. k'_(T-1) | v'_0 .. v'_(T-1)] (typed_linear on hgt_fold's w_in), inner = 32 heads; types
+    (B, L) int32 on the device (clamped to 0 .. T - 1 there); mask (B, H, W, L) contiguous fp32, 0 = key masked, or None
+    -> (B, L, H, W, inner).  A query whose keys are all masked gets zeros."""
+    code = dcode(proj.dtype)
+    heads, num_types = int(heads), int(num_types)
+    if proj.dim() != 5 or not proj.is_contiguous() or proj.numel() == 0:
+        raise CobevtHipError("hgt_attention: proj must be a contiguous non-empty (B, L, H, W, C) tensor, got %s (contiguous=%s)"
+                             % (tuple(proj.shape), proj.is_contiguous()))
+    b, l, h, w, c = (int(d) for d in proj.shape)
+    inner = 32 * heads
+    if heads < 1 or num_types < 1 or c != (1 + 2 * num_types) * inner:
+        raise CobevtHipError("hgt_attention: C=%d is not (1 + 2 T) * 32 heads for T=%d, heads=%d (dim_head = 32)" % (c, num_types, heads))
+    if l > HGT_MAX_AGENTS:
+        raise CobevtHipError("hgt_attention: %d agents exceed the kernel's %d" % (l, HGT_MAX_AGENTS))
+    if heads > 64 or num_types > 64:
+        raise CobevtHipError("hgt_attention: heads=%d / T=%d exceed the kernel's 64" % (heads, num_types))
+    if b * l > 65535:
+        raise CobevtHipError("hgt_attention: %d agent maps exceed the grid's 65535" % (b * l))
+    if types.dtype != torch.int32 or not types.is_contiguous() or types.numel() != b * l:
+        raise CobevtHipError("hgt_attention: types must be a contiguous int32 tensor of %d elements, got %s %s" % (b * l, types.dtype, tuple(types.shape)))
+    if mask is not None and (mask.dtype != torch.float32 or tuple(mask.shape) != (b, h, w, l) or not mask.is_contiguous()):
+        raise CobevtHipError("hgt_attention: mask must be a contiguous fp32 tensor of shape %s, got %s %s" % ((b, h, w, l), mask.dtype, tuple(mask.shape)))
+    oshape = (b, l, h, w, inner)
+    if out is not None and (tuple(out.shape) != oshape or out.dtype != proj.dtype or not out.is_contiguous()):
+        raise CobevtHipError("hgt_attention: out= must be a contiguous %s tensor of shape %s, got %s %s" % (proj.dtype, oshape, out.dtype, tuple(out.shape)))
+    _need_cuda(proj, types, mask, out)
+    if out is None:
+        out = torch.empty(oshape, device=proj.device, dtype=proj.dtype)
+    esz = 2 if code == BF16 else 4
+    px = b * h * w
+    cost = lambda: (4.0 * px * l * l * inner, float(esz * px * l * (inner + 2 * l * inner + inner)))         # noqa: E731
+    with _timed("hgt_attention|B%d L%d HW=%d heads=%d T=%d" % (b, l, h * w, heads, num_types), cost):
+        _L.call("cobevt_hgt_attention_nhwc", _p(proj), _p(types), _p(mask), _p(out), code, b, l, h * w, heads, num_types,
+                ctypes.c_float(32 ** -0.5), _stream())
+    return out
+
+
 # ---------------------------------------------------------------------------------------------- training of the transposed convolution
 # fp32 only, the native library (exact fp32 products).  Scratch buffers are cached per size like the sparse path's.
 def _deconv_geometry(cin, cout, s, what):

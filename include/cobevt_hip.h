@@ -425,6 +425,32 @@ int cobevt_att_fuse_nhwc(const void* x, const int* record_len, void* out, int dt
 int cobevt_att_fuse_bwd_nhwc(const float* x, const int* record_len, const float* dout, float* dx, int B, int N, long HW, int C, float scale,
                              hipStream_t stream);
 
+/* Typed agent attention (HGTCavAttention, base_transformer.py:175-319) in three row-local launches: typed projection, attention,
+ * typed output projection.  The 32 x 32 relation matrices are folded into the key / value projections by the host (ops.hgt_fold).
+ *
+ * cobevt_typed_linear:  y[row] = W[t] n(x[row]) + bias[t] (+ residual[row]).  The rows form G groups of R consecutive rows (one
+ * agent's H W pixels); t = clamp(types[g], 0, T - 1) is read on the device from int32 types[G], so any value of it reads inside W
+ * and bias.  n is the identity (ln = 0) or the LayerNorm normalisation (x - mean) rsqrt(var + ln_eps) without affine (ln = 1; the
+ * affine is folded into W and bias), rounded once to the storage type.  x (G R, K), residual and out (G R, N), W (T, N, K) in
+ * nn.Linear layout in the storage type (dtype 0 bf16 on v_mfma_f32_32x32x16_bf16, 1 fp32 on the exact v_mfma_f32_32x32x2_f32 in
+ * every library), bias (T, N) fp32.  fp32 accumulation, bias and residual added in fp32, one rounding.  A 32-row tile never mixes two
+ * groups and a tail tile stores nothing outside its group.  dims = [dtype, G, R, K, N, T, ln].
+ * COBEVT_ERR_ARG: a null pointer (residual may be null), dtype or ln not 0 / 1, ln_eps negative or NaN.  COBEVT_ERR_SHAPE: K or N
+ * not a positive multiple of 32, N > 2^20, G outside 1 .. 65535, R outside 1 .. 2^31 - 1, T outside 1 .. 65535, a pointer that is
+ * not 16-byte aligned (types: 4-byte).
+ * COBEVT_ERR_UNSUPPORTED: K > 512 with ln, K > 1024 without.  Everything is checked before the launch. */
+int cobevt_typed_linear(const void* x, const void* w, const float* bias, const int* types, const void* residual, void* out,
+                        const long* dims, float ln_eps, hipStream_t stream);
+/* cobevt_hgt_attention_nhwc: proj (B, L, HW, (1 + 2 T) inner) with rows [q | k'_0 .. k'_(T-1) | v'_0 .. v'_(T-1)], inner = 32 heads
+ * (dim_head = 32), types int32[B L] on the device, mask (B, HW, L) fp32 (0 = key masked) or null -> out (B, L, HW, inner).  Per
+ * pixel, head and query agent i with a = clamp(types[b L + i], 0, T - 1):  s_j = scale <q_i, k'_a of agent j> over the unmasked
+ * keys, out_i = sum_j softmax_j(s) v'_a of agent j.  fp32 arithmetic, accurate expf, running maximum, one rounding to the storage
+ * type; no atomics, bit-reproducible.  A query whose keys are ALL masked writes zeros (the reference's softmax over -inf gives NaN
+ * there).  COBEVT_ERR_ARG: a null pointer (mask may be null), dtype not 0 / 1.  COBEVT_ERR_SHAPE: B, L, HW, heads or T < 1,
+ * B L > 65535, misaligned pointers.  COBEVT_ERR_UNSUPPORTED: L > 8, heads > 64, T > 64. */
+int cobevt_hgt_attention_nhwc(const void* proj, const int* types, const float* mask, void* out, int dtype, int B, int L, long HW,
+                              int heads, int T, float scale, hipStream_t stream);
+
 /* regroup: split by record_len (device int32[B]), zero pad to max_cav, agent mask (B,max_cav) fp32.
  * Replaces fuse_utils.py:8-61 without its host synchronisation (:26). */
 int cobevt_regroup(const void* in, const int* record_len, void* out, float* mask, int dtype, int B, int max_cav,
