@@ -3,17 +3,16 @@
 The reference trains through torch autograd (opv2v/opencood/tools/train_camera.py:143-179: model.train(), loss.backward(),
 optimizer.step(); nuscenes/cross_view_transformer/model/model_module.py:35-60).  Here the attention core (gathered window / dilated-grid
 partition, relative-position bias, key mask, softmax, PV, partition reverse; optionally with its log-sum-exp as a differentiable output),
-LayerNorm, GELU, swish, every convolution and dense projection (implicit-GEMM forward / input gradient, cobevt_conv_wgrad[_blocked] weight
-gradient, operands prepared by csrc/train_prep.hip), the depthwise convolution, BatchNorm (+ residual + ReLU), max-pool, PixelUnshuffle,
-nearest / bilinear resizes, the STTF and pairwise warps and the losses run as HIP kernels in both directions - no vendor GEMM, no MIOpen.
-The attention / LayerNorm / GELU kernels compute in fp32 (their inputs are cast at the Function boundary under autocast, see _amp_fwd);
-the convolution family follows a bf16 autocast region (bf16 storage, fp32 master weights and gradients).
-
-No CPU path: every Function raises on CPU tensors (lib.CobevtHipError) like the inference ops do.
-
-Library variant: every launch below goes through `_call` or an `ops._launch_*(..., variant="")`, i.e. to the native library.
+LayerNorm, GELU, swish, every convolution and dense projection (Conv2dFn: the kernels of forward, input gradient and weight gradient and the
+operand preparation of csrc/train_prep.hip are named by ONE pure function, train_conv_route, which tests/test_launch_traces.py replays on the
+CPU), the depthwise convolution, BatchNorm (+ residual + ReLU), max-pool, PixelUnshuffle, nearest / bilinear resizes, the STTF and pairwise
+warps and the losses run as HIP kernels in both directions - no vendor GEMM, no MIOpen.  The attention / LayerNorm / GELU kernels compute in
+fp32 (their inputs are cast at the Function boundary under autocast, see _amp_fwd); the convolution family follows a bf16 autocast region (bf16
+storage, fp32 master weights and gradients).  No CPU path: every Function raises on CPU tensors (lib.CobevtHipError) like the inference ops do.
+Every launch below goes through `_call` or an `ops._launch_*(..., variant="")`, i.e. to the native library.
 """
 import ctypes
+from collections import namedtuple
 
 import torch
 
@@ -475,13 +474,11 @@ def column_sum(rows2d):
     partial sums per workgroup"""
     _need_cuda(rows2d)
     m, c = rows2d.shape
-    acc = torch.empty(c, device=rows2d.device, dtype=torch.float64)
+    acc, out = (torch.empty(c, device=rows2d.device, dtype=dt) for dt in (torch.float64, torch.float32))
     if c % 8:
-        out = torch.empty(c, device=rows2d.device, dtype=torch.float32)
         _call("cobevt_channel_sums", _p(rows2d), None, _p(acc), None, None, None, 0, ops.dcode(rows2d.dtype), m, c, _stream())
         _call("cobevt_f64_to_f32", _p(acc), _p(out), c, _stream())
         return out
-    out = torch.empty(c, device=rows2d.device, dtype=torch.float32)
     _call("cobevt_channel_sums", _p(rows2d), None, _p(acc), None, _p(out), _p(_scratch(c, rows2d.device)), _SCRATCH_BLOCKS,
           ops.dcode(rows2d.dtype), m, c, _stream())
     return out
@@ -491,9 +488,8 @@ USE_LIBRARY_GEMM = False     # True: nn.Linear through torch / rocBLAS (A/B runs
 
 
 def linear(x, lin):
-    """nn.Linear container on (..., K) rows.  A dense projection is a 1 x 1 convolution over a (1, rows, 1, K) channels-last map:
-    forward and input gradient on the implicit-GEMM kernel (csrc/igemm.hip), weight gradient on cobevt_conv_wgrad (a GEMM over the
-    rows), bias gradient a column sum - no vendor GEMM (VERDICT r02 #6; train_camera.py:143-179 runs these through cuBLAS)."""
+    """nn.Linear container on (..., K) rows.  A dense projection is a 1 x 1 convolution over a channels-last map of the rows (Conv2dFn, kernels
+    by train_conv_route), bias gradient a column sum - no vendor GEMM (VERDICT r02 #6; train_camera.py:143-179 runs these through cuBLAS)."""
     return linear_weight(x, lin.weight, lin.bias)
 
 
@@ -502,31 +498,21 @@ def linear_weight(x, weight, bias=None):
     _need_cuda(x)
     if USE_LIBRARY_GEMM:                           # explicit A/B switch only (tools/train_grad_diag.py): never taken by shape
         return torch.nn.functional.linear(x, weight, bias)
-    if x.shape[-1] % 4 or weight.shape[0] % 4:
+    k, n = x.shape[-1], weight.shape[0]
+    if k % 4 or n % 4:
         # widths off the kernels' 16-byte pieces: zero-pad K and / or the output width to the next multiple of 4 (memory ops with
         # exact adjoints - zero columns add nothing to a product) and run the SAME kernels; no library GEMM behind any shape
-        k, n = x.shape[-1], weight.shape[0]
         kp, npad = -(-k // 4) * 4, -(-n // 4) * 4
         F = torch.nn.functional
         y = linear_weight(F.pad(x, (0, kp - k)), F.pad(weight, (0, kp - k, 0, npad - n)), None if bias is None else F.pad(bias, (0, npad - n)))
         return y[..., :n]
-    k = x.shape[-1]
     rows = x.numel() // k
     # any (H, W) factorisation of the rows is the same 1 x 1 convolution; the blocked weight-gradient kernel walks 16-pixel blocks of
     # map rows and shares rows out over workgroups, so the rows are presented as an H x W map with a wide W (as (rows, 1) every
     # "map row" was one pixel padded to 16: 20 ms of padding copies per 5-agent step)
-    mh, mw = rows, 1
-    for cand in (256, 128, 64, 32, 16):
-        if rows % cand == 0 and rows // cand >= 4:
-            mh, mw = rows // cand, cand
-            break
-    x4 = x.reshape(1, mh, mw, k).permute(0, 3, 1, 2)                   # (1, K, H, W)-shaped view of channels-last memory
-    w4 = _master(weight)[:, :, None, None]
-    if torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.bfloat16:
-        with torch.autocast("cuda", enabled=False):
-            y = Conv2dFn.apply(x4.to(torch.bfloat16), w4, bias, 1, 0)
-    else:
-        y = Conv2dFn.apply(x4, w4, bias, 1, 0)
+    mw = next((cand for cand in (256, 128, 64, 32, 16) if rows % cand == 0 and rows // cand >= 4), 1)
+    x4 = x.reshape(1, rows // mw, mw, k).permute(0, 3, 1, 2)           # (1, K, H, W)-shaped view of channels-last memory
+    y = _apply_in_bf16_region(Conv2dFn, x4, _master(weight)[:, :, None, None], bias, 1, 0)
     return y.permute(0, 2, 3, 1).reshape(x.shape[:-1] + (weight.shape[0],))
 
 
@@ -534,6 +520,15 @@ def _master(weight):
     """The fp32 master copy the training convolutions take (a module kept in fp32 - the reference's --half loop keeps fp32 parameters
     under autocast - hands its parameter over as it is; anything else goes through a differentiable cast)"""
     return weight if weight.dtype == torch.float32 else weight.float()
+
+
+def _apply_in_bf16_region(fn, x, *args):
+    """fn.apply(x, *args) of a convolution Function; inside a bf16 autocast region on x cast to bf16, with autocast off: it computes in bf16 like
+    torch's own conv, from the fp32 master weights (the parameter receives an fp32 gradient).  fp16 regions stay on the fp32 kernels (_amp_fwd)."""
+    if _autocast_mode() == "bf16":
+        with torch.autocast("cuda", enabled=False):
+            return fn.apply(x.to(torch.bfloat16), *args)
+    return fn.apply(x, *args)
 
 
 def dropout(x, p):
@@ -552,8 +547,7 @@ def _weight_rows(weight):
     kernel's weight layout, produced ON THE DEVICE (a permute + pad) so that it follows the parameter through optimizer steps."""
     cout, cin, kh, kw = weight.shape
     K = kh * kw * cin
-    tile = 32 if weight.dtype == torch.bfloat16 else 16
-    kpad = (K + tile - 1) // tile * tile
+    kpad = _kpad(K, weight.dtype)
     w2 = weight.permute(0, 2, 3, 1).reshape(cout, K)
     if kpad != K:
         w2 = torch.nn.functional.pad(w2, (0, kpad - K))
@@ -576,9 +570,6 @@ def _kpad(K, dtype):
     return (K + tile - 1) // tile * tile
 
 
-USE_TORCH_OPERAND_PREP = False      # True: weight rows / blocked operands through the torch-op specifications (A/B and diagnostics only)
-
-
 def conv_weight_rows(weight, dtype, fwd=True, dgrad=False):
     """fp32 master weight (Cout, Cin, kh, kw) -> (rows_fwd [Cout][Kpad] | None, rows_dgrad [Cin][Kpad'] | None) in `dtype`: ONE launch of
     cobevt_conv_weight_rows (csrc/train_prep.hip) instead of cast + permute + pad (+ flip + transpose + permute + pad) per convolution and
@@ -591,8 +582,7 @@ def conv_weight_rows(weight, dtype, fwd=True, dgrad=False):
     kpf, kpd = _kpad(kh * kw * cin, dtype), _kpad(kh * kw * cout, dtype)
     rf = torch.empty((cout, kpf), device=w.device, dtype=dtype) if fwd else None
     rd = torch.empty((cin, kpd), device=w.device, dtype=dtype) if dgrad else None
-    dims = _ints([ops.dcode(dtype), cout, cin, kh, kw, kpf, kpd])
-    _call("cobevt_conv_weight_rows", _p(w), _p(rf), _p(rd), dims, _stream())
+    _call("cobevt_conv_weight_rows", _p(w), _p(rf), _p(rd), _ints([ops.dcode(dtype), cout, cin, kh, kw, kpf, kpd]), _stream())
     return rf, rd
 
 
@@ -610,37 +600,30 @@ def _igemm_rows(x, w2, cout, cin, kh, kw, bias, stride, pad, ho, wo):
     return out
 
 
-USE_WGRAD3 = True             # bf16 3x3 / stride-1 weight gradients straight from the channels-last maps (csrc/wgrad3.hip)
-USE_TRAIN_STRIPS = True       # bf16 3x3 / pad-1 convolutions with 64 | Cin: forward and (stride 1) input gradient on the inference kernels
-
-
 def conv3_weight_operand(weight, variant, dgrad):
     """fp32 master weight (Cout, Cin, 3, 3) -> the bf16 operand that `variant` reads (csrc/train_prep.hip), for the forward convolution or
     (dgrad) for its input gradient = the convolution with the channel roles swapped and the taps flipped.  Specification:
     ops.ConvPlan(weight or weight.flip(2, 3).transpose(0, 1), ...).wfrag / .wgt3."""
     cout, cin = weight.shape[:2]
-    o, i = (cin, cout) if dgrad else (cout, cin)
     w = _f32c(weight.detach(), "weight")
-    if variant:
-        op = torch.empty(((o + 127) // 128 * 4, i // 64, 9, 4, 64, 8), device=w.device, dtype=torch.bfloat16)
-    else:
-        op = torch.empty((o, i // 64, 9, 64), device=w.device, dtype=torch.bfloat16)
+    op = _conv3_operand_buffer(cin, cout, variant, w.device) if dgrad else _conv3_operand_buffer(cout, cin, variant, w.device)
     _call("cobevt_conv3_weight_operands", _p(w), _p(op) if variant else None, None if variant else _p(op), _ints([cout, cin, int(dgrad)]),
           _stream())
     return op
+
+
+def _conv3_operand_buffer(o, i, variant, device):
+    """the bf16 table of an (o out, i in) 3x3 convolution: the fragment table of a strip variant, or (variant 0) the LDS-staged kernel's rows"""
+    shape = ((o + 127) // 128 * 4, i // 64, 9, 4, 64, 8) if variant else (o, i // 64, 9, 64)
+    return torch.empty(shape, device=device, dtype=torch.bfloat16)
 
 
 def conv3_weight_operand_pair(weight, var_f, var_d):
     """conv3_weight_operand(weight, var_f, False) and (var_d >= 0) conv3_weight_operand(weight, var_d, True) from ONE launch"""
     cout, cin = weight.shape[:2]
     w = _f32c(weight.detach(), "weight")
-
-    def buf(o, i, variant):
-        if variant:
-            return torch.empty(((o + 127) // 128 * 4, i // 64, 9, 4, 64, 8), device=w.device, dtype=torch.bfloat16)
-        return torch.empty((o, i // 64, 9, 64), device=w.device, dtype=torch.bfloat16)
-    f = buf(cout, cin, var_f)
-    d = buf(cin, cout, var_d) if var_d >= 0 else None
+    f = _conv3_operand_buffer(cout, cin, var_f, w.device)
+    d = _conv3_operand_buffer(cin, cout, var_d, w.device) if var_d >= 0 else None
     outs = (ctypes.c_void_p * 4)(f.data_ptr() if var_f else None, None if var_f else f.data_ptr(),
                                  d.data_ptr() if (d is not None and var_d) else None, d.data_ptr() if (d is not None and not var_d) else None)
     _call("cobevt_conv3_weight_operands2", _p(w), outs, _ints([cout, cin]), _stream())
@@ -656,9 +639,6 @@ def _conv3_strips(x, operand, variant, cout, bias, stride):
     b = None if bias is None else _f32c(bias.detach().float(), "bias")
     ops._launch_conv3x3(x, operand, b, None, out, cout=cout, tile=variant, stride=stride, variant="")
     return out
-
-
-USE_TRAIN_ROWS_GEMM = True    # bf16 dense projections / 1x1 stride-1 convolutions with K, N <= 512: forward and input gradient on the inference row GEMM
 
 
 def linear_weight_frags(weight2d, forward=True, transposed=False):
@@ -680,10 +660,6 @@ def _rows_gemm(x2d, frag, n_out, k_in, bias):
     b = None if bias is None else _f32c(bias.detach().float(), "bias")
     ops._launch_rows(x2d.reshape(1, m, 1, k_in), frag, b, None, None, None, out.view(1, m, 1, n_out), rows=32, variant="")
     return out
-
-
-USE_WGRAD_BLOCKED = True      # bf16: weight gradient on the bf16 matrix path (cobevt_conv_wgrad_blocked) where wgrad_blocked_mode() has a form for it
-USE_WGRAD_BLOCKED_STRIDED = True   # ... incl. the stride-2 and stem forms (modes 1 / 2); False: those stay on cobevt_conv_wgrad (A/B runs)
 
 
 def _blocked_operands(xl, dyl, k, pad):
@@ -754,15 +730,104 @@ def blocked_operands(xl, dyl, k, pad, stride=1, mode=0):
     return xb, db, hp, nxb, ndb
 
 
+# the switches of the training convolutions (A/B runs and diagnostics; COBEVT_TRAIN_FLAGS): train_conv_route reads the first five
+USE_TRAIN_ROWS_GEMM = True    # bf16 dense projections / 1x1 stride-1 convolutions with K, N <= 512: forward and input gradient on the inference row GEMM
+USE_TRAIN_STRIPS = True       # bf16 3x3 / pad-1 convolutions with 64 | Cin: forward and (stride 1) input gradient on the inference kernels
+USE_WGRAD3 = True             # bf16 3x3 / stride-1 weight gradients straight from the channels-last maps (csrc/wgrad3.hip)
+USE_WGRAD_BLOCKED = True      # bf16: weight gradient on the bf16 matrix path (cobevt_conv_wgrad_blocked) where wgrad_blocked_mode() has a form for it
+USE_WGRAD_BLOCKED_STRIDED = True   # ... incl. the stride-2 and stem forms (modes 1 / 2); False: those stay on cobevt_conv_wgrad (A/B runs)
+USE_TORCH_OPERAND_PREP = False      # True: weight rows / blocked operands through the torch-op specifications (A/B and diagnostics only)
+TrainConvRoute = namedtuple("TrainConvRoute", "fwd var_f dgrad var_d prep wgrad wgrad_mode")
+
+
+def train_conv_route(code, n, h, w, cin, cout, k, stride, pad, x_grad=True, w_grad=True):
+    """What Conv2dFn launches for a k x k convolution of an (n, h, w, cin) map of dtype `code` to cout channels - from these arguments, the USE_*
+    switches of this module and ops.conv3_variant alone (training is always the native library).  fwd / var_f: the forward kernel, "rows" (the
+    inference row GEMM), "strips" with its variant, "conv3" (the LDS-staged 3x3 kernel, variant 0) or "igemm".  dgrad / var_d: the same for the
+    input gradient (the stride-1 convolution of the zero-stuffed output gradient, taps flipped, channel roles swapped), None when x takes none.
+    prep: the operand-preparation calls (keys of _PREP), the first before the forward launch, a second - the input gradient's own - after it.
+    wgrad: the weight-gradient forms (_wgrad_chunked, _wgrad_atomics) in the order tried: "chunked" steps aside when its chunk question answers <= 0, "blocked"
+    (in form wgrad_mode) or "generic" takes every shape; () when the weight takes no gradient."""
+    bf16 = code == ops.BF16
+    fwd, var_f, dgrad, var_d = "igemm", 0, ("igemm" if x_grad else None), 0
+    c3 = USE_TRAIN_STRIPS and bf16 and k == 3 and pad == 1
+    if USE_TRAIN_ROWS_GEMM and bf16 and (k, stride, pad) == (1, 1, 0) and cin % 8 == 0 and cout % 8 == 0 and cin <= 512 and cout <= 512:
+        fwd, dgrad = "rows", ("rows" if x_grad else None)
+    if c3 and stride in (1, 2) and cin % 64 == 0 and cout % 8 == 0 and n * h * w * cin < 2 ** 31:
+        var_f = ops.conv3_variant(n, (h - 1) // stride + 1, (w - 1) // stride + 1, cin, cout, 64, stride)
+        fwd = "strips" if var_f else "conv3"
+    # the input gradient of a stride-1 convolution is a 3x3 / pad-1 convolution again (Cout -> Cin channels)
+    if c3 and x_grad and stride == 1 and cout % 64 == 0 and cin % 8 == 0 and n * h * w * cout < 2 ** 31:
+        var_d = ops.conv3_variant(n, h, w, cout, cin, 64, 1)
+        dgrad = "strips" if var_d else "conv3"
+    # (beside a 3x3 forward the weight-rows call is made even when x takes no gradient: it then has no output)
+    d3 = dgrad in ("strips", "conv3")
+    prep = (("weight_rows",) + ("operand",) * d3) if fwd == "igemm" else (("pair",) + ("weight_rows",) * (not d3))
+    prep = ("frags",) if fwd == "rows" else prep
+    mode = wgrad_blocked_mode(k, stride, pad, cin) if (USE_WGRAD_BLOCKED and bf16) else None
+    if mode in (1, 2) and not USE_WGRAD_BLOCKED_STRIDED:
+        mode = None
+    chunked = bool(USE_WGRAD3 and bf16 and stride == 1 and (k, pad) in ((3, 1), (1, 0)))
+    wgrad = (("chunked",) * chunked + ("generic" if mode is None else "blocked",)) if w_grad else ()
+    return TrainConvRoute(fwd, var_f, dgrad, var_d, prep, wgrad, mode if w_grad else None)
+
+
+def _train_conv_launch(kernel, variant, x, operand, cout, k, bias, stride, pad, ho, wo):
+    """x (N, H, W, Cin) channels-last through `kernel` (a word of train_conv_route) -> (N, ho, wo, cout)"""
+    if kernel == "rows":           # a dense projection: weights resident per workgroup, rows streamed once
+        return _rows_gemm(x.reshape(-1, x.shape[3]), operand, cout, x.shape[3], bias).reshape(x.shape[0], ho, wo, cout)
+    if kernel in ("strips", "conv3"):
+        return _conv3_strips(x, operand, variant, cout, bias, stride)
+    return _igemm_rows(x, operand, cout, x.shape[3], k, k, bias, stride, pad, ho, wo)
+
+
+def _launch_conv_wgrad(x, dy, dw, k, stride, pad):
+    """zeroed fp32 dw (Cout, Cin, k, k) += the weight gradient of the k x k convolution x (N, H, W, Cin) -> dy (N, Ho, Wo, Cout), channels-last, both
+    fp32 or both bf16 (the code sent is x's dtype; DeconvFn hands over fp32 maps): cobevt_conv_wgrad (csrc/train_rows.hip, fp32 atomics).  Returns dw."""
+    dims = _ints([x.shape[0], x.shape[1], x.shape[2], x.shape[3], dy.shape[1], dy.shape[2], dy.shape[3], k, stride, pad, ops.dcode(x.dtype)])
+    _call("cobevt_conv_wgrad", _p(x), _p(dy), _p(dw), dims, _stream())
+    return dw
+
+
+def _wgrad_chunked(xl, dyl, k):
+    """bf16, stride 1 (csrc/wgrad3.hip): a dense projection (k = 1: dy^T x over the rows) or a 3x3 straight from the channels-last maps; dw written,
+    partial sums in a scratch buffer.  The C side says how many chunks the shape takes (a pure function of it); <= 0: not this form (None)"""
+    (n, h, w, cin), cout = xl.shape, dyl.shape[3]
+    name, shape, ctype = ("cobevt_linear_wgrad", [n * h * w, cin, cout], ctypes.c_long) if k == 1 else \
+        ("cobevt_conv_wgrad3", [n, h, w, cin, cout], ctypes.c_int)
+    chunks = getattr(_L.load(""), name + "_chunks")((ctype * len(shape))(*shape))
+    if chunks <= 0:
+        return None
+    dw = torch.empty((cout, cin, k, k), device=dyl.device, dtype=torch.float32)
+    scratch = torch.empty((chunks, cout * cin * k * k), device=dyl.device, dtype=torch.float32)
+    _call(name, _p(xl), _p(dyl), _p(dw), _p(scratch), (ctype * (len(shape) + 1))(*shape, chunks), _stream())
+    return dw
+
+
+def _wgrad_atomics(xl, dyl, k, stride, pad, mode):
+    """every shape, into a zeroed dw: the bf16 matrix path on the blocked operands in form `mode` (wgrad_blocked_mode), or (None) cobevt_conv_wgrad"""
+    dw = _zeros((dyl.shape[3], xl.shape[3], k, k), dyl.device, torch.float32)
+    if mode is None:
+        return _launch_conv_wgrad(xl, dyl, dw, k, stride, pad)
+    x_blk, dy_blk, hp, nxb, ndb = blocked_operands(xl, dyl, k, pad, stride, mode)
+    dims = _ints([xl.shape[0], hp, nxb, xl.shape[3], dyl.shape[1], ndb, dyl.shape[3], k, stride, mode])
+    _call("cobevt_conv_wgrad_blocked", _p(x_blk), _p(dy_blk), _p(dw), dims, _stream())
+    return dw
+
+
+# one operand-preparation call on the fp32 master weight -> (forward operand | None, input-gradient operand | None)
+_PREP = {"frags": lambda wt, dtype, r: linear_weight_frags(wt.reshape(wt.shape[:2]), True, r.dgrad == "rows"),
+         "pair": lambda wt, dtype, r: conv3_weight_operand_pair(wt, r.var_f, r.var_d if r.dgrad in ("strips", "conv3") else -1),
+         "operand": lambda wt, dtype, r: (None, conv3_weight_operand(wt, r.var_d, True)),
+         "weight_rows": lambda wt, dtype, r: conv_weight_rows(wt, dtype, r.fwd == "igemm", r.dgrad == "igemm")}
+
+
 class Conv2dFn(torch.autograd.Function):
     """nn.Conv2d (square kernel, symmetric padding, groups 1) on (N, C, H, W)-shaped tensors (channels-last memory is used as it
-    is).  Forward and the input gradient run on the implicit-GEMM kernel (the input gradient is the same convolution with the
-    taps flipped and the channel roles swapped, on the zero-stuffed output gradient when stride > 1); the weight gradient is
-    cobevt_conv_wgrad (csrc/train_rows.hip: a GEMM over the pixels on the fp32 matrix path, operands straight from global memory)
-    or cobevt_conv_wgrad_blocked (bf16 matrix path).  weight / bias are the fp32 MASTER parameters; x is fp32, or bf16 - which is
-    what conv2d() hands over inside a bf16 autocast region: bf16 storage, the bf16 matrix instructions in forward / input gradient,
-    fp32 accumulation of the weight gradient.  The weight rows of both directions are made from the master weight by one launch
-    (conv_weight_rows), the gradients of weight and bias are returned in fp32: no cast nodes in the autograd graph."""
+    is).  forward computes train_conv_route once and keeps it on ctx; both methods only dispatch on it.  weight / bias are the fp32
+    MASTER parameters; x is fp32, or bf16 - which is what conv2d() hands over inside a bf16 autocast region: bf16 storage, the bf16
+    matrix instructions in forward / input gradient, fp32 accumulation of the weight gradient.  The operands of both directions are
+    made from the master weight (_PREP), the gradients of weight and bias are returned in fp32: no cast nodes in the autograd graph."""
 
     @staticmethod
     @_amp_fwd
@@ -771,89 +836,40 @@ class Conv2dFn(torch.autograd.Function):
         if weight.dtype != torch.float32 or x.dtype not in (torch.float32, torch.bfloat16):
             raise CobevtHipError("training conv2d: fp32 master weight, x fp32 or bf16 (got %s, %s)" % (weight.dtype, x.dtype))
         xl = x.permute(0, 2, 3, 1).contiguous()
-        n, h, w, _ = xl.shape
-        cout, cin, kh, kw = weight.shape
-        ho, wo = (h + 2 * pad - kh) // stride + 1, (w + 2 * pad - kw) // stride + 1
-        strips = (USE_TRAIN_STRIPS and xl.dtype == torch.bfloat16 and kh == 3 and kw == 3 and pad == 1 and stride in (1, 2) and cin % 64 == 0
-                  and cout % 8 == 0 and xl.numel() < 2 ** 31)
-        # the input gradient of a stride-1 convolution is a 3x3 / pad-1 convolution again (Cout -> Cin channels)
-        strips_d = USE_TRAIN_STRIPS and xl.dtype == torch.bfloat16 and kh == 3 and kw == 3 and pad == 1 and stride == 1 and cout % 64 == 0 \
-            and cin % 8 == 0 and n * h * w * cout < 2 ** 31
-        need_d = ctx.needs_input_grad[0]
-        var_d = ops.conv3_variant(n, h, w, cout, cin, 64, 1) if (strips_d and need_d) else -1
-        rows = (USE_TRAIN_ROWS_GEMM and xl.dtype == torch.bfloat16 and kh == 1 and kw == 1 and stride == 1 and pad == 0 and cin % 8 == 0
-                and cout % 8 == 0 and cin <= 512 and cout <= 512)
-        if rows:
-            # a dense projection: the inference row GEMM both ways (weights resident per workgroup, rows streamed once)
-            frag_f, rows_d = linear_weight_frags(weight.reshape(cout, cin), True, need_d)
-            out = _rows_gemm(xl.reshape(-1, cin), frag_f, cout, cin, bias).reshape(n, ho, wo, cout)
-            var_d = -2 if need_d else -1
-        elif strips:
-            var_f = ops.conv3_variant(n, ho, wo, cin, cout, 64, stride)      # 0: the LDS-staged kernel (reads `rows3`), else `frag`
-            op_f, op_d = conv3_weight_operand_pair(weight, var_f, var_d)      # both directions' operands from one launch
-            out = _conv3_strips(xl, op_f, var_f, cout, bias, stride)
-            rows_d = op_d if var_d >= 0 else conv_weight_rows(weight, xl.dtype, False, need_d)[1]
-        else:
-            rows_f, rows_d = conv_weight_rows(weight, xl.dtype, True, need_d and var_d < 0)
-            out = _igemm_rows(xl, rows_f, cout, cin, kh, kw, bias, stride, pad, ho, wo)
-            if var_d >= 0:
-                rows_d = conv3_weight_operand(weight, var_d, True)
-        ctx.save_for_backward(xl, rows_d)
-        ctx.cfg = (stride, pad, bias is not None, tuple(weight.shape))
-        ctx.var_d = var_d
-        ctx.bias_dtype = None if bias is None else bias.dtype
+        (n, h, w, _), (cout, cin, k, kw) = xl.shape, weight.shape
+        if k != kw:
+            raise CobevtHipError("training conv2d: square kernels only (got %d x %d)" % (k, kw))
+        ho, wo = (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1
+        r = train_conv_route(ops.dcode(xl.dtype), n, h, w, cin, cout, k, stride, pad, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        op_f, op_d = _PREP[r.prep[0]](weight, xl.dtype, r)
+        out = _train_conv_launch(r.fwd, r.var_f, xl, op_f, cout, k, bias, stride, pad, ho, wo)
+        for call in r.prep[1:]:                  # the input gradient's own operand, where the first call cannot make it
+            op_d = _PREP[call](weight, xl.dtype, r)[1]
+        ctx.save_for_backward(xl, op_d)
+        ctx.cfg = (r, stride, pad, cout, k, None if bias is None else bias.dtype)
         return out.permute(0, 3, 1, 2)
 
     @staticmethod
     @_amp_bwd
     def backward(ctx, dy):
-        xl, rows_d = ctx.saved_tensors
-        stride, pad, has_bias, (cout, cin, kh, kw) = ctx.cfg
-        n, h, w, _ = xl.shape
+        xl, op_d = ctx.saved_tensors
+        r, stride, pad, cout, k, bias_dtype = ctx.cfg
+        n, h, w, cin = xl.shape
         dyl = dy.to(xl.dtype).permute(0, 2, 3, 1).contiguous()
         ho, wo = dyl.shape[1:3]
         dx = dw = db = None
-        if ctx.needs_input_grad[0]:
+        if r.dgrad is not None:
             g = dyl
             if stride > 1:                       # zero-stuffed gradient map: dgrad of a strided conv = stride-1 conv on it
                 g = torch.zeros((n, (ho - 1) * stride + 1, (wo - 1) * stride + 1, cout), device=dyl.device, dtype=dyl.dtype)
                 g[:, ::stride, ::stride] = dyl
-            if ctx.var_d == -2:
-                dx = _rows_gemm(g.reshape(-1, cout), rows_d, cin, cout, None).reshape(n, h, w, cin).permute(0, 3, 1, 2)
-            elif ctx.var_d >= 0:
-                dx = _conv3_strips(g, rows_d, ctx.var_d, cin, None, 1).permute(0, 3, 1, 2)
-            else:
-                dx = _igemm_rows(g, rows_d, cin, cout, kh, kw, None, 1, kh - 1 - pad, h, w).permute(0, 3, 1, 2)
-        chunks3 = -1
-        if ctx.needs_input_grad[1] and USE_WGRAD3 and xl.dtype == torch.bfloat16 and kh == 3 and kw == 3 and stride == 1 and pad == 1:
-            chunks3 = _L.load("").cobevt_conv_wgrad3_chunks(_ints([n, h, w, cin, cout]))
-        chunks1 = -1
-        if ctx.needs_input_grad[1] and USE_WGRAD3 and xl.dtype == torch.bfloat16 and kh == 1 and kw == 1 and stride == 1 and pad == 0:
-            chunks1 = _L.load("").cobevt_linear_wgrad_chunks((ctypes.c_long * 3)(n * h * w, cin, cout))
-        if chunks1 > 0:
-            # a dense projection: dy^T x over the rows (csrc/wgrad3.hip), dw written, partial sums in a scratch buffer
-            dw = torch.empty((cout, cin, 1, 1), device=dyl.device, dtype=torch.float32)
-            scratch = torch.empty((chunks1, cout * cin), device=dyl.device, dtype=torch.float32)
-            _call("cobevt_linear_wgrad", _p(xl), _p(dyl), _p(dw), _p(scratch), (ctypes.c_long * 4)(n * h * w, cin, cout, chunks1), _stream())
-        elif chunks3 > 0:
-            # straight from the channels-last maps (csrc/wgrad3.hip): dw is written, partial sums in a scratch buffer
-            dw = torch.empty((cout, cin, kh, kw), device=dyl.device, dtype=torch.float32)
-            scratch = torch.empty((chunks3, cout * cin * 9), device=dyl.device, dtype=torch.float32)
-            _call("cobevt_conv_wgrad3", _p(xl), _p(dyl), _p(dw), _p(scratch), _ints([n, h, w, cin, cout, chunks3]), _stream())
-        elif ctx.needs_input_grad[1]:
-            dw = _zeros((cout, cin, kh, kw), dyl.device, torch.float32)
-            mode = wgrad_blocked_mode(kh, stride, pad, cin) if (USE_WGRAD_BLOCKED and xl.dtype == torch.bfloat16 and kh == kw) else None
-            if mode is not None and not USE_WGRAD_BLOCKED_STRIDED and mode != 0:
-                mode = None
-            if mode is not None:
-                x_blk, dy_blk, hp, nxb, ndb = blocked_operands(xl, dyl, kh, pad, stride, mode)
-                dims = _ints([n, hp, nxb, cin, ho, ndb, cout, kh, stride, mode])
-                _call("cobevt_conv_wgrad_blocked", _p(x_blk), _p(dy_blk), _p(dw), dims, _stream())
-            else:
-                dims = _ints([n, h, w, cin, ho, wo, cout, kh, stride, pad, ops.BF16 if xl.dtype == torch.bfloat16 else ops.FP32])
-                _call("cobevt_conv_wgrad", _p(xl), _p(dyl), _p(dw), dims, _stream())
-        if has_bias and ctx.needs_input_grad[2]:
-            db = column_sum(dyl.reshape(-1, cout)).to(ctx.bias_dtype)
+            dx = _train_conv_launch(r.dgrad, r.var_d, g, op_d, cin, k, None, 1, k - 1 - pad, h, w).permute(0, 3, 1, 2)
+        for form in r.wgrad:
+            dw = _wgrad_chunked(xl, dyl, k) if form == "chunked" else _wgrad_atomics(xl, dyl, k, stride, pad, r.wgrad_mode)
+            if dw is not None:
+                break
+        if bias_dtype is not None and ctx.needs_input_grad[2]:
+            db = column_sum(dyl.reshape(-1, cout)).to(bias_dtype)
         return dx, dw, db, None, None
 
 
@@ -863,13 +879,7 @@ def conv2d(x, conv, pad=None):
     if conv.groups != 1 or conv.dilation != (1, 1) or conv.kernel_size[0] != conv.kernel_size[1] or conv.stride[0] != conv.stride[1] \
             or conv.padding[0] != conv.padding[1]:
         raise CobevtHipError("training conv2d: square kernel / stride / padding, groups 1, dilation 1 only")
-    pad = conv.padding[0] if pad is None else int(pad)
-    if torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.bfloat16:
-        # a bf16 autocast region: the convolution computes in bf16 like torch's own conv would, from the fp32 master weights (the
-        # parameter receives an fp32 gradient); fp16 regions stay on the fp32 kernels (_amp_fwd)
-        with torch.autocast("cuda", enabled=False):
-            return Conv2dFn.apply(x.to(torch.bfloat16), _master(conv.weight), conv.bias, conv.stride[0], pad)
-    return Conv2dFn.apply(x, _master(conv.weight), conv.bias, conv.stride[0], pad)
+    return _apply_in_bf16_region(Conv2dFn, x, _master(conv.weight), conv.bias, conv.stride[0], conv.padding[0] if pad is None else int(pad))
 
 
 # ----------------------------------------------------------------------------------------------
@@ -1324,10 +1334,7 @@ def depthwise_conv2d(x, conv, pad):
     """x through the depthwise nn.Conv2d container `conv` (groups == channels, no bias) with static "same" padding pad = (before, after)"""
     if conv.groups != conv.in_channels or conv.bias is not None or conv.kernel_size[0] != conv.kernel_size[1] or conv.stride[0] != conv.stride[1]:
         raise CobevtHipError("training depthwise conv: groups == channels, square kernel / stride, no bias")
-    if torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.bfloat16:
-        with torch.autocast("cuda", enabled=False):
-            return DepthwiseConvFn.apply(x.to(torch.bfloat16), _master(conv.weight), conv.stride[0], tuple(pad))
-    return DepthwiseConvFn.apply(x, _master(conv.weight), conv.stride[0], tuple(pad))
+    return _apply_in_bf16_region(DepthwiseConvFn, x, _master(conv.weight), conv.stride[0], tuple(pad))
 
 
 class ResizeBilinearFn(torch.autograd.Function):
@@ -1416,10 +1423,7 @@ class PairwiseWarpFn(torch.autograd.Function):
 def conv2d_weight(x, weight, bias, stride=1, pad=0):
     """the training convolution on a weight TENSOR (a differentiable function of parameters: sliced / re-indexed taps) instead of an
     nn.Conv2d container"""
-    if torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.bfloat16:
-        with torch.autocast("cuda", enabled=False):
-            return Conv2dFn.apply(x.to(torch.bfloat16), _master(weight).contiguous(), bias, stride, pad)
-    return Conv2dFn.apply(x, _master(weight).contiguous(), bias, stride, pad)
+    return _apply_in_bf16_region(Conv2dFn, x, _master(weight).contiguous(), bias, stride, pad)
 
 
 # ----------------------------------------------------------------------------------------------
@@ -1694,13 +1698,9 @@ class DeconvFn(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             dx = _igemm_rows(dzl, rows, cin, cout, s, s, None, s, 0, h, w).permute(0, 3, 1, 2)
         if ctx.needs_input_grad[1]:
-            if USE_DECONV_WGRAD:
-                dw = ops.deconv_wgrad(xl, dzl, s)
-            else:
-                # the same tensor as the weight gradient of the convolution dz -> x: (out = Cin, in = Cout, s, s), fp32 atomics
-                dw = _zeros((cin, cout, s, s), dzl.device, torch.float32)
-                dims = _ints([n, s * h, s * w, cout, h, w, cin, s, s, 0, ops.FP32])
-                _call("cobevt_conv_wgrad", _p(dzl), _p(xl), _p(dw), dims, _stream())
+            # (switched off: the same tensor as the weight gradient of the convolution dz -> x, (out = Cin, in = Cout, s, s), fp32 atomics)
+            dw = ops.deconv_wgrad(xl, dzl, s) if USE_DECONV_WGRAD else \
+                _launch_conv_wgrad(dzl, xl, _zeros((cin, cout, s, s), dzl.device, torch.float32), s, s, 0)
         return dx, dw, None
 
 

@@ -112,6 +112,73 @@ STRIPS_PLAN = ((1, 32, 32, 128, 128, 1, 0), (20, 64, 64, 128, 128, 1, 0), (5, 64
 DTYPES = {"bf16": torch.bfloat16, "fp32": torch.float32}
 
 
+# ---- the routing table of the TRAINING convolutions (tests/launch_trace.py case `train_conv_table`): autograd.Conv2dFn forward and
+# backward, one row per branch.  x = channels-last input shape (n, h, w, cin); knobs = autograd.USE_* switches set for the row;
+# variant = ops.CONV3_VARIANT; chunks = what the fake library answers to the two *_chunks questions (0 when not named);
+# linear = the weight shape (N, K) of a row that goes through autograd.linear_weight instead (x is then (..., K)), and as_conv = the
+# 1 x 1 convolution it must arrive as: (h, w, cin, cout) of a one-image map.
+def trow(name, x, cout=None, k=1, stride=1, pad=0, dt="bf16", bias=True, x_grad=True, w_grad=True, knobs=None, variant=0, chunks=None,
+         linear=None, as_conv=None):
+    return dict(name=name, x=x, cout=cout, k=k, stride=stride, pad=pad, dt=dt, bias=bias, x_grad=x_grad, w_grad=w_grad, knobs=knobs or {},
+                variant=variant, chunks=chunks or {}, linear=linear, as_conv=as_conv)
+
+
+def train_conv_args(r):
+    """the arguments of autograd.train_conv_route for a row, after the dtype code: (n, h, w, cin, cout, k, stride, pad, x_grad, w_grad)"""
+    n, h, w, cin, cout = ((1,) + r["as_conv"]) if r["linear"] else (r["x"] + (r["cout"],))
+    return (n, h, w, cin, cout, r["k"], r["stride"], r["pad"], r["x_grad"], r["w_grad"])
+
+
+X8, X16 = (2, 8, 8), (2, 16, 16)
+C3 = dict(k=3, pad=1)
+C3S2 = dict(k=3, stride=2, pad=1)
+LIN_CHUNKS, C3_CHUNKS = "cobevt_linear_wgrad_chunks", "cobevt_conv_wgrad3_chunks"
+
+TRAIN_ROWS = (
+    # ---- forward and input gradient, bf16 (both chunk questions answered 0: the weight gradient falls to the blocked / generic kernel)
+    trow("1x1", X8 + (128,), 32),                                                   # the row GEMM both ways; blocked mode 0
+    trow("1x1_rows_gemm_off", X8 + (128,), 32, bias=False, knobs={"USE_TRAIN_ROWS_GEMM": False}),
+    trow("1x1_cin520", X8 + (520,), 32),                                            # over the 512 cap
+    trow("1x1_cout12", X8 + (64,), 12),                                             # 12 % 8 != 0; the bias gradient through cobevt_f64_to_f32
+    trow("1x1_s2", X8 + (64,), 128, stride=2),                                      # shortcut conv: zero-stuffed dgrad, blocked mode 1
+    trow("3x3", X16 + (64,), 64, **C3),                                             # strips both ways, operands from the paired launch
+    trow("3x3_cout32", X16 + (64,), 32, bias=False, **C3),                          # strips forward, implicit-GEMM dgrad
+    trow("3x3_cin8", X16 + (8,), 64, **C3),                                         # implicit-GEMM forward, strips dgrad
+    trow("3x3_cout48", X16 + (64,), 48, **C3),                                      # forward variant 0: the LDS-staged kernel
+    trow("3x3_cin48", X16 + (48,), 64, **C3),                                       # dgrad variant 0
+    trow("3x3_s2", X16 + (64,), 128, **C3S2),                                       # stride-2 strips, zero-stuffed dgrad, blocked mode 1
+    trow("3x3_strips_off", X16 + (64,), 64, knobs={"USE_TRAIN_STRIPS": False}, **C3),
+    trow("3x3_variant140", X16 + (64,), 64, variant=140, **C3),
+    trow("stem", X16 + (3,), 64, k=7, stride=2, pad=3),                             # klut gather path (x widened to fp32); blocked mode 2
+    trow("5x5", X16 + (64,), 64, k=5, pad=2),                                       # no blocked form: the generic kernel, bf16 code
+    trow("3x3_s2_p0", X16 + (64,), 64, k=3, stride=2),
+    trow("3x3_x_no_grad", X16 + (64,), 64, x_grad=False, **C3),
+    # ---- weight gradient, bf16
+    trow("1x1_linear_wgrad", X8 + (128,), 32, chunks={LIN_CHUNKS: 3}),
+    trow("3x3_wgrad3", X16 + (64,), 64, chunks={C3_CHUNKS: 4}, **C3),
+    trow("3x3_wgrad3_refused", X16 + (64,), 64, chunks={C3_CHUNKS: -4}, **C3),
+    trow("3x3_wgrad3_off", X16 + (64,), 64, knobs={"USE_WGRAD3": False}, chunks={C3_CHUNKS: 4}, **C3),
+    trow("1x1_wgrad3_off", X8 + (128,), 32, knobs={"USE_WGRAD3": False}, chunks={LIN_CHUNKS: 3}),
+    trow("3x3_s2_blocked_strided_off", X16 + (64,), 128, knobs={"USE_WGRAD_BLOCKED_STRIDED": False}, **C3S2),
+    trow("3x3_blocked_strided_off", X16 + (64,), 64, knobs={"USE_WGRAD_BLOCKED_STRIDED": False}, **C3),       # mode 0 stays blocked
+    trow("3x3_blocked_off", X16 + (64,), 64, knobs={"USE_WGRAD_BLOCKED": False}, **C3),
+    trow("1x1_blocked_off", X8 + (128,), 32, knobs={"USE_WGRAD_BLOCKED": False}),
+    trow("3x3_w_no_grad", X16 + (64,), 64, w_grad=False, chunks={C3_CHUNKS: 4}, **C3),
+    trow("3x3_torch_prep", X16 + (64,), 64, knobs={"USE_TORCH_OPERAND_PREP": True}, **C3),
+    trow("3x3_s2_torch_prep", X16 + (64,), 128, knobs={"USE_TORCH_OPERAND_PREP": True}, **C3S2),
+    # ---- fp32: conv_weight_rows, the implicit GEMM twice, the generic weight gradient with the fp32 code
+    trow("3x3.fp32", X16 + (64,), 64, dt="fp32", chunks={C3_CHUNKS: 4}, **C3),
+    trow("1x1.fp32", X8 + (128,), 32, dt="fp32", bias=False, chunks={LIN_CHUNKS: 3}),
+    trow("3x3_s2.fp32", X16 + (64,), 128, dt="fp32", **C3S2),
+    # ---- autograd.linear_weight: the rows as an H x W map
+    trow("linear_1024", (4, 256, 128), linear=(32, 128), as_conv=(4, 256, 128, 32)),
+    trow("linear_64", (64, 128), linear=(32, 128), bias=False, as_conv=(4, 16, 128, 32)),
+    trow("linear_48", (48, 128), linear=(32, 128), as_conv=(48, 1, 128, 32)),       # no candidate width leaves four map rows
+    trow("linear_k6_n5", (16, 6), linear=(5, 6), as_conv=(16, 1, 8, 8)),            # zero-padded to K = N = 8, run again
+    trow("linear.fp32", (64, 128), linear=(32, 128), dt="fp32", as_conv=(4, 16, 128, 32)),
+)
+
+
 def plan(r):
     """the ConvPlan of a row, on the CPU"""
     w = r["w"]

@@ -258,6 +258,41 @@ def _conv2d_table():
             ops.CONV3_VARIANT = old
 
 
+def _train_conv_table():
+    """every branch of the training convolution's routing (autograd.Conv2dFn forward + backward, autograd.linear_weight), one call per
+    row of cases_conv.TRAIN_ROWS on zero tensors; each row sets its own autograd switches, ops.CONV3_VARIANT and the fake library's
+    answers to the *_chunks questions, and restores them"""
+    import cases_conv as cv
+    status = _RECORDER.status
+    for r in cv.TRAIN_ROWS:
+        dtype = cv.DTYPES[r["dt"]]
+        old = {k: getattr(autograd, k) for k in r["knobs"]}
+        old_variant, old_status = ops.CONV3_VARIANT, dict(status)
+        _note("row", r["name"])
+        try:
+            for k, v in r["knobs"].items():
+                setattr(autograd, k, v)
+            ops.CONV3_VARIANT = r["variant"]
+            status.update(r["chunks"])
+            x = torch.zeros(r["x"], dtype=dtype, requires_grad=r["x_grad"])
+            cout = r["linear"][0] if r["linear"] else r["cout"]
+            bias = torch.zeros(cout, requires_grad=r["w_grad"]) if r["bias"] else None
+            with torch.enable_grad():
+                if r["linear"]:
+                    y = autograd.linear_weight(x, torch.zeros(r["linear"], requires_grad=r["w_grad"]), bias)
+                else:
+                    weight = torch.zeros((cout, r["x"][3], r["k"], r["k"]), requires_grad=r["w_grad"])
+                    y = autograd.Conv2dFn.apply(x.permute(0, 3, 1, 2), weight, bias, r["stride"], r["pad"])
+                if y.requires_grad:
+                    y.float().sum().backward()
+        finally:
+            status.clear()
+            status.update(old_status)
+            ops.CONV3_VARIANT = old_variant
+            for k, v in old.items():
+                setattr(autograd, k, v)
+
+
 CASES = {}
 for _mode in MODES:
     CASES["corpbevt_small.%s" % _mode] = _corpbevt(_mode)
@@ -270,6 +305,7 @@ CASES["corpbevt_small_train.fp32"] = _corpbevt_train
 CASES["voxelize_points"] = _voxelize
 CASES["detect_post_process"] = _detect_post
 CASES["conv2d_table"] = _conv2d_table
+CASES["train_conv_table"] = _train_conv_table
 
 
 def trace(name, setattr_, status=None):

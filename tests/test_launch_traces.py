@@ -7,7 +7,7 @@ import pytest
 import torch
 
 import launch_trace as lt
-from cobevt_amd import host, lib, ops
+from cobevt_amd import autograd, host, lib, ops
 from cobevt_amd.lib import CobevtHipError
 
 
@@ -79,6 +79,122 @@ def test_conv_route_agrees_with_the_recorded_table(monkeypatch):
         assert not (route.ln_fused and not plan.has_ln), r["name"]
     # one stride-2 fp32 plan, three libraries, three routes: the library is an input of the decision like any other
     assert [routes["c3_s2.fp32.lib" + v][::2] for v in ("native", "f32s", "f32h")] == [("strips", 131), ("igemm", 0), ("strips", 130)]
+
+
+# the entry point behind every word of autograd.train_conv_route ("chunked": by kernel size; it asks <symbol>_chunks first)
+TRAIN_SYMBOLS = {"rows": "cobevt_linear_rows_small_k", "strips": "cobevt_conv3x3_wfrag_nhwc", "conv3": "cobevt_conv3x3_nhwc",
+                 "igemm": "cobevt_conv2d_nhwc", "frags": "cobevt_linear_weight_frags", "pair": "cobevt_conv3_weight_operands2",
+                 "weight_rows": "cobevt_conv_weight_rows", "operand": "cobevt_conv3_weight_operands", "blocked": "cobevt_conv_wgrad_blocked",
+                 "generic": "cobevt_conv_wgrad", "chunked": {1: "cobevt_linear_wgrad", 3: "cobevt_conv_wgrad3"}}
+TRAIN_SWITCHES = ("USE_TRAIN_ROWS_GEMM", "USE_TRAIN_STRIPS", "USE_WGRAD3", "USE_WGRAD_BLOCKED", "USE_WGRAD_BLOCKED_STRIDED")
+
+
+def _dims(args):
+    """the integer vector among a launch's recorded arguments"""
+    return next((v for v in args if isinstance(v, list) and v and isinstance(v[0], int)), None)
+
+
+def _train_table():
+    """[(row of cases_conv.TRAIN_ROWS, its launches in the fixture)]"""
+    import cases_conv as cv
+    launched = []
+    for record in lt.read_fixture("train_conv_table"):
+        if record[1] == "row":
+            launched.append([])
+        else:
+            launched[-1].append(record)
+    assert [r["name"] for r in cv.TRAIN_ROWS] == [rec[2][0] for rec in lt.read_fixture("train_conv_table") if rec[1] == "row"]
+    return list(zip(cv.TRAIN_ROWS, launched))
+
+
+def _train_route(m, r, **switches):
+    """autograd.train_conv_route for a row under its own switches and strip pin, then `switches`"""
+    import cases_conv as cv
+    for knob, value in dict(r["knobs"], **switches).items():
+        m.setattr(autograd, knob, value)
+    m.setattr(ops, "CONV3_VARIANT", r["variant"])
+    return autograd.train_conv_route(ops.dcode(cv.DTYPES[r["dt"]]), *cv.train_conv_args(r))
+
+
+def test_train_conv_route_agrees_with_the_recorded_table(monkeypatch):
+    """autograd.train_conv_route names, for every row of the training table, exactly what the fixture (recorded before the function
+    existed) shows launched, in order: the operand preparation, the forward kernel and its strip variant, the input-gradient kernel and
+    its variant, the weight-gradient entry point under the row's chunk answers (with the blocked form at dims[9]) - all in the native
+    library, whichever one is the ambient one"""
+    import cases_conv as cv
+    for r, records in _train_table():
+        got = set()
+        for ambient in lib.VARIANTS:
+            with monkeypatch.context() as m:
+                m.setattr(lib, "_variant", ambient)
+                got.add(_train_route(m, r))
+        assert len(got) == 1, "%s: the route moves with lib.get_variant(): %s" % (r["name"], got)
+        route = got.pop()
+        k, cout = r["k"], cv.train_conv_args(r)[4]
+        torch_prep = r["knobs"].get("USE_TORCH_OPERAND_PREP", False)       # the torch-op specifications launch nothing
+        want = [(TRAIN_SYMBOLS[route.prep[0]], None), (TRAIN_SYMBOLS[route.fwd], route.var_f)]
+        want += [(TRAIN_SYMBOLS[call], None) for call in route.prep[1:]]
+        if torch_prep:
+            want = [item for item in want if item[0] != TRAIN_SYMBOLS["weight_rows"]]
+        if route.dgrad is not None:
+            want.append((TRAIN_SYMBOLS[route.dgrad], route.var_d))
+        for form in route.wgrad:
+            if form == "chunked":
+                want.append((TRAIN_SYMBOLS[form][k] + "_chunks", None))
+                if r["chunks"].get(want[-1][0], 0) > 0:
+                    want.append((TRAIN_SYMBOLS[form][k], None))
+                    break
+            else:
+                want += [("cobevt_wgrad_block_operand", None)] * (0 if (torch_prep or form != "blocked") else 2)
+                want.append((TRAIN_SYMBOLS[form], route.wgrad_mode))
+        if r["bias"] and r["w_grad"]:
+            want += [("cobevt_channel_sums", None)] + [("cobevt_f64_to_f32", None)] * bool(cout % 8)
+        assert [name for _, name, _ in records] == [name for name, _ in want], r["name"]
+        assert {variant for variant, _, _ in records} == {""}, r["name"]
+        for (_, name, args), (_, detail) in zip(records, want):
+            dims = _dims(args)
+            if name == TRAIN_SYMBOLS["strips"]:
+                assert detail == dims[11] > 0, r["name"]
+            elif name == TRAIN_SYMBOLS["conv3"]:
+                assert detail == 0, r["name"]
+            elif name == TRAIN_SYMBOLS["blocked"]:
+                assert detail == dims[9] and detail is not None, r["name"]
+            elif name == TRAIN_SYMBOLS["generic"]:
+                assert detail is None, r["name"]
+        if r["linear"]:       # the rows arrive as the H x W map the table states
+            maps = [_dims(args)[1:3] for _, name, args in records if name in ("cobevt_wgrad_block_operand", TRAIN_SYMBOLS["generic"])]
+            assert maps[0] == list(r["as_conv"][:2]), r["name"]
+    # the table reaches every word of the route and every blocked form
+    routes = [_train_route(monkeypatch, r) for r, _ in _train_table()]
+    words = {w for rt in routes for w in (rt.fwd, rt.dgrad) + rt.prep + rt.wgrad}
+    assert words == set(TRAIN_SYMBOLS) | {None} and {rt.wgrad_mode for rt in routes} == {None, 0, 1, 2}
+
+
+@pytest.mark.parametrize("switch", TRAIN_SWITCHES)
+def test_train_conv_route_moves_only_where_a_switch_governs(switch, monkeypatch):
+    """planted fault: with ONE switch off (all others at their defaults) the route changes for exactly the rows whose shape the fixture
+    shows on that switch's kernels - evidence from the rows recorded under default switches - and for no other row"""
+    import cases_conv as cv
+    evidence = {"USE_TRAIN_ROWS_GEMM": lambda name, dims: name == TRAIN_SYMBOLS["rows"],
+                "USE_TRAIN_STRIPS": lambda name, dims: name in (TRAIN_SYMBOLS["strips"], TRAIN_SYMBOLS["conv3"]),
+                "USE_WGRAD3": lambda name, dims: name.endswith("_chunks"),
+                "USE_WGRAD_BLOCKED": lambda name, dims: name == TRAIN_SYMBOLS["blocked"],
+                "USE_WGRAD_BLOCKED_STRIDED": lambda name, dims: name == TRAIN_SYMBOLS["blocked"] and dims[9] in (1, 2)}[switch]
+    key = lambda r: (r["dt"], r["variant"]) + cv.train_conv_args(r)          # noqa: E731  (what the route may depend on besides the switches)
+    governed = set()
+    for r, records in _train_table():
+        if not r["knobs"] and any(evidence(name, _dims(args)) for _, name, args in records):
+            governed.add(key(r))
+    assert governed, switch
+    defaults = {s: getattr(autograd, s) for s in TRAIN_SWITCHES}
+    moved = {}
+    for r, _ in _train_table():
+        plain = dict(r, knobs={})
+        with monkeypatch.context() as m:
+            before = _train_route(m, plain, **defaults)
+            after = _train_route(m, plain, **dict(defaults, **{switch: False}))
+        moved.setdefault(key(r), set()).add(before != after)
+    assert {k for k, v in moved.items() if v == {True}} == governed and all(len(v) == 1 for v in moved.values()), switch
 
 
 def test_failing_key_split_launch_names_its_own_symbol(monkeypatch):

@@ -52,7 +52,7 @@ def test_every_case_selects_what_the_parent_launched(program):
 
 def test_cases_file_is_the_table_plus_every_trace_record():
     """cases.txt is what the tool writes today: no case of the table left out, every distinct record of the five entry points in the
-    launch-trace fixtures in it (284 at present: 20 attn_mlp_chain, 262 linear_rows_small_k, 2 mean_linear_rows_small_k)"""
+    launch-trace fixtures in it (294 at present: 20 attn_mlp_chain, 272 linear_rows_small_k, 2 mean_linear_rows_small_k)"""
     assert open(fx.CASES).read().splitlines() == fx.table() + fx.trace_cases()
 
 

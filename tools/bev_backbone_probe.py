@@ -108,11 +108,10 @@ def train(dev, out_path):
         hw = 128 >> i
         xi, dz = torch.rand((1, hw, hw, cin), device=dev), torch.rand((1, hw * s, hw * s, 128), device=dev)
         dw = torch.zeros((cin, 128, s, s), device=dev)
-        dims = ops._ints([1, s * hw, s * hw, 128, hw, hw, cin, s, s, 0, ops.FP32])
 
         def atomics():
             dw.zero_()
-            ag._call("cobevt_conv_wgrad", ops._p(dz), ops._p(xi), ops._p(dw), dims, ops._stream())
+            ag._launch_conv_wgrad(dz, xi, dw, s, s, 0)
         new = ops.deconv_wgrad(xi, dz, s)
         atomics()
         res["deconv_wgrad_ms"].append({"s": s, "cin": cin, "cout": 128, "pixels": hw * hw, "chunks": ops.deconv_wgrad_chunks(1, hw, hw, cin, 128, s),
