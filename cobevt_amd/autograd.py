@@ -152,7 +152,8 @@ class WindowAttentionFn(torch.autograd.Function):
         d = heads * 32
         dout = _f32c(dout, "dout")
         dl = _f32c(dlse, "dlse") if (want_lse and dlse is not None) else None
-        # dq is accumulated with atomics by the key tiles of a window; dk / dv rows are written once each
+        # dq / dk / dv rows are written once each, with no atomics (attention_bwd.hip's header; tests/test_attn_bwd_bounds_gpu.py pins it on
+        # sentinel-filled buffers); only dbias is accumulated with atomics and must start at zero
         dq = _zeros((q.shape[0], d), q.device, torch.float32)
         dk = _zeros((k.shape[0], d), q.device, torch.float32)
         dv = _zeros((v.shape[0], d), q.device, torch.float32)

@@ -54,7 +54,8 @@ test_rows_bounds.py::test_layernorm_folding_of_the_plans checks it on its own ag
 Left out, by name:
   bev_embed / bev_query (gemm_rows3_kernel<true, 32>, bev_query_kernel<4>): the embedding's geometry needs another reference;
       test_bev_query_wave_level_kernel stays.
-  swap_stage.hip: it has an attention inside.
+  swap_stage.hip: it has an attention inside.  The attention bound it was waiting for now exists for the backward kernels (DESIGN.md
+      section 3z, tests/attn_bwd_ref.py); the forward families, this one among them, are still without one.
   swish and sigmoid epilogues (act 3, 4): no derivation yet.
   row_chain64_kernel<NNT, 6, true> and <NNT, 6, false> (NNT 0, 2, 4, 6): reached only through COBEVT_RC64_PREFETCH, an environment gate
       read once per process.
